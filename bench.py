@@ -9,12 +9,18 @@ N>1: one rank per GPU.  Started without a torch.distributed environment (no WORL
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...`;
 started by torch.distributed.run (the driver's form) it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env.
 
-Prints ONE JSON line on rank 0 (the last line of stdout).  `roofline` prices the dominant single-shape kernel of the step
+Prints ONE JSON line on rank 0 (the last line of stdout).  A plain run sets up, warms up, times the K steps and prints the
+line; its `roofline` prices one whole step (79.478 GFLOP per image) against the dense MFMA peak from
+the HIP events of the timed region.  `--dump-outputs DIR` writes what the last timed step handed its caller (losses, heat-maps,
+updated student state) as .npy files; inputs and weights are seeded, so two builds can be compared output for output.
+
+Everything else takes runs of its own and is measured only with `--full`:
+`roofline` then prices the dominant single-shape kernel of the step
 -- the fused frozen Bottleneck of the teacher at 64x64 (17 launches/step: 9 alone, 8 paired with a 32x32 one; the largest
 single (kernel, shape) entry of the rocprof trace) -- with its algorithmic conv FLOPs against the dense bf16 MFMA peak,
-timed live with HIP events on the launch stream; `roofline.step` prices one whole step (79.478 GFLOP per image, SURVEY.md
-section 8(d)) the same way; `roofline.conv_classes` lists the costliest convolution classes of the step, each timed from
-the step's own plan (`--config hrnet`: its top entry IS the roofline kernel).
+timed live with HIP events on the launch stream; `roofline.step` is the step figure above; `roofline.conv_classes` lists the
+costliest convolution classes of the step, each timed from the step's own plan (`--config hrnet`: its top entry IS the
+roofline kernel).  `phase_times`, the host enqueue time of one step and the bf16-vs-fp32 `parity` object follow.
 `cpu_baseline` times the CPU oracle (restatement of the reference loop) on a bounded sample of the same workload on the
 host cores: thread count swept per configuration, both the reference-faithful variant (teacher graph retained,
 function.py:120) and the teacher-under-no_grad variant, 3 timed steps each at cfg-1 (hg2x64, B=2) and the benchmark pair (B=8).
@@ -60,6 +66,14 @@ def make_cfg(feats, stacks, joints, dtype):
     return AD(MODEL=AD(NUM_JOINTS=joints, DTYPE=dtype, EXTRA=AD(NUM_FEATURES=feats, NUM_STACKS=stacks, NUM_BLOCKS=1)))
 
 
+def host_cpus():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS when that is set (a shared host can show many
+    more cores than a job is given, and threads beyond them only slow the oracle down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    omp = os.environ.get('OMP_NUM_THREADS', '')
+    return min(n, int(omp)) if omp.isdigit() and int(omp) > 0 else n
+
+
 def _cpu_time(pair, batch, steps, no_grad, seed=0):
     """seconds/step of the CPU oracle (port of lib/core/function.py:114-147 over the restated hourglass)."""
     from oracle import fpd_ref, hourglass_ref
@@ -83,7 +97,7 @@ def cpu_baseline():
     timed with its best count for 3 steps after one warm-up, both with the teacher under no_grad and reference-faithful
     (teacher graph retained, function.py:120; fewer steps, and said so, if the ~100 s budget is exhausted).  `value` =
     images/s of the benchmark pair with the teacher under no_grad (the faster variant: the stronger baseline)."""
-    ncpu = os.cpu_count() or 1
+    ncpu = host_cpus()
     cfg1, pair = ((64, 2), (64, 2)), ((128, 4), (256, 8))
     t_begin = time.time()
 
@@ -129,7 +143,7 @@ def cpu_baseline_hrnet():
     """The same loop of the CPU oracle (function.py:114-147) over the HRNet restatement (oracle/hrnet_ref.py): W32 student,
     W48 teacher, 256x192, J=17 at batch 2 -- 3 timed steps after one warm-up, teacher under no_grad and reference-faithful."""
     from oracle import fpd_ref, hrnet_ref
-    ncpu = os.cpu_count() or 1
+    ncpu = host_cpus()
     ex_s, ex_t = hr_extra([32, 64, 128, 256]), hr_extra([48, 96, 192, 384])
     fs = lambda sd, x, train: [hrnet_ref.hrnet_forward(sd, ex_s, x, train)]
     ft = lambda sd, x, train: [hrnet_ref.hrnet_forward(sd, ex_t, x, train)]
@@ -366,6 +380,35 @@ def parity_object(build_pair, E, student, teacher, batch, dev, H, W):
     return res
 
 
+DUMP_BYTES = 60 * 10 ** 6           # --dump-outputs budget over all arrays
+
+
+def dump_outputs(step, out_dir):
+    """What the last timed step handed its caller, as .npy files in `out_dir`: losses.npy (pose, kd, total; float64),
+    student_heatmap.npy / teacher_heatmap.npy (the student's last-stack map and the teacher map it was distilled against, NCHW
+    float32), student_params.npy / student_running_stats.npy (the flat parameter arena after Adam and the BN running statistics,
+    float32).  An array larger than its share of DUMP_BYTES is replaced by a fixed seeded sample of its flattened elements."""
+    import numpy as np
+    s, A = step.student, step.student.state.A
+    t_shape = step.teacher.g.outputs[-1].shape if step.teacher is not None else None
+    arrays = {'losses': np.array(step.losses(), dtype=np.float64),
+              'student_heatmap': s.output_view(len(s.g.outputs) - 1).permute(0, 3, 1, 2).float().cpu().numpy()}
+    if t_shape is not None:             # the slot the last student step read (student_step: slot = k % 2)
+        tmap = step.tmap[(step._k_s - 1) % 2].view(-1, *t_shape[1:])
+        arrays['teacher_heatmap'] = tmap.permute(0, 3, 1, 2).float().cpu().numpy()
+    arrays['student_params'] = A.tensor('param').float().cpu().numpy()
+    arrays['student_running_stats'] = A.tensor('rstat').float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -427,9 +470,13 @@ def main():
                          "HRNet-W48 teacher, 256x192, J=17; hrnet_fp8 = configs[4] shapes: the same pair at 384x288 with the "
                          "student's forward convolutions on the fp8 matrix pipe (secondary lines: step-level roofline only)")
     ap.add_argument('--no-fp8', action='store_true', help='hrnet_fp8 shapes with bf16 forward convolutions (same-shape A/B of the fp8 path)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true', help='skip the bf16-vs-fp32-build parity sub-object')
-    ap.add_argument('--no-phase-times', action='store_true', help='skip the per-phase / lane timing after the timed region')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure the dominant kernel and convolution classes, phase times, host enqueue '
+                         'time, bf16-vs-fp32 parity and the CPU baseline (off: the headline line only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the bf16-vs-fp32-build parity sub-object')
+    ap.add_argument('--no-phase-times', action='store_true', help='with --full: skip the per-phase / lane timing after the timed region')
     ap.add_argument('--graphs', action='store_true',
                     help='replay each phase as a hipGraph instead of launching kernel by kernel (same GPU time; with more\n'
                          'than 4 hardware queues ROCm 7.2 graph replay of multi-stream phases is pathologically slow)')
@@ -437,6 +484,8 @@ def main():
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise the RCCL process group and use the all-reduce path even with one rank (path check)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         self_launch(args.gpus)                     # does not return
@@ -499,7 +548,7 @@ def main():
     torch.cuda.empty_cache()
 
     init_sd = None
-    if rank == 0 and args.dtype == 'bf16' and not args.no_parity:     # snapshot for the parity sub-object (after the timed region)
+    if args.full and rank == 0 and args.dtype == 'bf16' and not args.no_parity:     # snapshot for the parity sub-object (after the timed region)
         init_sd = ({k: v.detach().cpu().clone() for k, v in student.state_dict().items()},
                    {k: v.detach().cpu().clone() for k, v in teacher.state_dict().items()})
     step = E.FusedFPDStep(student.device_state(), student.cfg_hg, teacher.device_state(), teacher.cfg_hg, B, H, W,
@@ -535,12 +584,16 @@ def main():
     wall = time.time() - t0
     ev_ms = l.fpd_event_elapsed_ms(ev0, ev1)
     pose, kd, loss = step.losses()
-    # host launch path, measured where nothing can block it: ONE step enqueued into empty queues after the timed region
-    # (every kernel launch, event record / wait of one teacher forward + one student step), clock stopped before any sync
-    t1 = time.time()
-    step.run_pipelined(1, allreduce)
-    host_enqueue_ms = (time.time() - t1) * 1e3
-    barrier()
+    if args.dump_outputs and rank == 0:             # before anything below runs the step again
+        dump_outputs(step, args.dump_outputs)
+    host_enqueue_ms = None
+    if args.full:
+        # host launch path, measured where nothing can block it: ONE step enqueued into empty queues after the timed region
+        # (every kernel launch, event record / wait of one teacher forward + one student step), clock stopped before any sync
+        t1 = time.time()
+        step.run_pipelined(1, allreduce)
+        host_enqueue_ms = round((time.time() - t1) * 1e3, 3)
+        barrier()
     if use_dist:
         t = torch.tensor([wall], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -555,9 +608,9 @@ def main():
                  'note': 'one replay of the whole FPD step plan on one GPU: %.3f TFLOP algorithmic conv work (%.3f '
                          'GFLOP/image x %d), HIP events on the launch stream: %.3f ms/step' % (flop_step / 1e12, gfl, B,
                                                                                               ev_ms / args.steps)}
-    dom = dominant_kernel(step, R) if (rank == 0 and args.dtype == 'bf16' and not hr) else None
+    dom = dominant_kernel(step, R) if (args.full and rank == 0 and args.dtype == 'bf16' and not hr) else None
     classes = None
-    if rank == 0 and args.dtype == 'bf16' and not args.graphs:
+    if args.full and rank == 0 and args.dtype == 'bf16' and not args.graphs:
         top, total_ms = conv_classes(step, R, peak)
         classes = {'top': top, 'all_classes_ms_per_step_serialised': total_ms,
                    'note': 'un-paired convolution launches of the step by (role, kind, shape): one recorded op of the step\'s own '
@@ -608,7 +661,7 @@ def main():
                     'frac': step_roof['frac'], 'traffic': None, 'note': step_roof['note']}
     if classes is not None:
         roofline['conv_classes'] = classes
-    phases = phase_times(step, R) if (rank == 0 and world == 1 and not args.graphs and not args.no_phase_times) else None
+    phases = phase_times(step, R) if (args.full and rank == 0 and world == 1 and not args.graphs and not args.no_phase_times) else None
     out = {
         'metric': ('images/sec FPD train step (HRNet-W32 student with fp8 forward convolutions, HRNet-W48 teacher) 384x288' if f8 else
                    'images/sec FPD train step (HRNet-W32 student, HRNet-W48 teacher) 256x192' if hr else
@@ -625,7 +678,7 @@ def main():
                                'fused FPD step incl. Adam, teacher forward one batch ahead on a 2nd stream%s' % (' + RCCL all-reduce' if use_dist else ''),
                    'global_batch': world * B, 'parallelism': 'dp%d' % world, 'backend': args.backend,
                    'launch': 'hipGraph replay per phase' if args.graphs else 'one native plan call per phase, kernels launched eagerly on 3 streams',
-                   'host_enqueue_ms_per_step': round(host_enqueue_ms, 3),
+                   'host_enqueue_ms_per_step': host_enqueue_ms,
                    'host_ms_per_step_inside_timed_region': round(host_busy_ms, 3),
                    'launches_per_step': step.launches_per_step(),
                    'ranks': world,
@@ -644,13 +697,13 @@ def main():
             'ONE asynchronous RCCL all-reduce of the flat gradient arena (%d fp32 elements) issued behind the backward, waited for before Adam '
             '(overlaps the next teacher forward); FPD_ALLREDUCE_BUCKETS=1 = one per bucket' % student.table.sizes['param'])
         out['config']['gpu_max_hw_queues'] = os.environ.get('GPU_MAX_HW_QUEUES')
-    if rank == 0:
+    if args.full and rank == 0:
         print('[bench] timed region done: %.3f ms/step; parity / cpu baseline next' % ms_per_step, file=sys.stderr, flush=True)
     if init_sd is not None:
         del step
         torch.cuda.empty_cache()
         out['parity'] = parity_object(build_pair, E, init_sd[0], init_sd[1], (x, tg, tw), dev, H, W)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         t_cpu = time.time()
         out['cpu_baseline'] = cpu_baseline_hrnet() if hr else cpu_baseline()
         print('[bench] cpu baseline took %.1f s' % (time.time() - t_cpu), file=sys.stderr, flush=True)

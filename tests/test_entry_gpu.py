@@ -289,3 +289,23 @@ def test_graft_entry_smoke_runs_in_a_fresh_process():
     p = subprocess.run([sys.executable, '-c', 'import __graft_entry__ as g; g.smoke()'], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert 'smoke ok' in p.stdout, p.stdout[-2000:]
+
+
+def test_plain_bench_run_prints_the_headline_line_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line only (the measurements of --full are absent),
+    K timed steps, and the last step's losses / maps / student state as float .npy files within the 64 MB budget."""
+    d = str(tmp_path / 'out')
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', d],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line['unit'] == 'images/s' and line['higher_is_better'] is True and line['dtype'] == 'bf16' and line['steps'] == 3
+    assert line['value'] > 0 and abs(line['value'] - 32 * 1e3 / line['ms_per_step']) < 0.01 * line['value']
+    assert not {'phase_times', 'parity', 'cpu_baseline'} & set(line) and 'conv_classes' not in line['roofline']
+    files = sorted(os.listdir(d))
+    assert files == ['losses.npy', 'student_heatmap.npy', 'student_params.npy', 'student_running_stats.npy', 'teacher_heatmap.npy']
+    arrays = {f: np.load(os.path.join(d, f)) for f in files}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert arrays['student_heatmap.npy'].shape == arrays['teacher_heatmap.npy'].shape == (32, 16, 64, 64)
+    assert abs(arrays['losses.npy'][2] - line['config']['loss_last_step']) < 1e-5

@@ -138,6 +138,40 @@ def test_bench_picks_the_hardware_queue_count_before_torch_loads(argv, env, want
     assert out.stdout.strip() == want
 
 
+def test_bench_dump_outputs_writes_the_last_step_within_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the losses, the student's last-stack map and the teacher map of the slot the last student step read
+    (NCHW), the parameters and running statistics -- float32 / float64 .npy files; an array beyond its share of the byte budget is
+    replaced by the same seeded sample on every run.  Here on a stand-in for the fused step (CPU tensors)."""
+    import types
+    import numpy as np
+    import torch
+    monkeypatch.setenv('GPU_MAX_HW_QUEUES', os.environ.get('GPU_MAX_HW_QUEUES', '4'))     # importing bench must not change it
+    import bench
+    B, H, W, J = 2, 8, 6, 3
+    gen = torch.Generator().manual_seed(0)
+    g = types.SimpleNamespace(outputs=[types.SimpleNamespace(shape=(B, H, W, J))] * 2)
+    maps = [torch.randn(B, H, W, J, generator=gen).bfloat16() for _ in range(2)]
+    tmap = [torch.randn(B * H * W * J, generator=gen).bfloat16() for _ in range(2)]
+    arenas = {'param': torch.randn(5000, generator=gen), 'rstat': torch.rand(40, generator=gen)}
+    student = types.SimpleNamespace(g=g, output_view=lambda i: maps[i],
+                                    state=types.SimpleNamespace(A=types.SimpleNamespace(tensor=lambda name: arenas[name])))
+    step = types.SimpleNamespace(student=student, teacher=types.SimpleNamespace(g=g), tmap=tmap, _k_s=3, losses=lambda: (0.25, 0.5, 0.375))
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 8000)
+    bench.dump_outputs(step, str(tmp_path / 'a'))
+    bench.dump_outputs(step, str(tmp_path / 'b'))
+    got = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert sorted(got) == ['losses', 'student_heatmap', 'student_params', 'student_running_stats', 'teacher_heatmap']
+    assert got['losses'].dtype == np.float64 and got['losses'].tolist() == [0.25, 0.5, 0.375]
+    assert all(a.dtype == np.float32 for k, a in got.items() if k != 'losses')
+    assert np.array_equal(got['student_heatmap'], maps[1].float().permute(0, 3, 1, 2).numpy())
+    assert np.array_equal(got['teacher_heatmap'], tmap[0].float().view(B, H, W, J).permute(0, 3, 1, 2).numpy())    # slot of step 3
+    assert np.array_equal(got['student_running_stats'], arenas['rstat'].numpy())
+    p = got['student_params']
+    assert sum(a.nbytes for a in got.values()) <= 8000 and 0 < p.size < 5000 and np.isin(p, arenas['param'].numpy()).all()
+    for k, a in got.items():                        # the same sample every time
+        assert np.array_equal(a, np.load(str(tmp_path / 'b' / (k + '.npy'))))
+
+
 def test_isa_report_splits_a_listing_into_kernels_and_basic_blocks():
     """tools/isa_report.py (static instruction counts: the issue-bound model of DESIGN.md section 8 makes them a time estimate)."""
     import isa_report
