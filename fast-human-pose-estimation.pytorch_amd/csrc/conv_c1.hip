@@ -637,7 +637,10 @@ int c1_fuse_wgrad() { return 1; }
 bool c1_chan(int c) { return c == 32 || c == 64 || c == 128; }
 bool c1_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-bool c1_domain(const fpd_conv_t& a) {
+// folded: decide for the launch as it will be made WITH a folded BN-backward apply, whatever a.fold_x holds now (the fold query
+// is asked before the caller fills in the fold fields: include/fpd_amd.h, fpd_conv_fold_supported())
+bool c1_domain(const fpd_conv_t& a, bool folded = false) {
+    const bool fold = folded || a.fold_x != nullptr;
     if (a.dtype != FPD_BF16 || a.R != 1 || a.S != 1 || a.stride != 1 || a.pad != 0 || a.P != a.H || a.Q != a.W) return false;
     // (16 -> 128: the inter-stack score_ convolution and the data gradient of the score convolution, hourglass.py:136-137, one k-step)
     if (!(c1_chan(a.C) || (a.C == 16 && a.K == 128)) || !c1_chan(a.K)) return false;
@@ -648,10 +651,10 @@ bool c1_domain(const fpd_conv_t& a) {
     if (a.epi == FPD_EPI_BNRELU_BWD) {
         // the data gradients of the hot path: no bias, no accumulate source, no prologue BN; dW tiles for every wave
         if (a.bias != nullptr || a.residual != nullptr || a.bn.mode != FPD_BN_NONE) return false;
-        if (a.C == 16) { if (a.fold_x != nullptr) return false; }      // (no dW tiles: its weight gradient stays a separate launch)
+        if (a.C == 16) { if (fold) return false; }                    // (no dW tiles: its weight gradient stays a separate launch)
         // 128 <-> 64 with the fused weight gradient; 128 x 128 (the dy + a(u) tiles of 8 waves do not fit the LDS) as a plain data
         // gradient, its weight gradient a launch of its own on the lane
-        else if ((a.C / 32) * (a.K / 32) != C1_NW && !(a.C == 128 && a.K == 128 && a.fold_x == nullptr)) return false;
+        else if ((a.C / 32) * (a.K / 32) != C1_NW && !(a.C == 128 && a.K == 128 && !fold)) return false;
     } else {
         if (a.epi != FPD_EPI_PLAIN || a.fold_x != nullptr || a.wg_partial != nullptr) return false;
         if (a.y == a.x) return false;
@@ -663,12 +666,12 @@ bool c1_wg_shape(const fpd_conv_t& a) {
 }
 int c1_rounds(const fpd_conv_t& a) { return cdiv(a.N * a.H * a.W / 32, C1_NW); }
 
-bool c1_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
+bool c1_takes(const fpd_conv_t& a, const fpd_conv_t* b, bool folded = false) {
     const int mode = c1_mode();
-    if (mode == 0 || !c1_domain(a)) return false;
+    if (mode == 0 || !c1_domain(a, folded)) return false;
     long long px = (long long)a.N * a.H * a.W;
     if (b != nullptr) {
-        if (!c1_domain(*b) || a.K != b->K || a.C != b->C || a.epi != b->epi) return false;
+        if (!c1_domain(*b, folded) || a.K != b->K || a.C != b->C || a.epi != b->epi) return false;
         if ((a.residual != nullptr) != (b->residual != nullptr)) return false;      // (the residual is a template parameter)
         px += (long long)b->N * b->H * b->W;
     }
@@ -782,11 +785,12 @@ int fpd_conv_c1_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_
     if (!c1_takes(a, &b)) return 1;
     return c1_launch(a, &b, st);
 }
-// 1 if the launch (pair) is served by this kernel as a BNRELU_BWD data gradient: a folded BN-backward apply is a run-time flag
+// 1 if the launch (pair) WITH a folded BN-backward apply is served by this kernel as a BNRELU_BWD data gradient (the fold is a
+// run-time flag of the FOLD variants; 16 -> 128 and 128 x 128 have none and are taken only unfolded)
 int fpd_conv_c1_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b) {
     if (a.epi != FPD_EPI_BNRELU_BWD || (b != nullptr && b->epi != FPD_EPI_BNRELU_BWD)) return 0;
     C1Plan pl;
-    return (c1_takes(a, b) && c1_plan(a, b, false, pl)) ? 1 : 0;
+    return (c1_takes(a, b, true) && c1_plan(a, b, false, pl)) ? 1 : 0;
 }
 // -1 = this kernel does not take the launch (ask the next kernel); else the slabs of the fused weight gradient (0: served
 // here, but without the fusion)

@@ -145,6 +145,11 @@ def test_host_side_dispatch_predicates_of_round_3_without_a_device(runtime):
     assert fold(_conv(R, 4, 64, 64, 64, 128, 1)) == 0
     lib.fpd_set_option(b'conv_c1', prev_c1)
     assert fold(_conv(R, 2, 16, 16, 64, 128, 1)) == 1          # 512 pixels: below conv_c1's threshold, 4 tiles of the halo-tile kernel
+    # 128 -> 128 and 16 -> 128 data gradients: conv_c1 serves them only unfolded (no FOLD variant); at 16 384 pixels conv_pp
+    # declines (128 tiles) and the halo-tile kernel runs them at TN = 4: nothing serves the launch folded.  From 256 tiles conv_pp does
+    assert fold(_conv(R, 4, 64, 64, 128, 128, 1)) == 0
+    assert fold(_conv(R, 4, 64, 64, 16, 128, 1)) == 0
+    assert fold(_conv(R, 32, 64, 64, 128, 128, 1)) == 1
     assert fold(_conv(R, 32, 64, 64, 64, 64, 3, bwd=False)) == 0        # not a BNRELU_BWD data gradient
     assert fold(_conv(R, 32, 64, 64, 64, 64, 3, bn=True)) == 0          # a prologue BN of its own
     pair = R.ConvPairT()

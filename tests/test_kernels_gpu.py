@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import plan_interp as PI
+from tests._fold_ops import bn_backward_dgrad_ops
 from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -346,44 +347,10 @@ def test_conv_pp_dgrad_with_folded_bn_backward_apply(case, forced):
     ReLU mask and sums, the convolution's weight / bias gradient (fused into the launch for 1x1, a separate launch reading
     the materialised operand for 3x3), the BN's dgamma / dbeta -- must match the specification of the un-folded op list."""
     N, H, W, C, K, Rr, blocks, bias = case                # forward convolution u = conv(a(x)), C -> K, then bn_next(u)
-    pad = (Rr - 1) // 2
     gen = torch.Generator().manual_seed(53 + sum(case[:7]))
     bt = Bench(1)
-    x_val = rnd(gen, N, H, W, C)
-    x = bt.act((N, H, W, C), x_val, 'x')                  # forward input of the convolution (pre BN+ReLU)
-    u_val = rnd(gen, N, H, W, K)
-    u = bt.act((N, H, W, K), u_val, 'u')                  # its output = input of the next BN
-    g_val = rnd(gen, N, H, W, K, scale=0.1)
-    g = bt.act((N, H, W, K), g_val, 'g')                  # masked gradient that reached that BN
-    wm = bt.buf('param', (K, Rr, Rr, C), rnd(gen, K, Rr, Rr, C, scale=1.0 / np.sqrt(C * Rr * Rr)))
-    wb = bt.buf('wlp', (C, Rr, Rr, K))
-    du = bt.act((N, H, W, K), None, 'du')
-    dz = bt.act((N, H, W, C), None, 'dz')
-    bn = make_bn(bt, gen, C, 'train')                     # BN in front of the convolution (mask + sums of the data gradient)
-    bn.count = N * H * W
-    bn.stats = bt.buf('stats', (RS, 2, C), tensor_stats(x_val.to(torch.bfloat16).float()))
-    bn2 = make_bn(bt, gen, K, 'train')                    # the BN whose backward is folded
-    bn2.count = N * H * W
-    bn2.stats = bt.buf('stats', (RS, 2, K), tensor_stats(u_val.to(torch.bfloat16).float()))
-    gq, uq = g_val.to(torch.bfloat16).float(), u_val.to(torch.bfloat16).float()
-    mean, var = uq.mean((0, 1, 2)), uq.var((0, 1, 2), unbiased=False)
-    xhat = (uq - mean) / torch.sqrt(var + 1e-5)
-    sums = torch.zeros(RS, 2, K, dtype=torch.float64)
-    sums[0, 0], sums[0, 1] = gq.double().sum((0, 1, 2)), (gq.double() * xhat.double()).sum((0, 1, 2))
-    bst2 = bt.buf('stats', (RS, 2, K), sums)
-    dgam, dbet = bt.buf('grad', (K,), torch.zeros(K)), bt.buf('grad', (K,), torch.zeros(K))
-    bst = bt.buf('stats', (RS, 2, C), torch.zeros(RS, 2, C, dtype=torch.float64))
-    dw = bt.buf('grad', (K, Rr, Rr, C), torch.zeros(K, Rr, Rr, C))
-    db = bt.buf('grad', (K,), torch.zeros(K)) if bias else None
-    ap = G.Op('ew', op='bn_bwd_apply', dims=(N, H, W, K), x=u, x2=None, dy=g, add=None, y=du, out_stats=None, bstats=bst2,
-              dgamma=dgam, dbeta=dbet, bn=bn2)
-    wg = G.Op('wgrad', x=x, dy=du, dw=dw, dbias=db, bn=bn, dims=(N, H, W, C, K, Rr, Rr, 1, pad, H, W))
-    dg = G.Op('conv', x=du, w=wb, wkey='w', bias=None, bkey=None, residual=None, y=dz, out_stats=None, bn=None,
-              epi='bnrelu_bwd', epi_x=x, epi_bn=bn, epi_stats=bst, dims=(N, H, W, K, C, Rr, Rr, 1, Rr - 1 - pad, H, W))
-    dg.fold_apply, dg.fold_wgrad = ap, wg
-    if Rr == 1:
-        dg.fused_wgrad = wg
-    ops = [G.Op('wprep', entries=[{'w': wm, 'w_fwd': None, 'w_bwd': wb}]), ap, dg, wg]
+    ops, o = bn_backward_dgrad_ops(bt, gen, N, H, W, C, K, Rr, bias)
+    dg, dz, bst, dgam, dbet, dw, db, du = (o[k] for k in ('dg', 'dz', 'bst', 'dgam', 'dbet', 'dw', 'db', 'du'))
     # forced: the persistent kernel for every shape; else the default dispatch (persistent kernel from 256 tiles, halo-tile below)
     bt.realise().run(ops, ('pp', blocks) if forced else 0, partials=True)
     # (default dispatch: a mid-sized launch of the halo-tile kernel with 128 output channels per block has no FOLD variant --
