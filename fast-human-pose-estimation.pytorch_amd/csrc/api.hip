@@ -7,73 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
-
-int fpd_conv_mfma_launch(const fpd_conv_t& a, hipStream_t st);
-int fpd_conv_tile_launch(const fpd_conv_t& a, hipStream_t st);
-int fpd_conv_pp_launch(const fpd_conv_t& a, hipStream_t st);
-int fpd_conv_c1_launch(const fpd_conv_t& a, hipStream_t st);
-int fpd_conv_c3_launch(const fpd_conv_t& a, hipStream_t st);
-int fpd_conv_c3_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st);
-int fpd_conv_c3_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b);
-int fpd_conv_c3_option(int which, int value);
-int fpd_conv_c1_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st);
-int fpd_conv_c1_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b);
-int fpd_conv_c1_option(int which, int value);
-int fpd_conv_c1_wgrad_partials(const fpd_conv_t& a);
-int fpd_conv_c1_pair_wgrad_partials(const fpd_conv_t& a, const fpd_conv_t& b, int* na, int* nb);
-int fpd_conv_pp_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st);
-int fpd_conv_pp_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b);
-int fpd_conv_tile_fold_ok(const fpd_conv_t& a);
-int fpd_conv_tile_pair_fold_ok(const fpd_conv_t& a, const fpd_conv_t& b);
-int fpd_conv_pp_option(int which, int value);
-int fpd_conv_pp_wgrad_partials(const fpd_conv_t& a);
-int fpd_conv_pp_pair_wgrad_partials(const fpd_conv_t& a, const fpd_conv_t& b, int* na, int* nb);
-int fpd_conv_tile_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st);
-int fpd_bneck_fused_launch(const fpd_bneck_t& a, hipStream_t st);
-int fpd_bneck_fold_launch(const fpd_bneck_t& a, float* out, hipStream_t st);
-int fpd_pck_launch(const fpd_pck_t& a, hipStream_t st);
-int fpd_conv_smallc_launch(const fpd_conv_t& a, hipStream_t st);
-bool fpd_conv_f8_domain(const fpd_conv_t& a);
-int fpd_conv_tile_f8_launch(const fpd_conv_t& a, const void* w8, const float* wscale, hipStream_t st);
-int fpd_weight_quant_f8_launch(const fpd_wquant_entry_t* table, int n, hipStream_t st);
-int fpd_flip_w_launch(const float* x, float* y, int64_t rows, int W, hipStream_t st);
-int fpd_flip_merge_launch(const fpd_flipmerge_t& p, hipStream_t st);
-int fpd_final_preds_launch(const fpd_finalpreds_t& p, hipStream_t st);
-int fpd_render_targets_launch(const fpd_targets_t& a, hipStream_t st);
-int fpd_warp_affine_launch(const fpd_warp_t& a, hipStream_t st);
-int fpd_head_fused_launch(const fpd_head_t& a, hipStream_t st);
-int fpd_head_fold_launch(const fpd_head_t& a, float* out, hipStream_t st);
-int fpd_bneck_fused_pair_launch(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st);
-int fpd_wgrad_mfma_launch(const fpd_wgrad_t& a, hipStream_t st);
-int fpd_wgrad_tile_launch(const fpd_wgrad_t& a, hipStream_t st);
-int fpd_wgrad_tile_partials(const fpd_wgrad_t& a);
-int fpd_wgrad_smallc_launch(const fpd_wgrad_t& a, hipStream_t st);
-int fpd_wgrad_smallc_partials(const fpd_wgrad_t& a);
-int fpd_wgrad_mfma_partials(const fpd_wgrad_t& a);
-int fpd_wgrad_naive_partials(const fpd_wgrad_t& a);
-int fpd_stem_wgrad_mfma_partials(const fpd_stem_t& a);
-int fpd_stem_wgrad_partials(const fpd_stem_t& a);
-int fpd_wreduce_launch(const fpd_wreduce_entry_t* table, int n, int64_t max_elems, hipStream_t st);
-int fpd_conv_naive_launch(const fpd_conv_t& a, hipStream_t st);
-int fpd_wgrad_naive_launch(const fpd_wgrad_t& a, hipStream_t st);
-int fpd_stem_forward_launch(const fpd_stem_t& a, hipStream_t st);
-int fpd_stem_forward_mfma_launch(const fpd_stem_t& a, hipStream_t st);
-int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st);
-int fpd_stem_wgrad_s2d_launch(const fpd_stem_t& a, hipStream_t st);
-int fpd_stem_wgrad_s2d_partials(const fpd_stem_t& a);
-int fpd_stem_wgrad_mfma_launch(const fpd_stem_t& a, hipStream_t st);
-int fpd_stem_wgrad_launch(const fpd_stem_t& a, hipStream_t st);
-int fpd_elementwise_launch(const fpd_ew_t& a, hipStream_t st);
-int fpd_elementwise_pair_launch(const fpd_ew_t& a, const fpd_ew_t& b, hipStream_t st);
-int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st);
-int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
-int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st);
-int fpd_weight_prep_launch(const fpd_wprep_entry_t* table, int n, int64_t max_elems, int dtype, hipStream_t st);
-int fpd_bn_update_running_launch(const fpd_bnupd_entry_t* table, int n, hipStream_t st);
-int fpd_cast_launch(const void* src, void* dst, int64_t n, int sd, int dd, hipStream_t st);
-int fpd_nchw_to_nhwc_launch(const float* src, void* dst, int N, int C, int H, int W, int dtype, hipStream_t st);
-int fpd_nhwc_to_nchw_launch(const void* src, float* dst, int N, int C, int H, int W, int dtype, hipStream_t st);
+#include "conv_dispatch.h"
 
 int g_fpd_backend = FPD_BACKEND_MFMA;
 static thread_local char g_err[512] = "";
@@ -167,56 +101,90 @@ static int validate_conv(const fpd_conv_t* a) {
     return 0;
 }
 
-static int dispatch_conv(const fpd_conv_t* a, hipStream_t st) {
-    int rc = 1;
-    if (g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_c1_launch(*a, st);      // big maps, 1x1: streaming kernel
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_c3_launch(*a, st);      // big maps, 3x3 64 -> 64: strip kernel
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_pp_launch(*a, st);      // big maps: persistent kernel
-    FPD_REQUIRE(rc != 1 || a->wg_partial == nullptr, "conv: a fused weight gradient (wg_partial) needs the persistent kernel; "
-                "fpd_conv_fused_wgrad_partials() reports 0 for this launch");
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_tile_launch(*a, st);
-    FPD_REQUIRE(rc != 1 || a->fold_x == nullptr, "conv: a folded BN-backward apply (fold_x) needs the persistent or the halo-tile "
-                "kernel; fpd_conv_fold_supported() reports 0 for this launch");
-    if (rc == 1 && g_fpd_backend != FPD_BACKEND_NAIVE) rc = fpd_conv_mfma_launch(*a, st);
-    if (rc == 1 && g_fpd_backend != FPD_BACKEND_NAIVE) rc = fpd_conv_smallc_launch(*a, st);   // tiny input-channel counts (3, 17)
-    if (rc == 1) rc = fpd_conv_naive_launch(*a, st);
+// ---- convolution backends, in dispatch order: the ONE place that states it.  Launches and queries walk this table. ----
+constexpr unsigned ON_MFMA = 1u << FPD_BACKEND_MFMA, ON_GENERIC = ON_MFMA | 1u << FPD_BACKEND_MFMA_GENERIC, ON_ANY = ON_GENERIC | 1u << FPD_BACKEND_NAIVE;
+struct ConvBackend {
+    const char* name;
+    unsigned backends;          // the g_fpd_backend values it is eligible under (bit set)
+    int (*route)(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r);      // nullptr: decides inside its launch; no fold, no slabs, no pairs
+    int (*launch)(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
+};
+static const ConvBackend g_conv_backends[] = {
+    {"conv_c1", ON_MFMA, fpd_conv_c1_route, fpd_conv_c1_launch},            // big maps, 1x1: streaming kernel
+    {"conv_c3", ON_MFMA, fpd_conv_c3_route, fpd_conv_c3_launch},            // big maps, 3x3 64 -> 64: strip kernel
+    {"conv_pp", ON_MFMA, fpd_conv_pp_route, fpd_conv_pp_launch},            // big maps: persistent kernel
+    {"conv_tile", ON_MFMA, fpd_conv_tile_route, fpd_conv_tile_launch},      // halo-tile kernel
+    {"conv_mfma", ON_GENERIC, nullptr, [](const fpd_conv_t& a, const fpd_conv_t*, hipStream_t st) { return fpd_conv_mfma_launch(a, st); }},
+    {"conv_smallc", ON_GENERIC, nullptr, [](const fpd_conv_t& a, const fpd_conv_t*, hipStream_t st) { return fpd_conv_smallc_launch(a, st); }},   // tiny input-channel counts (3, 17)
+    {"conv_naive", ON_ANY, nullptr, [](const fpd_conv_t& a, const fpd_conv_t*, hipStream_t st) { return fpd_conv_naive_launch(a, st); }},
+};
+static bool eligible(unsigned backends) { return (backends >> g_fpd_backend & 1u) != 0; }
+
+// The backend that serves the launch (b != nullptr: the pair launch) carrying `ask`, and what it offers there.  The walk ends at
+// the first generic backend: whichever of them launches, it offers nothing.  nullptr: a pair that no kernel pairs.
+static const ConvBackend* route_conv(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
+    r = ConvRoute{false, 0, 0};
+    for (const ConvBackend& e : g_conv_backends) {
+        if (!eligible(e.backends)) continue;
+        if (e.route == nullptr ? b == nullptr : e.route(a, b, ask, r) == 0) return &e;
+    }
+    return nullptr;
+}
+
+static int launch_conv(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
+    ConvRoute r;
+    const ConvBackend* e = route_conv(a, b, fpd_conv_ask(a, b), r);
+    if (e == nullptr) {                  // not pairable: same result from two launches
+        const int rc = launch_conv(a, nullptr, st);
+        return rc ? rc : launch_conv(*b, nullptr, st);
+    }
+    // a fusion the fields ask for and the route does not offer: refused here, before any HIP call
+    FPD_REQUIRE(!(a.wg_partial != nullptr && r.slabs_a == 0) && !(b != nullptr && b->wg_partial != nullptr && r.slabs_b == 0),
+                "conv: the launch asks for a fused weight gradient (wg_partial), which its route (%s) does not offer; %s() reports 0 for it",
+                e->name, b ? "fpd_conv_pair_fused_wgrad_partials" : "fpd_conv_fused_wgrad_partials");
+    FPD_REQUIRE(r.folds || (a.fold_x == nullptr && (b == nullptr || b->fold_x == nullptr)),
+                "conv: the launch asks for a folded BN-backward apply (fold_x), which its route (%s) does not offer; %s() reports 0 for it",
+                e->name, b ? "fpd_conv_pair_fold_supported" : "fpd_conv_fold_supported");
+    int rc = e->launch(a, b, st);
+    for (++e; rc == 1 && e != std::end(g_conv_backends); ++e)      // a generic kernel declines inside its launch: on to the next one
+        if (e->route == nullptr && eligible(e->backends)) rc = e->launch(a, b, st);
     return rc;
 }
 
 int fpd_conv_forward(const fpd_conv_t* a, fpd_stream_t stream) {
     int rc = validate_conv(a);
     if (rc) return rc;
-    rc = dispatch_conv(a, (hipStream_t)stream);
+    rc = launch_conv(*a, nullptr, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 
+// The queries answer for the launch as it will be made: `fold` / `wg` asked for, the other taken from the fields.
 int fpd_conv_fold_supported(const fpd_conv_t* a) {
-    if (!a || g_fpd_backend != FPD_BACKEND_MFMA || validate_conv(a) != 0) return 0;
-    return (fpd_conv_c1_fold_ok(*a, nullptr) || fpd_conv_c3_fold_ok(*a, nullptr) || fpd_conv_pp_fold_ok(*a, nullptr) || fpd_conv_tile_fold_ok(*a)) ? 1 : 0;
+    ConvRoute r;
+    if (!a || validate_conv(a) != 0) return 0;
+    route_conv(*a, nullptr, ConvAsk{true, a->wg_partial != nullptr}, r);
+    return r.folds ? 1 : 0;
 }
 int fpd_conv_pair_fold_supported(const fpd_conv_pair_t* p) {
-    if (!p || g_fpd_backend != FPD_BACKEND_MFMA || validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
-    // the dispatch order of fpd_conv_forward_pair(): streaming pair, persistent pair, halo-tile pair, two single launches
-    if (fpd_conv_c1_fold_ok(p->a, &p->b)) return 1;
-    if (fpd_conv_c3_fold_ok(p->a, &p->b)) return 1;
-    if (fpd_conv_pp_fold_ok(p->a, &p->b)) return 1;
-    const int r = fpd_conv_tile_pair_fold_ok(p->a, p->b);
-    if (r >= 0) return r;
-    return (fpd_conv_fold_supported(&p->a) && fpd_conv_fold_supported(&p->b)) ? 1 : 0;
+    ConvRoute r;
+    if (!p || validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
+    if (route_conv(p->a, &p->b, ConvAsk{true, fpd_conv_ask(p->a, &p->b).wg}, r) != nullptr) return r.folds ? 1 : 0;
+    return (fpd_conv_fold_supported(&p->a) && fpd_conv_fold_supported(&p->b)) ? 1 : 0;      // two single launches
 }
 
 int fpd_conv_fused_wgrad_partials(const fpd_conv_t* a) {
-    if (!a || g_fpd_backend != FPD_BACKEND_MFMA || validate_conv(a) != 0) return 0;
-    const int n = fpd_conv_c1_wgrad_partials(*a);      // (-1: the streaming kernel does not take this launch)
-    return n >= 0 ? n : fpd_conv_pp_wgrad_partials(*a);
+    ConvRoute r;
+    if (!a || validate_conv(a) != 0) return 0;
+    route_conv(*a, nullptr, ConvAsk{a->fold_x != nullptr, true}, r);
+    return r.slabs_a;
 }
 int fpd_conv_pair_fused_wgrad_partials(const fpd_conv_pair_t* p, int32_t* n_a, int32_t* n_b) {
     FPD_REQUIRE(p && n_a && n_b, "conv_pair_fused_wgrad_partials: null pointer");
     *n_a = *n_b = 0;
-    if (g_fpd_backend != FPD_BACKEND_MFMA || validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
-    int na = 0, nb = 0;
-    if (fpd_conv_c1_pair_wgrad_partials(p->a, p->b, &na, &nb) < 0) fpd_conv_pp_pair_wgrad_partials(p->a, p->b, &na, &nb);
-    *n_a = na; *n_b = nb;
+    if (validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
+    ConvRoute r;
+    route_conv(p->a, &p->b, ConvAsk{fpd_conv_ask(p->a, &p->b).fold, true}, r);      // (a pair that nothing pairs: two launches without the fusion)
+    *n_a = r.slabs_a; *n_b = r.slabs_b;
     return 0;
 }
 
@@ -230,7 +198,7 @@ int fpd_conv_forward_f8(const fpd_conv_f8_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(((uintptr_t)a->w8 & 15) == 0, "conv_f8: w8 must be 16-byte aligned");
     rc = 1;
     if (g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_tile_f8_launch(a->c, a->w8, a->w8_scale, (hipStream_t)stream);
-    if (rc == 1) rc = dispatch_conv(&a->c, (hipStream_t)stream);      // outside the fp8 domain: the bf16 weights
+    if (rc == 1) rc = launch_conv(a->c, nullptr, (hipStream_t)stream);      // outside the fp8 domain: the bf16 weights
     return rc ? rc : check_launch();
 }
 
@@ -246,18 +214,7 @@ int fpd_conv_forward_pair(const fpd_conv_pair_t* p, fpd_stream_t stream) {
     if (rc) return rc;
     rc = validate_conv(&p->b);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rc = 1;
-    if (g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_c1_pair_launch(p->a, p->b, st);
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_c3_pair_launch(p->a, p->b, st);
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_pp_pair_launch(p->a, p->b, st);
-    FPD_REQUIRE(rc != 1 || (p->a.wg_partial == nullptr && p->b.wg_partial == nullptr),
-                "conv_pair: fused weight gradients need the persistent kernel; fpd_conv_pair_fused_wgrad_partials() reports 0 for this launch");
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_conv_tile_pair_launch(p->a, p->b, st);
-    if (rc == 1) {                       // not pairable: same result from two launches
-        rc = dispatch_conv(&p->a, st);
-        if (rc == 0) rc = dispatch_conv(&p->b, st);
-    }
+    rc = launch_conv(p->a, &p->b, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 
@@ -309,40 +266,60 @@ int fpd_bottleneck_forward(const fpd_bneck_t* a, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+// ---- weight-gradient backends, in dispatch order; partials: slabs the launch writes (0: it declines) ----
+struct WgradBackend {
+    unsigned backends;
+    int (*partials)(const fpd_wgrad_t& a);
+    int (*launch)(const fpd_wgrad_t& a, hipStream_t st);
+};
+static const WgradBackend g_wgrad_backends[] = {
+    {ON_MFMA, fpd_wgrad_tile_partials, fpd_wgrad_tile_launch},      // halo-tile kernel (the only one under option wgrad_tile_only)
+    {ON_GENERIC, fpd_wgrad_mfma_partials, fpd_wgrad_mfma_launch},
+    {ON_GENERIC, fpd_wgrad_smallc_partials, fpd_wgrad_smallc_launch},
+    {ON_ANY, fpd_wgrad_naive_partials, fpd_wgrad_naive_launch},
+};
+
 int fpd_conv_wgrad(const fpd_wgrad_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a && a->x && a->dy && a->dw, "wgrad: null pointer");
     int rc = validate_conv_dims(a->N, a->H, a->W, a->C, a->K, a->R, a->S, a->stride, a->pad, a->P, a->Q);
     if (rc) return rc;
     FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "wgrad: bad dtype %d", a->dtype);
-    hipStream_t st = (hipStream_t)stream;
-    rc = 1;
     FPD_REQUIRE(a->partial == nullptr || a->partial_stride >= (int64_t)a->K * a->R * a->S * a->C + a->K,
                 "wgrad: partial_stride %lld smaller than weight + bias", (long long)a->partial_stride);
-    if (g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_wgrad_tile_launch(*a, st);
-    FPD_REQUIRE(!(g_wgrad_tile_only && rc == 1), "wgrad: option wgrad_tile_only is set and the halo-tile kernel declines N=%d H=%d W=%d C=%d K=%d R=%d", a->N, a->H, a->W, a->C, a->K, a->R);
-    if (rc == 1 && g_fpd_backend != FPD_BACKEND_NAIVE) rc = fpd_wgrad_mfma_launch(*a, st);
-    if (rc == 1 && g_fpd_backend != FPD_BACKEND_NAIVE) rc = fpd_wgrad_smallc_launch(*a, st);
-    if (rc == 1) rc = fpd_wgrad_naive_launch(*a, st);
+    rc = 1;
+    for (const WgradBackend& e : g_wgrad_backends) {
+        FPD_REQUIRE(!(g_wgrad_tile_only && &e != g_wgrad_backends), "wgrad: option wgrad_tile_only is set and the halo-tile kernel declines N=%d H=%d W=%d C=%d K=%d R=%d", a->N, a->H, a->W, a->C, a->K, a->R);
+        if (eligible(e.backends)) rc = e.launch(*a, (hipStream_t)stream);
+        if (rc != 1) break;
+    }
     return rc ? rc : check_launch();
 }
 
-/* slabs the kernel fpd_conv_wgrad() dispatches these dimensions to will write (same dispatch order as above) */
+/* slabs the kernel fpd_conv_wgrad() dispatches these dimensions to will write */
 int fpd_wgrad_num_partials(const fpd_wgrad_t* a) {
-    if (!a) return 0;
     int n = 0;
-    if (g_fpd_backend == FPD_BACKEND_MFMA) n = fpd_wgrad_tile_partials(*a);
-    if (n == 0 && g_fpd_backend != FPD_BACKEND_NAIVE) n = fpd_wgrad_mfma_partials(*a);
-    if (n == 0 && g_fpd_backend != FPD_BACKEND_NAIVE) n = fpd_wgrad_smallc_partials(*a);
-    if (n == 0) n = fpd_wgrad_naive_partials(*a);
+    for (const WgradBackend& e : g_wgrad_backends)
+        if (a && n == 0 && eligible(e.backends)) n = e.partials(*a);
     return n;
 }
 
+// ---- stem backends, in dispatch order (forward and weight gradient) ----
+struct StemBackend {
+    unsigned backends;
+    int (*forward)(const fpd_stem_t& a, hipStream_t st);
+    int (*wgrad_partials)(const fpd_stem_t& a);
+    int (*wgrad)(const fpd_stem_t& a, hipStream_t st);
+};
+static const StemBackend g_stem_backends[] = {
+    {ON_MFMA, fpd_stem_forward_s2d_launch, fpd_stem_wgrad_s2d_partials, fpd_stem_wgrad_s2d_launch},      // space-to-depth 4x4 form (round 5)
+    {ON_MFMA, fpd_stem_forward_mfma_launch, fpd_stem_wgrad_mfma_partials, fpd_stem_wgrad_mfma_launch},
+    {ON_ANY, fpd_stem_forward_launch, fpd_stem_wgrad_partials, fpd_stem_wgrad_launch},
+};
+
 int fpd_stem_wgrad_num_partials(const fpd_stem_t* a) {
-    if (!a) return 0;
     int n = 0;
-    if (g_fpd_backend == FPD_BACKEND_MFMA) n = fpd_stem_wgrad_s2d_partials(*a);
-    if (n == 0 && g_fpd_backend == FPD_BACKEND_MFMA) n = fpd_stem_wgrad_mfma_partials(*a);
-    if (n == 0) n = fpd_stem_wgrad_partials(*a);
+    for (const StemBackend& e : g_stem_backends)
+        if (a && n == 0 && eligible(e.backends)) n = e.wgrad_partials(*a);
     return n;
 }
 
@@ -355,9 +332,8 @@ int fpd_stem_forward(const fpd_stem_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a && a->x && a->w && a->bias && a->y, "stem: null pointer");
     FPD_REQUIRE(a->P == (a->H + 6 - 7) / 2 + 1 && a->Q == (a->W + 6 - 7) / 2 + 1, "stem: bad output size");
     int rc = 1;
-    if (g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_stem_forward_s2d_launch(*a, (hipStream_t)stream);      // space-to-depth 4x4 form (round 5)
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_stem_forward_mfma_launch(*a, (hipStream_t)stream);
-    if (rc == 1) rc = fpd_stem_forward_launch(*a, (hipStream_t)stream);
+    for (const StemBackend& e : g_stem_backends)
+        if (rc == 1 && eligible(e.backends)) rc = e.forward(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 
@@ -366,9 +342,8 @@ int fpd_stem_wgrad(const fpd_stem_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a->partial == nullptr || a->partial_stride >= (int64_t)a->K * 148, "stem wgrad: partial_stride %lld smaller than weight + bias",
                 (long long)a->partial_stride);
     int rc = 1;
-    if (g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_stem_wgrad_s2d_launch(*a, (hipStream_t)stream);
-    if (rc == 1 && g_fpd_backend == FPD_BACKEND_MFMA) rc = fpd_stem_wgrad_mfma_launch(*a, (hipStream_t)stream);
-    if (rc == 1) rc = fpd_stem_wgrad_launch(*a, (hipStream_t)stream);
+    for (const StemBackend& e : g_stem_backends)
+        if (rc == 1 && eligible(e.backends)) rc = e.wgrad(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 

@@ -28,7 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 #include "mfma_frag.h"
 
 namespace {
@@ -637,10 +637,8 @@ int c1_fuse_wgrad() { return 1; }
 bool c1_chan(int c) { return c == 32 || c == 64 || c == 128; }
 bool c1_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// folded: decide for the launch as it will be made WITH a folded BN-backward apply, whatever a.fold_x holds now (the fold query
-// is asked before the caller fills in the fold fields: include/fpd_amd.h, fpd_conv_fold_supported())
-bool c1_domain(const fpd_conv_t& a, bool folded = false) {
-    const bool fold = folded || a.fold_x != nullptr;
+// fold: decide for the launch as it will be made WITH a folded BN-backward apply, whatever a.fold_x holds now (ConvAsk)
+bool c1_domain(const fpd_conv_t& a, bool fold) {
     if (a.dtype != FPD_BF16 || a.R != 1 || a.S != 1 || a.stride != 1 || a.pad != 0 || a.P != a.H || a.Q != a.W) return false;
     // (16 -> 128: the inter-stack score_ convolution and the data gradient of the score convolution, hourglass.py:136-137, one k-step)
     if (!(c1_chan(a.C) || (a.C == 16 && a.K == 128)) || !c1_chan(a.K)) return false;
@@ -656,32 +654,28 @@ bool c1_domain(const fpd_conv_t& a, bool folded = false) {
         // gradient, its weight gradient a launch of its own on the lane
         else if ((a.C / 32) * (a.K / 32) != C1_NW && !(a.C == 128 && a.K == 128 && !fold)) return false;
     } else {
-        if (a.epi != FPD_EPI_PLAIN || a.fold_x != nullptr || a.wg_partial != nullptr) return false;
-        if (a.y == a.x) return false;
+        if (a.epi != FPD_EPI_PLAIN || a.y == a.x) return false;      // (a forward launch offers neither fusion: ConvRoute)
     }
     return true;
 }
-bool c1_wg_shape(const fpd_conv_t& a) {
-    return c1_fuse_wgrad() != 0 && c1_domain(a) && a.epi == FPD_EPI_BNRELU_BWD && (a.C / 32) * (a.K / 32) == C1_NW;
-}
 int c1_rounds(const fpd_conv_t& a) { return cdiv(a.N * a.H * a.W / 32, C1_NW); }
 
-bool c1_takes(const fpd_conv_t& a, const fpd_conv_t* b, bool folded = false) {
+struct C1Plan { int na, nb, grid; bool wg; };
+// The ONE decision of this unit, for the launch and for the queries: does the kernel take the launch (pair) carrying `ask`, with
+// which grid, and which of the two fusions does it offer.  16 -> 128 and 128 x 128 data gradients are taken only unfolded (no FOLD
+// variant: their folded launch goes on to the next kernel); the fused weight gradient needs a dW tile for every wave.
+bool c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, C1Plan& pl) {
     const int mode = c1_mode();
-    if (mode == 0 || !c1_domain(a, folded)) return false;
+    if (mode == 0 || !c1_domain(a, ask.fold)) return false;
+    const bool bwd = a.epi == FPD_EPI_BNRELU_BWD;
     long long px = (long long)a.N * a.H * a.W;
     if (b != nullptr) {
-        if (!c1_domain(*b, folded) || a.K != b->K || a.C != b->C || a.epi != b->epi) return false;
+        if (!c1_domain(*b, ask.fold) || a.K != b->K || a.C != b->C || a.epi != b->epi) return false;
         if ((a.residual != nullptr) != (b->residual != nullptr)) return false;      // (the residual is a template parameter)
         px += (long long)b->N * b->H * b->W;
     }
-    return mode != 1 || px >= (a.epi == FPD_EPI_BNRELU_BWD ? c1_min_px_bwd() : c1_min_px());
-}
-
-struct C1Plan { int na, nb, grid; bool wg; };
-bool c1_plan(const fpd_conv_t& a, const fpd_conv_t* b, bool want_wg, C1Plan& pl) {
+    if (mode == 1 && px < (bwd ? c1_min_px_bwd() : c1_min_px())) return false;
     const int ra = c1_rounds(a), rb = b ? c1_rounds(*b) : 0;
-    pl.wg = want_wg && c1_wg_shape(a) && (b == nullptr || c1_wg_shape(*b));
     // blocks under the cap, balanced: every block runs the same number of rounds (512 rounds under a cap of 192 -> 171 blocks of 3,
     // not 192 blocks of which two thirds run 3 and the rest 2)
     int total = std::max(1, std::min(c1_blocks(), ra + rb));
@@ -693,6 +687,10 @@ bool c1_plan(const fpd_conv_t& a, const fpd_conv_t* b, bool want_wg, C1Plan& pl)
     }
     pl.na = total - pl.nb;
     pl.grid = total;
+    pl.wg = ask.wg && c1_fuse_wgrad() != 0 && bwd && (a.C / 32) * (a.K / 32) == C1_NW;      // (a pair: same C, K, epilogue)
+    r.folds = ask.fold && bwd;
+    r.slabs_a = pl.wg ? pl.na : 0;
+    r.slabs_b = pl.wg ? pl.nb : 0;
     return true;
 }
 
@@ -739,33 +737,6 @@ int c1_launch_c(const fpd_conv_t& a, const fpd_conv_t* b, const C1Plan& pl, hipS
     }
 }
 
-int c1_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
-    const bool want_wg = a.wg_partial != nullptr || (b != nullptr && b->wg_partial != nullptr);
-    C1Plan pl;
-    if (!c1_plan(a, b, want_wg, pl)) return 1;
-    if (want_wg) {
-        if (!pl.wg) return fpd_fail(-2, "conv: a fused weight gradient was requested for a launch fpd_conv_fused_wgrad_partials() reports 0 for");
-        const fpd_conv_t* cs[2] = {&a, b};
-        const int nblk[2] = {pl.na, pl.nb};
-        for (int i = 0; i < 2; ++i) {
-            if (cs[i] == nullptr || cs[i]->wg_partial == nullptr) continue;
-            if (cs[i]->wg_stride < (int64_t)cs[i]->C * cs[i]->K + cs[i]->C)
-                return fpd_fail(-2, "conv: wg_stride %lld smaller than weight + bias", (long long)cs[i]->wg_stride);
-            if (cs[i]->wg_count != nblk[i])
-                return fpd_fail(-2, "conv: the launch writes %d weight-gradient slabs but the caller sized its workspace for %d "
-                                    "(fpd_conv_fused_wgrad_partials: has a conv_c1 option changed since?)", nblk[i], cs[i]->wg_count);
-        }
-        if ((a.wg_partial == nullptr) != (b != nullptr && b->wg_partial == nullptr) && b != nullptr)
-            return fpd_fail(-2, "conv_pair: both or neither convolution of a pair take a fused weight gradient");
-    }
-    switch (a.C) {
-        case 16: return c1_launch_ck<16, 128>(a, b, pl, st);
-        case 32: return c1_launch_c<32>(a, b, pl, st);
-        case 64: return c1_launch_c<64>(a, b, pl, st);
-        default: return c1_launch_c<128>(a, b, pl, st);
-    }
-}
-
 }  // namespace
 
 int fpd_conv_c1_option(int which, int value) {      // which: 0 = mode, 1 = blocks (returns the previous value), 2 = launches served so far
@@ -776,33 +747,23 @@ int fpd_conv_c1_option(int which, int value) {      // which: 0 = mode, 1 = bloc
     return prev;
 }
 
-// 0 = launched, 1 = outside this kernel's domain (the caller tries conv_pp next), < 0 error
-int fpd_conv_c1_launch(const fpd_conv_t& a, hipStream_t st) {
-    if (!c1_takes(a, nullptr)) return 1;
-    return c1_launch(a, nullptr, st);
-}
-int fpd_conv_c1_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
-    if (!c1_takes(a, &b)) return 1;
-    return c1_launch(a, &b, st);
-}
-// 1 if the launch (pair) WITH a folded BN-backward apply is served by this kernel as a BNRELU_BWD data gradient (the fold is a
-// run-time flag of the FOLD variants; 16 -> 128 and 128 x 128 have none and are taken only unfolded)
-int fpd_conv_c1_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b) {
-    if (a.epi != FPD_EPI_BNRELU_BWD || (b != nullptr && b->epi != FPD_EPI_BNRELU_BWD)) return 0;
+int fpd_conv_c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
     C1Plan pl;
-    return (c1_takes(a, b, true) && c1_plan(a, b, false, pl)) ? 1 : 0;
+    return c1_route(a, b, ask, r, pl) ? 0 : 1;
 }
-// -1 = this kernel does not take the launch (ask the next kernel); else the slabs of the fused weight gradient (0: served
-// here, but without the fusion)
-int fpd_conv_c1_wgrad_partials(const fpd_conv_t& a) {
+int fpd_conv_c1_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
+    ConvRoute r;
     C1Plan pl;
-    if (!c1_takes(a, nullptr) || !c1_plan(a, nullptr, true, pl)) return -1;
-    return pl.wg ? pl.na : 0;
-}
-int fpd_conv_c1_pair_wgrad_partials(const fpd_conv_t& a, const fpd_conv_t& b, int* na, int* nb) {
-    C1Plan pl;
-    *na = *nb = 0;
-    if (!c1_takes(a, &b) || !c1_plan(a, &b, true, pl)) return -1;
-    if (pl.wg) { *na = pl.na; *nb = pl.nb; }
-    return 0;
+    if (!c1_route(a, b, fpd_conv_ask(a, b), r, pl)) return 1;
+    if (int rc = fpd_conv_check_slabs(a, r.slabs_a, "conv_c1")) return rc;
+    if (b != nullptr) {
+        if (int rc = fpd_conv_check_slabs(*b, r.slabs_b, "conv_c1")) return rc;
+        FPD_REQUIRE((a.wg_partial == nullptr) == (b->wg_partial == nullptr), "conv_pair: both or neither convolution of a pair take a fused weight gradient");
+    }
+    switch (a.C) {
+        case 16: return c1_launch_ck<16, 128>(a, b, pl, st);
+        case 32: return c1_launch_c<32>(a, b, pl, st);
+        case 64: return c1_launch_c<64>(a, b, pl, st);
+        default: return c1_launch_c<128>(a, b, pl, st);
+    }
 }

@@ -27,7 +27,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -471,11 +471,11 @@ bool c3_domain(const fpd_conv_t& a) {
     if ((long long)a.N * a.H * a.W > (1ll << 28)) return false;
     if (!c3_aligned(a.x) || !c3_aligned(a.y) || !c3_aligned(a.w) || !c3_aligned(a.epi_x) || !c3_aligned(a.fold_x) || !c3_aligned(a.fold_out))
         return false;
-    if (a.residual != nullptr || a.wg_partial != nullptr || a.y == a.x) return false;
+    if (a.residual != nullptr || a.y == a.x) return false;
     if (a.epi == FPD_EPI_BNRELU_BWD) {
         if (a.bias != nullptr || a.bn.mode != FPD_BN_NONE) return false;
     } else {
-        if (a.epi != FPD_EPI_PLAIN || a.fold_x != nullptr) return false;
+        if (a.epi != FPD_EPI_PLAIN) return false;      // (a forward launch does not fold: ConvRoute)
     }
     return true;
 }
@@ -530,14 +530,12 @@ int c3_launch_t(const fpd_conv_t& a, const fpd_conv_t* b, const C3Plan& pl, hipS
     g_c3_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
-int c3_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
-    C3Plan pl;
-    if (!c3_plan(a, b, pl)) return 1;
-    if (a.epi == FPD_EPI_BNRELU_BWD) {
-        if (a.fold_x != nullptr || (b != nullptr && b->fold_x != nullptr)) return c3_launch_t<true, true>(a, b, pl, st);
-        return c3_launch_t<true, false>(a, b, pl, st);
-    }
-    return c3_launch_t<false, false>(a, b, pl, st);
+// The ONE decision of this unit, for the launch and for the queries.  A data gradient evaluates a folded BN-backward apply on its
+// operand; the weight gradient of a 3x3 convolution stays a separate launch that reads fold_out (0 slabs).
+bool c3_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, C3Plan& pl) {
+    if (!c3_takes(a, b) || !c3_plan(a, b, pl)) return false;
+    r = ConvRoute{ask.fold && a.epi == FPD_EPI_BNRELU_BWD, 0, 0};
+    return true;
 }
 
 }  // namespace
@@ -549,24 +547,14 @@ int fpd_conv_c3_option(int which, int value) {      // which: 0 = mode, 1 = bloc
     g = value;
     return prev;
 }
-// 0 = launched, 1 = outside this kernel's domain (the caller tries conv_pp next), < 0 error
-int fpd_conv_c3_launch(const fpd_conv_t& a, hipStream_t st) {
-    if (!c3_takes(a, nullptr)) return 1;
-    return c3_launch(a, nullptr, st);
-}
-int fpd_conv_c3_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
-    if (!c3_takes(a, &b)) return 1;
-    return c3_launch(a, &b, st);
-}
-// 1 if the launch (pair) is served by this kernel as a BNRELU_BWD data gradient (a folded BN-backward apply is then evaluated on
-// its operand; the weight gradient of a 3x3 convolution stays a separate launch that reads fold_out)
-int fpd_conv_c3_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b) {
-    if (a.epi != FPD_EPI_BNRELU_BWD || (b != nullptr && b->epi != FPD_EPI_BNRELU_BWD)) return 0;
+int fpd_conv_c3_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
     C3Plan pl;
-    return (c3_takes(a, b) && c3_plan(a, b, pl)) ? 1 : 0;
+    return c3_route(a, b, ask, r, pl) ? 0 : 1;
 }
-// 1 if this kernel takes the launch (so that no other kernel's fused weight gradient may be planned for it)
-int fpd_conv_c3_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
+int fpd_conv_c3_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
+    ConvRoute r;
     C3Plan pl;
-    return (c3_takes(a, b) && c3_plan(a, b, pl)) ? 1 : 0;
+    if (!c3_route(a, b, fpd_conv_ask(a, b), r, pl)) return 1;
+    if (a.epi != FPD_EPI_BNRELU_BWD) return c3_launch_t<false, false>(a, b, pl, st);
+    return r.folds ? c3_launch_t<true, true>(a, b, pl, st) : c3_launch_t<true, false>(a, b, pl, st);
 }

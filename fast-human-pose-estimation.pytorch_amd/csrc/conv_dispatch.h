@@ -1,0 +1,89 @@
+// Internal entry points of the kernel units, as api.hip dispatches to them (host code only).
+//
+// Launch convention: 0 = launched, 1 = outside this kernel's domain (the caller tries the next one), < 0 error.
+#pragma once
+#include "common.h"
+
+// ---- convolutions: conv_c1 / conv_c3 / conv_pp / conv_tile decide in ONE route function each, which their launch and the
+//      queries of api.hip (fold, slab count) both go through ----
+// What the launch (b != nullptr: the pair launch) WILL carry, whatever the descriptor fields hold now: the queries are asked
+// before the caller fills in the fold and slab fields.
+struct ConvAsk { bool fold, wg; };         // some convolution of the launch folds a BN-backward apply / forms a weight gradient
+struct ConvRoute { bool folds; int slabs_a, slabs_b; };      // the fold is evaluated; weight-gradient slabs written for a / b (0: none)
+inline ConvAsk fpd_conv_ask(const fpd_conv_t& a, const fpd_conv_t* b) {
+    return ConvAsk{a.fold_x != nullptr || (b != nullptr && b->fold_x != nullptr), a.wg_partial != nullptr || (b != nullptr && b->wg_partial != nullptr)};
+}
+// the slab fields of a launch against the slab count of its route (the count was asked for when the workspace was sized; a
+// geometry that has changed since would write past the workspace or leave slabs unwritten)
+inline int fpd_conv_check_slabs(const fpd_conv_t& c, int slabs, const char* unit) {
+    if (c.wg_partial == nullptr) return 0;
+    FPD_REQUIRE(c.wg_stride >= (int64_t)c.C * c.K + c.C, "conv: wg_stride %lld smaller than weight + bias", (long long)c.wg_stride);
+    FPD_REQUIRE(c.wg_count == slabs, "conv: the launch writes %d weight-gradient slabs but the caller sized its workspace for %d "
+                "(fpd_conv_fused_wgrad_partials: has a %s option changed since?)", slabs, c.wg_count, unit);
+    return 0;
+}
+// route: 0 = this kernel takes the launch carrying `ask` (r: what it offers), 1 = it declines.  launch: routes with the ask read
+// from the fields, then launches.
+int fpd_conv_c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r);
+int fpd_conv_c1_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
+int fpd_conv_c3_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r);
+int fpd_conv_c3_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
+int fpd_conv_pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r);
+int fpd_conv_pp_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
+int fpd_conv_tile_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r);
+int fpd_conv_tile_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
+int fpd_conv_c1_option(int which, int value);
+int fpd_conv_c3_option(int which, int value);
+int fpd_conv_pp_option(int which, int value);
+// the generic kernels and the fp8 tile kernel decide inside their launch: no fold, no fused weight gradient, no pairs
+int fpd_conv_mfma_launch(const fpd_conv_t& a, hipStream_t st);
+int fpd_conv_smallc_launch(const fpd_conv_t& a, hipStream_t st);
+int fpd_conv_naive_launch(const fpd_conv_t& a, hipStream_t st);
+bool fpd_conv_f8_domain(const fpd_conv_t& a);
+int fpd_conv_tile_f8_launch(const fpd_conv_t& a, const void* w8, const float* wscale, hipStream_t st);
+int fpd_weight_quant_f8_launch(const fpd_wquant_entry_t* table, int n, hipStream_t st);
+
+// ---- weight gradients: *_partials = slabs the launch of the same unit writes (0: it declines) ----
+int fpd_wgrad_tile_partials(const fpd_wgrad_t& a);
+int fpd_wgrad_tile_launch(const fpd_wgrad_t& a, hipStream_t st);
+int fpd_wgrad_mfma_partials(const fpd_wgrad_t& a);
+int fpd_wgrad_mfma_launch(const fpd_wgrad_t& a, hipStream_t st);
+int fpd_wgrad_smallc_partials(const fpd_wgrad_t& a);
+int fpd_wgrad_smallc_launch(const fpd_wgrad_t& a, hipStream_t st);
+int fpd_wgrad_naive_partials(const fpd_wgrad_t& a);
+int fpd_wgrad_naive_launch(const fpd_wgrad_t& a, hipStream_t st);
+int fpd_wreduce_launch(const fpd_wreduce_entry_t* table, int n, int64_t max_elems, hipStream_t st);
+
+// ---- stem ----
+int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st);
+int fpd_stem_wgrad_s2d_partials(const fpd_stem_t& a);
+int fpd_stem_wgrad_s2d_launch(const fpd_stem_t& a, hipStream_t st);
+int fpd_stem_forward_mfma_launch(const fpd_stem_t& a, hipStream_t st);
+int fpd_stem_wgrad_mfma_partials(const fpd_stem_t& a);
+int fpd_stem_wgrad_mfma_launch(const fpd_stem_t& a, hipStream_t st);
+int fpd_stem_forward_launch(const fpd_stem_t& a, hipStream_t st);
+int fpd_stem_wgrad_partials(const fpd_stem_t& a);
+int fpd_stem_wgrad_launch(const fpd_stem_t& a, hipStream_t st);
+
+// ---- everything else: one kernel each ----
+int fpd_bneck_fused_launch(const fpd_bneck_t& a, hipStream_t st);
+int fpd_bneck_fused_pair_launch(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st);
+int fpd_bneck_fold_launch(const fpd_bneck_t& a, float* out, hipStream_t st);
+int fpd_head_fused_launch(const fpd_head_t& a, hipStream_t st);
+int fpd_head_fold_launch(const fpd_head_t& a, float* out, hipStream_t st);
+int fpd_pck_launch(const fpd_pck_t& a, hipStream_t st);
+int fpd_flip_w_launch(const float* x, float* y, int64_t rows, int W, hipStream_t st);
+int fpd_flip_merge_launch(const fpd_flipmerge_t& p, hipStream_t st);
+int fpd_final_preds_launch(const fpd_finalpreds_t& p, hipStream_t st);
+int fpd_render_targets_launch(const fpd_targets_t& a, hipStream_t st);
+int fpd_warp_affine_launch(const fpd_warp_t& a, hipStream_t st);
+int fpd_elementwise_launch(const fpd_ew_t& a, hipStream_t st);
+int fpd_elementwise_pair_launch(const fpd_ew_t& a, const fpd_ew_t& b, hipStream_t st);
+int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st);
+int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
+int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st);
+int fpd_weight_prep_launch(const fpd_wprep_entry_t* table, int n, int64_t max_elems, int dtype, hipStream_t st);
+int fpd_bn_update_running_launch(const fpd_bnupd_entry_t* table, int n, hipStream_t st);
+int fpd_cast_launch(const void* src, void* dst, int64_t n, int sd, int dd, hipStream_t st);
+int fpd_nchw_to_nhwc_launch(const float* src, void* dst, int N, int C, int H, int W, int dtype, hipStream_t st);
+int fpd_nhwc_to_nchw_launch(const void* src, float* dst, int N, int C, int H, int W, int dtype, hipStream_t st);

@@ -29,7 +29,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "mfma_frag.h"
 
@@ -757,8 +757,8 @@ static int pp_tiles(const fpd_conv_t& a) { return cdiv(a.N * a.H, pp_nrows(a)); 
 // shapes whose data-gradient launch can carry the forward convolution's weight gradient (conv_pp_body<.., WG = true>)
 static int pp_wg_kmax() { return 128; }       // widest data gradient (output channels) that also forms the weight gradient
 static int pp_wg_ckmax() { return 128 * 128; }      // largest weight matrix (C x K elements) formed inside a data-gradient launch
-static bool pp_wg_shape(const fpd_conv_t& a) {
-    return pp_fuse_wgrad() != 0 && pp_domain(a) && a.epi == FPD_EPI_BNRELU_BWD && a.R == 1 && a.C >= 32 && a.K <= pp_wg_kmax() && a.C * a.K <= pp_wg_ckmax() &&
+static bool pp_wg_shape(const fpd_conv_t& a) {      // (a: in the domain)
+    return pp_fuse_wgrad() != 0 && a.epi == FPD_EPI_BNRELU_BWD && a.R == 1 && a.C >= 32 && a.K <= pp_wg_kmax() && a.C * a.K <= pp_wg_ckmax() &&
            (pp_nrows(a) * a.W) % 16 == 0;
 }
 
@@ -776,9 +776,9 @@ static PPGeo pp_geo(const fpd_conv_t& a) {
     return g;
 }
 
-// launch geometry of one convolution (b == nullptr) or a pair: ONE place decides it, for the launch and for the slab-count query
+// launch geometry of one convolution (b == nullptr) or a pair carrying `ask` (the fused weight gradient changes the LDS layout)
 struct PPPlan { PPGeo ga, gb; int ks, grid; size_t lds; bool wg; };
-static bool pp_plan(const fpd_conv_t& a, const fpd_conv_t* b, bool want_wg, PPPlan& pl) {
+static bool pp_plan(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, PPPlan& pl) {
     const int KH = a.K > 32 ? 2 : 1;
     const bool bwd = a.epi == FPD_EPI_BNRELU_BWD;
     pl.ga = pp_geo(a);
@@ -789,7 +789,7 @@ static bool pp_plan(const fpd_conv_t& a, const fpd_conv_t* b, bool want_wg, PPPl
         pl.gb = pp_geo(*b);
         total += pl.gb.ntiles;
     }
-    pl.wg = want_wg && pp_wg_shape(a) && (b == nullptr || pp_wg_shape(*b));
+    pl.wg = ask.wg && pp_wg_shape(a) && (b == nullptr || pp_wg_shape(*b));
     int region = std::max(pl.ga.region, b ? pl.gb.region : 0);
     if (pl.wg) {                                           // the image is not aliased: only the image counts
         const int LDA = a.C * 2 + 16;
@@ -838,38 +838,6 @@ static int pp_launch_c(const fpd_conv_t& a, const fpd_conv_t* b, const PPPlan& p
     return bwd ? pp_launch_t<R, C, 1, true, false>(a, b, pl, st) : pp_launch_t<R, C, 1, false, false>(a, b, pl, st);
 }
 
-static int pp_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
-    const bool want_wg = a.wg_partial != nullptr || (b != nullptr && b->wg_partial != nullptr);
-    PPPlan pl;
-    if (!pp_plan(a, b, want_wg, pl)) return 1;
-    if (want_wg) {
-        if (!pl.wg) return fpd_fail(-2, "conv: a fused weight gradient was requested for a launch fpd_conv_fused_wgrad_partials() reports 0 for");
-        const fpd_conv_t* cs[2] = {&a, b};
-        const int nblk[2] = {pl.ga.nblk, pl.gb.nblk};
-        for (int i = 0; i < 2; ++i) {
-            if (cs[i] == nullptr || cs[i]->wg_partial == nullptr) continue;
-            if (cs[i]->wg_stride < (int64_t)cs[i]->C * cs[i]->K + cs[i]->C)
-                return fpd_fail(-2, "conv: wg_stride %lld smaller than weight + bias", (long long)cs[i]->wg_stride);
-            // the slab count was asked for when the workspace was sized; a geometry that has changed since (conv_pp_blocks) would
-            // write past the workspace or leave slabs unwritten
-            if (cs[i]->wg_count != nblk[i])
-                return fpd_fail(-2, "conv: the launch writes %d weight-gradient slabs but the caller sized its workspace for %d "
-                                    "(fpd_conv_fused_wgrad_partials: has a conv_pp option changed since?)", nblk[i], cs[i]->wg_count);
-        }
-    }
-    if (a.R == 3) {
-        if (a.C == 64) return pp_launch_c<3, 64>(a, b, pl, st);
-        if (a.C == 32) return pp_launch_c<3, 32>(a, b, pl, st);
-        return pp_launch_c<3, 16>(a, b, pl, st);
-    }
-    switch (a.C) {
-        case 16: return pp_launch_c<1, 16>(a, b, pl, st);
-        case 32: return pp_launch_c<1, 32>(a, b, pl, st);
-        case 64: return pp_launch_c<1, 64>(a, b, pl, st);
-        default: return pp_launch_c<1, 128>(a, b, pl, st);
-    }
-}
-
 static bool pp_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
     const int mode = pp_mode();
     if (mode == 0 || !pp_domain(a)) return false;
@@ -881,6 +849,20 @@ static bool pp_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
     return mode != 1 || tiles >= pp_min_tiles();
 }
 
+// The ONE decision of this unit, for the launch and for the queries.  A BNRELU_BWD data gradient without a prologue BN evaluates
+// a folded BN-backward apply on the way into the operand image; the fold is decided before the fused weight gradient is, so it is
+// offered only where the launch exists both with and without that fusion (the slab count does not depend on the fold).
+static bool pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, PPPlan& pl) {
+    if (!pp_takes(a, b) || !pp_plan(a, b, ask, pl)) return false;
+    auto foldable = [](const fpd_conv_t& c) { return c.epi == FPD_EPI_BNRELU_BWD && c.bn.mode == FPD_BN_NONE; };
+    PPPlan other;
+    r.folds = ask.fold && foldable(a) && (b == nullptr || foldable(*b)) &&
+              (!(pp_wg_shape(a) && (b == nullptr || pp_wg_shape(*b))) || pp_plan(a, b, ConvAsk{ask.fold, !ask.wg}, other));
+    r.slabs_a = pl.wg ? pl.ga.nblk : 0;
+    r.slabs_b = pl.wg ? pl.gb.nblk : 0;
+    return true;
+}
+
 }  // namespace
 
 int fpd_conv_pp_option(int which, int value) {     // which: 0 = mode, 1 = blocks; returns the previous value
@@ -890,44 +872,25 @@ int fpd_conv_pp_option(int which, int value) {     // which: 0 = mode, 1 = block
     return prev;
 }
 
-// 0 = launched, 1 = outside this kernel's domain (the caller tries conv_tile next), < 0 error
-int fpd_conv_pp_launch(const fpd_conv_t& a, hipStream_t st) {
-    if (!pp_takes(a, nullptr)) return 1;
-    return pp_launch(a, nullptr, st);
-}
-
-// two independent convolutions of equal channel shapes in one launch; 1 = not pairable here
-int fpd_conv_pp_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
-    if (!pp_takes(a, &b)) return 1;
-    return pp_launch(a, &b, st);
-}
-
-// slabs of the fused weight gradient (fpd_conv_t.wg_partial) for a single launch / the two halves of a pair launch; 0 = the
-// launch would not run here, or not with the fusion
-// 1 if the launch (pair) is served by this kernel as a BNRELU_BWD data gradient without a prologue BN: the configuration in which
-// a folded BN-backward apply (fpd_conv_t.fold_x) is evaluated on the way into the operand image
-int fpd_conv_pp_fold_ok(const fpd_conv_t& a, const fpd_conv_t* b) {
-    if (a.epi != FPD_EPI_BNRELU_BWD || a.bn.mode != FPD_BN_NONE) return 0;
-    if (b != nullptr && (b->epi != FPD_EPI_BNRELU_BWD || b->bn.mode != FPD_BN_NONE)) return 0;
-    if (!pp_takes(a, b)) return 0;
-    // exactly what pp_launch() will decide: the launch may still be declined by its geometry (LDS, a pair with < 2 ranges),
-    // with and without the fused weight gradient
+int fpd_conv_pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
     PPPlan pl;
-    if (!pp_plan(a, b, false, pl)) return 0;
-    if (pp_wg_shape(a) && (b == nullptr || pp_wg_shape(*b)) && !pp_plan(a, b, true, pl)) return 0;
-    return 1;
+    return pp_route(a, b, ask, r, pl) ? 0 : 1;
 }
-
-int fpd_conv_pp_wgrad_partials(const fpd_conv_t& a) {
+int fpd_conv_pp_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
+    ConvRoute r;
     PPPlan pl;
-    if (!pp_takes(a, nullptr) || !pp_plan(a, nullptr, true, pl) || !pl.wg) return 0;
-    return pl.ga.nblk;
-}
-int fpd_conv_pp_pair_wgrad_partials(const fpd_conv_t& a, const fpd_conv_t& b, int* na, int* nb) {
-    PPPlan pl;
-    *na = *nb = 0;
-    if (!pp_takes(a, &b) || !pp_plan(a, &b, true, pl) || !pl.wg) return 0;
-    *na = pl.ga.nblk;
-    *nb = pl.gb.nblk;
-    return 0;
+    if (!pp_route(a, b, fpd_conv_ask(a, b), r, pl)) return 1;
+    if (int rc = fpd_conv_check_slabs(a, r.slabs_a, "conv_pp")) return rc;
+    if (b != nullptr) if (int rc = fpd_conv_check_slabs(*b, r.slabs_b, "conv_pp")) return rc;
+    if (a.R == 3) {
+        if (a.C == 64) return pp_launch_c<3, 64>(a, b, pl, st);
+        if (a.C == 32) return pp_launch_c<3, 32>(a, b, pl, st);
+        return pp_launch_c<3, 16>(a, b, pl, st);
+    }
+    switch (a.C) {
+        case 16: return pp_launch_c<1, 16>(a, b, pl, st);
+        case 32: return pp_launch_c<1, 32>(a, b, pl, st);
+        case 64: return pp_launch_c<1, 64>(a, b, pl, st);
+        default: return pp_launch_c<1, 128>(a, b, pl, st);
+    }
 }

@@ -14,7 +14,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 
 namespace {
@@ -415,10 +415,6 @@ __global__ __launch_bounds__(256, (tile_waves<TN, ALLW, FOLD>())) void conv_tile
 
 // largest grid (blocks) that uses the all-taps-staged variant (the FPD_CONV_ALLW knob of rounds 4-5: 320 measured best)
 static int allw_max_blocks() { return 320; }
-template <typename T, int BK>
-static bool allw_ok(const fpd_conv_t& a, int blocks) {
-    return a.R == 3 && a.C == BK && blocks <= allw_max_blocks();
-}
 
 constexpr size_t LDS_MAX = 160 * 1024;
 static int tile_rows(int W) { return std::max(1, 128 / W); }
@@ -432,57 +428,12 @@ static TileGeo make_geo(const fpd_conv_t& a) {
     g.mWV = magic_of(a.W * VPR);
     return g;
 }
-template <typename T, int TN, int BK, bool ALLW>
-static size_t tile_lds(const fpd_conv_t& c) {
-    constexpr int LD = BK + 16 / (int)sizeof(T);
-    const int hrows = tile_rows(c.W) + c.R - 1, WP = c.W + c.R - 1;
-    return (size_t)(hrows * WP + 3) * LD * sizeof(T) + (size_t)(ALLW ? 9 : 2) * 32 * TN * LD * sizeof(T);
-}
-
-template <typename T, int TN, int BK, bool ALLW>
-int launch_tile_v(const fpd_conv_t& a, hipStream_t st) {
-    const size_t epi = std::max((size_t)128 * (32 * TN + 4) * sizeof(float), (size_t)4 * 32 * TN * 2 * sizeof(double));
-    const size_t lds = (size_t)(2 * a.C + 4 * 32 * TN + (a.epi == FPD_EPI_BNRELU_BWD ? 3 * a.C : 0)) * sizeof(float) + std::max(tile_lds<T, TN, BK, ALLW>(a), epi);
-    if (lds > LDS_MAX) return 1;
-    dim3 grid(tiles_of(a), cdiv(a.K, 32 * TN));
-    static LdsAttr configured;        // per device, set once (thread-safe: common.h)
-    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&conv_tile_kernel<T, TN, BK, ALLW>), lds)) return rc_;
-    if constexpr (TN <= 2) {
-        if (a.fold_x != nullptr) {
-            static LdsAttr configured_f;        // per device, set once (thread-safe: common.h)
-            if (int rc_ = configured_f.ensure(reinterpret_cast<const void*>(&conv_tile_kernel<T, TN, BK, ALLW, true>), lds)) return rc_;
-            FPD_LAUNCH((conv_tile_kernel<T, TN, BK, ALLW, true>), grid, dim3(256), lds, st, a, make_geo<T, BK>(a));
-            return 0;
-        }
-    }
-    if (a.fold_x != nullptr) return fpd_fail(-2, "conv_tile: a folded BN-backward apply is compiled for TN <= 2 only (fpd_conv_fold_supported)");
-    FPD_LAUNCH((conv_tile_kernel<T, TN, BK, ALLW>), grid, dim3(256), lds, st, a, make_geo<T, BK>(a));
-    return 0;
-}
-template <typename T, int TN, int BK>
-int launch_tile(const fpd_conv_t& a, hipStream_t st) {
-    if constexpr (BK == 64 || (BK == 32 && sizeof(T) == 4)) {
-        if (allw_ok<T, BK>(a, tiles_of(a) * cdiv(a.K, 32 * TN))) {
-            const int rc = launch_tile_v<T, TN, BK, true>(a, st);
-            if (rc != 1) return rc;              // 1: the nine weight tiles do not fit the LDS next to the halo
-        }
-    }
-    return launch_tile_v<T, TN, BK, false>(a, st);
-}
 
 // 32-channel output tiles per block: 4 / 2 / 1 by K, halved while the launch would have fewer than 128 blocks
 static int tile_tn(int K, int mt) {
     int tn = K > 64 ? 4 : (K > 32 ? 2 : 1);
     while (tn > 1 && mt * cdiv(K, 32 * tn) < 128) tn >>= 1;       // small layers: more, shorter blocks
     return tn;
-}
-
-template <typename T, int BK>
-int launch_tile_tn(const fpd_conv_t& a, hipStream_t st) {
-    const int tn = tile_tn(a.K, tiles_of(a));
-    if (tn == 4) return launch_tile<T, 4, BK>(a, st);
-    if (tn == 2) return launch_tile<T, 2, BK>(a, st);
-    return launch_tile<T, 1, BK>(a, st);
 }
 
 // shapes the halo-tile kernel covers: stride-1 "same" 1x1 / 3x3, rows of at most 128 pixels, C a multiple of 16
@@ -496,107 +447,112 @@ static bool tile_domain(const fpd_conv_t& a) {
 }
 // the halo of one channel chunk must fit the 8 staging vectors a thread holds
 static bool halo_fits(const fpd_conv_t& a, int vpr) { return (tile_rows(a.W) + a.R - 1) * a.W * vpr <= 2048; }
-// channel chunk of a single bf16 launch: the widest of 64 / 32 / 16 that divides C and whose halo fits (0: none).  A 3x3
-// convolution on 128-wide rows does not fit 64-channel chunks (3 rows x 128 pixels x 8 vectors): it runs on 32-channel
-// chunks instead of falling through to the generic kernel (the frozen teacher's 3x3 64->64 at 128x128: 165 us there)
-static int tile_bk_bf16(const fpd_conv_t& a) {
-    for (int bk = 64; bk >= 16; bk >>= 1)
-        if (a.C % bk == 0 && halo_fits(a, bk / 8)) return bk;
-    return 0;
+
+// The kernel variant and launch geometry of one convolution (b == nullptr) or a pair: element size, channel chunk, 32-channel
+// output tiles per block, all nine weight tiles staged, the FOLD variant
+struct TilePlan { int esz, bk, tn, tiles; bool allw, fold; size_t lds; };
+
+// The ONE decision of this unit, for the launch and for the queries.  A pair needs both in the domain with the same dtype, K
+// (n-tiling), R and channel chunking.  A BNRELU_BWD data gradient without a prologue BN is served WITH a folded BN-backward apply
+// (fpd_conv_t.fold_x) by the FOLD variants, which are compiled for TN <= 2 (register budget) and kept to channel counts for
+// which the LDS never runs out.
+static bool tile_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, TilePlan& pl) {
+    if (!tile_domain(a)) return false;
+    if (b != nullptr && (!tile_domain(*b) || a.dtype != b->dtype || a.K != b->K || a.C != b->C || a.R != b->R)) return false;
+    pl.esz = a.dtype == FPD_BF16 ? 2 : 4;
+    const int vec = 16 / pl.esz;
+    auto fits = [&](int bk) { return halo_fits(a, bk / vec) && (b == nullptr || halo_fits(*b, bk / vec)); };
+    // channel chunk: the widest of 64 (bf16 only) / 32 / 16 that divides C.  A single bf16 launch whose halo does not fit it takes
+    // the next one down: a 3x3 convolution on 128-wide rows does not fit 64-channel chunks (3 rows x 128 pixels x 8 vectors) and
+    // runs on 32-channel chunks instead of falling through to the generic kernel (the frozen teacher's 3x3 64->64 at 128x128:
+    // 165 us there)
+    pl.bk = pl.esz == 2 ? 64 : 32;
+    while (a.C % pl.bk != 0) pl.bk >>= 1;
+    if (pl.esz == 2 && b == nullptr)
+        while (pl.bk > 16 && !fits(pl.bk)) pl.bk >>= 1;
+    if (!fits(pl.bk)) return false;
+    pl.tiles = tiles_of(a) + (b ? tiles_of(*b) : 0);
+    pl.tn = tile_tn(a.K, pl.tiles);
+    // all nine weight tiles staged: small grids of a 3x3 whose C is one chunk, where they fit the LDS next to the halo
+    const bool bwd = a.epi == FPD_EPI_BNRELU_BWD || (b != nullptr && b->epi == FPD_EPI_BNRELU_BWD);
+    const int LD = pl.bk + vec;
+    auto lds_of = [&](bool allw) {
+        auto halo = [&](const fpd_conv_t& c) {
+            return (size_t)((tile_rows(c.W) + c.R - 1) * (c.W + c.R - 1) + 3) * LD * pl.esz + (size_t)(allw ? 9 : 2) * 32 * pl.tn * LD * pl.esz;
+        };
+        const size_t epi = std::max((size_t)128 * (32 * pl.tn + 4) * sizeof(float), (size_t)4 * 32 * pl.tn * 2 * sizeof(double));
+        return (size_t)((bwd ? 5 : 2) * a.C + 4 * 32 * pl.tn) * sizeof(float) + std::max({halo(a), b ? halo(*b) : (size_t)0, epi});
+    };
+    pl.allw = (pl.bk == 64 || (pl.bk == 32 && pl.esz == 4)) && a.R == 3 && a.C == pl.bk &&
+              pl.tiles * cdiv(a.K, 32 * pl.tn) <= allw_max_blocks() && lds_of(true) <= LDS_MAX;
+    pl.lds = lds_of(pl.allw);
+    if (pl.lds > LDS_MAX) return false;
+    auto foldable = [](const fpd_conv_t& c) { return c.epi == FPD_EPI_BNRELU_BWD && c.bn.mode == FPD_BN_NONE && c.C <= 128 && c.K <= 128; };
+    pl.fold = ask.fold && pl.tn <= 2 && foldable(a) && (b == nullptr || foldable(*b));
+    r = ConvRoute{pl.fold, 0, 0};
+    return true;
 }
 
 template <typename T, int TN, int BK, bool ALLW>
-int launch_pair_v(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
-    const size_t epi = std::max((size_t)128 * (32 * TN + 4) * sizeof(float), (size_t)4 * 32 * TN * 2 * sizeof(double));
-    const bool bwd = a.epi == FPD_EPI_BNRELU_BWD || b.epi == FPD_EPI_BNRELU_BWD;
-    const size_t lds = (size_t)((bwd ? 5 : 2) * std::max(a.C, b.C) + 4 * 32 * TN) * sizeof(float) +
-                       std::max({tile_lds<T, TN, BK, ALLW>(a), tile_lds<T, TN, BK, ALLW>(b), epi});
-    if (lds > LDS_MAX) return 1;
-    const int nbx_a = tiles_of(a), nbx_b = tiles_of(b);
-    dim3 grid(nbx_a + nbx_b, cdiv(a.K, 32 * TN));
-    static LdsAttr configured;        // per device, set once (thread-safe: common.h)
-    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&conv_tile_pair_kernel<T, TN, BK, ALLW>), lds)) return rc_;
+int launch_tile_v(const fpd_conv_t& a, const fpd_conv_t* bp, const TilePlan& pl, hipStream_t st) {
+    const size_t lds = pl.lds;
+    const dim3 grid(pl.tiles, cdiv(a.K, 32 * TN));
+    static LdsAttr configured, configured_f, configured_p, configured_pf;        // per device, set once (thread-safe: common.h)
+    if (bp == nullptr) {
+        if constexpr (TN <= 2) {
+            if (pl.fold) {
+                if (int rc_ = configured_f.ensure(reinterpret_cast<const void*>(&conv_tile_kernel<T, TN, BK, ALLW, true>), lds)) return rc_;
+                FPD_LAUNCH((conv_tile_kernel<T, TN, BK, ALLW, true>), grid, dim3(256), lds, st, a, make_geo<T, BK>(a));
+                return 0;
+            }
+        }
+        if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&conv_tile_kernel<T, TN, BK, ALLW>), lds)) return rc_;
+        FPD_LAUNCH((conv_tile_kernel<T, TN, BK, ALLW>), grid, dim3(256), lds, st, a, make_geo<T, BK>(a));
+        return 0;
+    }
+    const fpd_conv_t& b = *bp;
+    const int nbx_a = tiles_of(a);
     if constexpr (TN <= 2) {
-        if (a.fold_x != nullptr || b.fold_x != nullptr) {
-            static LdsAttr configured_f;        // per device, set once (thread-safe: common.h)
-            if (int rc_ = configured_f.ensure(reinterpret_cast<const void*>(&conv_tile_pair_kernel<T, TN, BK, ALLW, true>), lds)) return rc_;
+        if (pl.fold) {
+            if (int rc_ = configured_pf.ensure(reinterpret_cast<const void*>(&conv_tile_pair_kernel<T, TN, BK, ALLW, true>), lds)) return rc_;
             FPD_LAUNCH((conv_tile_pair_kernel<T, TN, BK, ALLW, true>), grid, dim3(256), lds, st, a, b, make_geo<T, BK>(a), make_geo<T, BK>(b), nbx_a);
             return 0;
         }
     }
-    if (a.fold_x != nullptr || b.fold_x != nullptr) return fpd_fail(-2, "conv_tile pair: a folded BN-backward apply is compiled for TN <= 2 only");
+    if (int rc_ = configured_p.ensure(reinterpret_cast<const void*>(&conv_tile_pair_kernel<T, TN, BK, ALLW>), lds)) return rc_;
     FPD_LAUNCH((conv_tile_pair_kernel<T, TN, BK, ALLW>), grid, dim3(256), lds, st, a, b, make_geo<T, BK>(a), make_geo<T, BK>(b), nbx_a);
     return 0;
 }
-template <typename T, int TN, int BK>
-int launch_pair(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
+// the plan's (TN, ALLW) as template arguments
+template <typename T, int BK>
+int launch_tile(const fpd_conv_t& a, const fpd_conv_t* b, const TilePlan& pl, hipStream_t st) {
     if constexpr (BK == 64 || (BK == 32 && sizeof(T) == 4)) {
-        const int blocks = (tiles_of(a) + tiles_of(b)) * cdiv(a.K, 32 * TN);
-        if (allw_ok<T, BK>(a, blocks)) {
-            const int rc = launch_pair_v<T, TN, BK, true>(a, b, st);
-            if (rc != 1) return rc;
+        if (pl.allw) {
+            if (pl.tn == 4) return launch_tile_v<T, 4, BK, true>(a, b, pl, st);
+            if (pl.tn == 2) return launch_tile_v<T, 2, BK, true>(a, b, pl, st);
+            return launch_tile_v<T, 1, BK, true>(a, b, pl, st);
         }
     }
-    return launch_pair_v<T, TN, BK, false>(a, b, st);
-}
-
-template <typename T, int BK>
-int launch_pair_tn(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
-    const int tn = tile_tn(a.K, tiles_of(a) + tiles_of(b));
-    if (tn == 4) return launch_pair<T, 4, BK>(a, b, st);
-    if (tn == 2) return launch_pair<T, 2, BK>(a, b, st);
-    return launch_pair<T, 1, BK>(a, b, st);
+    if (pl.tn == 4) return launch_tile_v<T, 4, BK, false>(a, b, pl, st);
+    if (pl.tn == 2) return launch_tile_v<T, 2, BK, false>(a, b, pl, st);
+    return launch_tile_v<T, 1, BK, false>(a, b, pl, st);
 }
 
 }  // namespace
 
-// 1 if a BNRELU_BWD data gradient without a prologue BN is served by this kernel WITH a folded BN-backward apply
-// (fpd_conv_t.fold_x): the FOLD variants are compiled for TN <= 2 (register budget) and kept to channel counts for which
-// the LDS never runs out.
-static bool tile_fold_shape(const fpd_conv_t& a) {
-    if (a.epi != FPD_EPI_BNRELU_BWD || a.bn.mode != FPD_BN_NONE || !tile_domain(a) || a.C > 128 || a.K > 128) return false;
-    if (a.dtype == FPD_BF16) return tile_bk_bf16(a) != 0;
-    return halo_fits(a, ((a.C % 32 == 0) ? 32 : 16) / 4);
+int fpd_conv_tile_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
+    TilePlan pl;
+    return tile_route(a, b, ask, r, pl) ? 0 : 1;
 }
-int fpd_conv_tile_fold_ok(const fpd_conv_t& a) { return (tile_fold_shape(a) && tile_tn(a.K, tiles_of(a)) <= 2) ? 1 : 0; }
-// -1: this kernel would not pair the two (the caller launches them one by one); else 1 / 0 as above for the pair launch
-int fpd_conv_tile_pair_fold_ok(const fpd_conv_t& a, const fpd_conv_t& b) {
-    if (!tile_domain(a) || !tile_domain(b) || a.dtype != b.dtype || a.K != b.K || a.C != b.C || a.R != b.R) return -1;
-    const int vpr = a.dtype == FPD_BF16 ? ((a.C % 64 == 0) ? 64 : ((a.C % 32 == 0) ? 32 : 16)) / 8 : ((a.C % 32 == 0) ? 32 : 16) / 4;
-    if (!halo_fits(a, vpr) || !halo_fits(b, vpr)) return -1;
-    return (tile_fold_shape(a) && tile_fold_shape(b) && tile_tn(a.K, tiles_of(a) + tiles_of(b)) <= 2) ? 1 : 0;
-}
-
-// Two independent convolutions in one launch; 1 = the pair is outside the domain (caller launches them one by one).
-// Requires both in the halo-tile domain with the same dtype, K (n-tiling), R and channel chunking.
-int fpd_conv_tile_pair_launch(const fpd_conv_t& a, const fpd_conv_t& b, hipStream_t st) {
-    if (!tile_domain(a) || !tile_domain(b)) return 1;
-    if (a.dtype != b.dtype || a.K != b.K || a.C != b.C || a.R != b.R) return 1;
-    if (a.dtype == FPD_BF16) {
-        const int bk = (a.C % 64 == 0) ? 64 : ((a.C % 32 == 0) ? 32 : 16);
-        if (!halo_fits(a, bk / 8) || !halo_fits(b, bk / 8)) return 1;
-        if (bk == 64) return launch_pair_tn<bf16_t, 64>(a, b, st);
-        if (bk == 32) return launch_pair_tn<bf16_t, 32>(a, b, st);
-        return launch_pair_tn<bf16_t, 16>(a, b, st);
+int fpd_conv_tile_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
+    ConvRoute r;
+    TilePlan pl;
+    if (!tile_route(a, b, fpd_conv_ask(a, b), r, pl)) return 1;
+    if (pl.esz == 2) {
+        if (pl.bk == 64) return launch_tile<bf16_t, 64>(a, b, pl, st);
+        if (pl.bk == 32) return launch_tile<bf16_t, 32>(a, b, pl, st);
+        return launch_tile<bf16_t, 16>(a, b, pl, st);
     }
-    const int bk = (a.C % 32 == 0) ? 32 : 16;
-    if (!halo_fits(a, bk / 4) || !halo_fits(b, bk / 4)) return 1;
-    if (bk == 32) return launch_pair_tn<float, 32>(a, b, st);
-    return launch_pair_tn<float, 16>(a, b, st);
-}
-
-// returns 1 when the shape is outside this kernel's domain (caller tries the generic MFMA kernel next)
-int fpd_conv_tile_launch(const fpd_conv_t& a, hipStream_t st) {
-    if (!tile_domain(a)) return 1;
-    if (a.dtype == FPD_BF16) {
-        const int bk = tile_bk_bf16(a);
-        if (bk == 0) return 1;
-        if (bk == 64) return launch_tile_tn<bf16_t, 64>(a, st);
-        if (bk == 32) return launch_tile_tn<bf16_t, 32>(a, st);
-        return launch_tile_tn<bf16_t, 16>(a, st);
-    }
-    const int bk = (a.C % 32 == 0) ? 32 : 16;
-    if (!halo_fits(a, bk / 4)) return 1;
-    if (bk == 32) return launch_tile_tn<float, 32>(a, st);
-    return launch_tile_tn<float, 16>(a, st);
+    if (pl.bk == 32) return launch_tile<float, 32>(a, b, pl, st);
+    return launch_tile<float, 16>(a, b, pl, st);
 }

@@ -272,3 +272,24 @@ def test_lowered_hrnet_structs_match_the_queries(R, monkeypatch):
         totals.append((B, nf, ns))
     assert not fails, '\n'.join(fails[:40])
     assert any(nf > 0 for _, nf, _ in totals), totals
+
+
+def test_launch_refuses_a_fusion_its_route_does_not_offer(R):
+    """A launch whose fields ask for a fusion its route does not offer is refused by the dispatcher, naming the query that would
+    have said so.  conv_c1 / conv_c3 / conv_pp are off, so the route is conv_tile's: no fused weight gradient at all, and no
+    folded apply at four output tiles per block (128 output channels on 128 or more pixel tiles).  The refusal comes before any
+    device call (api.hip launch_conv), so nothing is launched and the fake addresses are never dereferenced."""
+    q = Queries(R)
+
+    def refused(rc, query):
+        err = q.l.fpd_last_error().decode()
+        assert rc < 0 and query + '()' in err, (rc, err)
+
+    with _modes(R, 0, 0, 0):
+        a = _dgrad(R, 4, 64, 128, 64, 1, False)
+        assert q.slabs(a) == 0
+        refused(q.l.fpd_conv_forward(ctypes.byref(_with_slabs(a, 4)), None), 'fpd_conv_fused_wgrad_partials')
+        a, b = _dgrad(R, 4, 64, 128, 128, 1, False), _dgrad(R, 4, 32, 128, 128, 1, False)
+        assert q.fold(a) == 0 and q.pfold(a, b) == 0
+        refused(q.l.fpd_conv_forward(ctypes.byref(_with_fold(R, a)), None), 'fpd_conv_fold_supported')
+        refused(q.l.fpd_conv_forward_pair(ctypes.byref(q.pair(_with_fold(R, a), _with_fold(R, b))), None), 'fpd_conv_pair_fold_supported')
