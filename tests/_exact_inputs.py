@@ -1,0 +1,492 @@
+"""Input constructions, op lists and case lists of the bit-exact tests of the streaming kernels (tests/test_exact_stream_gpu.py
+on the device, tests/test_exact_inputs_cpu.py for the preconditions).  No device is needed to import or use this module.
+
+Everything here is a small dyadic rational, chosen so that the specification (oracle/plan_interp.py) is EXACT: a kernel that
+groups its partial sums differently, folds its coefficients in another order or rounds an fp32 accumulator to bf16 once must
+still give the same bits.
+
+  activations / gradients   small(): {-1, -0.5, 0, 0.5, 1} with zeros mixed in
+  weights                   'sparse': two non-zeros per output channel (fp32 and bf16 storage agree bit for bit);
+                            'dense': every weight in {+-0.5, +-1} (every MFMA fragment position live; the accumulator is an
+                            exact multiple of 1/4 or finer, far below 2^24, and is rounded to bf16 ONCE: deterministic)
+  train-mode BatchNorm      exact_bn(): the statistics buffer is an input, s1 = count*mu, s2 = count*(1 - 1e-5 + mu*mu), so that
+                            invstd rounds to 1.0f, scale == gamma, shift == beta - mu*gamma, mean == mu -- per channel
+  BN-backward apply         exact_apply_stats(): st[0] = count*m1, st[1] = count*m2: du = gamma*(g - m1 - (u - mu)*m2) is a
+                            multiple of 1/16 with few significant bits whatever the order of evaluation
+
+Two cancellations are avoided by construction (device and interpreter form these coefficients in fp64 with an invstd that is
+1 + O(1e-13) before it is rounded to 1.0f, so an exact zero would come out as a residue of unspecified sign and size ~1e-14):
+shift = beta - mu*gamma is never zero unless mu is, and mu*m2 - m1 is never zero unless both terms are.
+
+Where the table of per-channel coefficients is varied and where it is not: forward prologues behind DENSE filters and on
+maps of more than 2048 pixels use the coarse draw of exact_bn() (budget() says why), and on the largest of them -- the 3x3
+conv_c3 / conv_pp cases at 4096 pixels -- budget() leaves no freely drawn channel: every channel there has gamma in {0.5, 1}
+and shift in {0, -1/2}.  A mis-indexed table is therefore caught by the 'sparse' mode of those shapes (all channels free),
+by the smaller shapes (all ten (C, K) of conv_c1 at 512 pixels: 78-100 % of the channels free) and by every backward epilogue / folded apply (always the
+free draw), not by the large dense forward cases, which are there for the tiles, strips, halos and statistics.
+
+check_reference() asserts, ON THE INTERPRETER'S RESULT, the headroom that makes every fp32 sum exact in any grouping (sum of
+|addend| in units of the common power of two below 2^24, per channel / element over the whole tensor), that no output is
+degenerate, that every ReLU mask keeps 10-90 % and that more than 1 % of every normalised tensor sits exactly ON the mask
+boundary (x*scale + shift == 0: `>` against `>=` is visible)."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from fpd_amd import graph as G
+from oracle import plan_interp as PI
+from tests.test_exact_gpu import small, sparse_weights
+from tests import test_conv_c1_gpu as _c1, test_conv_c3_gpu as _c3, test_kernels_gpu as _tk
+
+RS = _tk.RS
+WMODES = ['sparse', 'dense']
+LIMIT = float(2 ** 24)
+EPS_DEVICE = float(torch.tensor(1e-5, dtype=torch.float32))      # the device adds (double)(float)1e-5
+
+
+class CpuBench:
+    """tests.test_kernels_gpu.Bench without the device: the same bump allocator, arenas of the interpreter only."""
+
+    def __init__(self, dtype):
+        self.dtype, self.sizes, self.fills = dtype, {}, []
+
+    def buf(self, arena, shape, fill=None):
+        n = int(np.prod(shape)) if len(shape) else 1
+        off = self.sizes.get(arena, 0)
+        self.sizes[arena] = off + (n + 63) // 64 * 64
+        b = G.Buf(arena, off, shape, arena)
+        if fill is not None:
+            self.fills.append((b, fill))
+        return b
+
+    def act(self, shape, fill=None, name='t'):
+        a = G.Act(shape, name)
+        a.buf = self.buf('act', shape, fill)
+        return a
+
+    def realise(self):
+        self.cpu = PI.Arenas(self.sizes, torch.bfloat16 if self.dtype == 1 else torch.float32)
+        for b, val in self.fills:
+            v = self.cpu.view(b)
+            v.copy_(val.reshape(v.shape).to(v.dtype))
+        return self
+
+    def run(self, ops):
+        PI.run(self.cpu, ops)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# constructions
+def pick(gen, values, n):
+    v = torch.tensor(values, dtype=torch.float64)
+    return v[torch.randint(0, len(values), (n,), generator=gen)]
+
+
+def weights(gen, mode, K, R, C):
+    if mode == 'sparse':
+        return sparse_weights(gen, K, R, C)
+    sign = torch.randint(0, 2, (K, R, R, C), generator=gen).float() * 2 - 1
+    return sign * torch.where(torch.rand(K, R, R, C, generator=gen) < 0.5, 0.5, 1.0)
+
+
+MU = [0.0, 0.25, -0.25, 0.5, -0.5]
+GAMMA = [0.5, 1.0, 2.0]
+BETA = [0.0, 0.25, -0.25, 0.5, -0.5, 1.0, -1.0]
+
+
+def exact_bn(bt, gen, C, count, name='bn', live=None):
+    """-> (graph.BN in train mode with ReLU, dict of the exact per-channel fp64 values mu / gamma / beta / shift).
+    live None: mu, gamma, beta drawn freely from MU, GAMMA, BETA (shift: multiples of 1/8).  One channel in 16 has mu = beta = 0.
+    live in [0, 1] -- the COARSE draw for operands of large or dense convolutions, whose second statistics sum would leave its
+    headroom otherwise: beta and mu*gamma are multiples of 1/2 (still members of the sets), so that with inputs in {-1, 0, 1}
+    the normalised operand is a multiple of 1/2; the share `live` of the channels is otherwise free, the others are QUIET:
+    gamma in {0.5, 1} and shift in {0, -1/2}, i.e. relu(bn(x)) in {0, 1/2, 1} and non-zero only where x == 1."""
+    mu, gamma, beta = pick(gen, MU, C), pick(gen, GAMMA, C), pick(gen, BETA, C)
+    if live is not None:
+        mu = torch.where(gamma == 0.5, torch.zeros_like(mu), torch.where(gamma == 1.0, torch.round(mu * 2) / 2, mu))
+        beta = torch.round(beta * 2) / 2                  # (+-0.25 -> 0)
+        quiet = torch.rand(C, generator=gen) >= live
+        qg = pick(gen, [0.5, 1.0], C)
+        qs = pick(gen, [0.0, 0.0, -0.5], C)               # shift 0 (two in three, with mu = 0: no cancellation) or -1/2
+        qmu = torch.where((qg == 1.0) & (qs != 0), pick(gen, [0.0, 0.5, -0.5], C), torch.zeros(C, dtype=torch.float64))
+        qbeta = qs + qmu * qg                             # in {0, -0.5, -1}
+        mu, gamma, beta = torch.where(quiet, qmu, mu), torch.where(quiet, qg, gamma), torch.where(quiet, qbeta, beta)
+    on = torch.randperm(C, generator=gen)[:max(1, C // 16)]      # shift == 0 exactly: every zero input sits ON the mask boundary
+    mu[on], beta[on] = 0.0, 0.0
+    if live is not None:
+        gamma[on] = qg[on]
+    cancel = (mu != 0) & (beta == mu * gamma)             # beta == mu*gamma != 0: take -beta (in the set), shift = -2 mu gamma
+    beta = torch.where(cancel, -beta, beta)
+    st = torch.zeros(RS, 2, C, dtype=torch.float64)
+    st[0, 0] = count * mu
+    st[0, 1] = count * (1.0 - 1e-5 + mu * mu)
+    bn = G.BN(name, 'train', C, bt.buf('param', (C,), gamma.float()), bt.buf('param', (C,), beta.float()),
+              bt.buf('rstat', (C,), torch.zeros(C)), bt.buf('rstat', (C,), torch.ones(C)), bt.buf('nbt', ()), relu=True)
+    bn.count = count
+    bn.stats = bt.buf('stats', (RS, 2, C), st)
+    return bn, dict(mu=mu, gamma=gamma, beta=beta, shift=beta - mu * gamma)
+
+
+M1 = [0.0, 0.25, -0.25, 0.5, -0.5]
+M2 = [0.0, 0.5, -0.5]
+
+
+def exact_apply_stats(bt, gen, C, count, mu):
+    """The two sums a BN-backward apply reads, as an input: st[0] = count*m1, st[1] = count*m2.  -> (Buf, m1, m2)"""
+    m1, m2 = pick(gen, M1, C), pick(gen, M2, C)
+    cancel = (m1 != 0) & (mu * m2 == m1)                  # mu*m2 == m1 != 0: take -m1, so mu*m2 - m1 = 2 mu m2
+    m1 = torch.where(cancel, -m1, m1)
+    st = torch.zeros(RS, 2, C, dtype=torch.float64)
+    st[0, 0], st[0, 1] = count * m1, count * m2
+    return bt.buf('stats', (RS, 2, C), st), m1, m2
+
+
+def _limbs(v):
+    """A statistics value as the device holds it (csrc/common.h stat_split / stat_join, executor.Arenas.stats_write)."""
+    hi = torch.round(v * 2.0 ** 20)
+    lo = torch.round((v - hi / 2.0 ** 20) * 2.0 ** 60)
+    return hi * (1.0 / 2.0 ** 20) + lo * (1.0 / 2.0 ** 60)
+
+
+def device_bn_coef(st, gamma, beta, count, eps=EPS_DEVICE):
+    """csrc/common.h bn_resolve on [R][2][C] fp64 statistics that went through the limb split -> scale, shift, mean, invstd (fp32)."""
+    s = _limbs(st).sum(0)
+    m = s[0] / count
+    var = (s[1] / count - m * m).clamp_min(0)
+    inv = 1.0 / torch.sqrt(var + eps)
+    g = gamma.double()
+    return (g * inv).float(), (beta.double() - m * g * inv).float(), m.float(), inv.float()
+
+
+def device_fold_coef(st, bst, gamma, count, eps=EPS_DEVICE):
+    """The folded BN-backward apply as conv_c1 / conv_c3 / conv_pp form it: du = A g + B u + D  -> A, B, D (fp32)."""
+    s, b = _limbs(st).sum(0), _limbs(bst).sum(0)
+    mu = s[0] / count
+    var = (s[1] / count - mu * mu).clamp_min(0)
+    inv = 1.0 / torch.sqrt(var + eps)
+    gi = gamma.double() * inv
+    m1, m2 = b[0] / count, b[1] / count
+    return gi.float(), (-gi * inv * m2).float(), (gi * (mu * inv * m2 - m1)).float()
+
+
+class Built:
+    """ops: the op list; compare: [(label, Buf or Act)] to check bit for bit; bns: {graph.BN: exact values}; applies: {apply op: (m1, m2)}"""
+
+    def __init__(self):
+        self.ops, self.compare, self.bns, self.applies, self.h = [], [], {}, {}, {}
+
+    def bn(self, bt, gen, C, count, name='bn', live=None):
+        bn, ex = exact_bn(bt, gen, C, count, name, live)
+        self.bns[bn] = ex
+        return bn
+
+
+def budget(n, terms, use_bn):
+    """-> (input density, share of freely drawn BN channels or None) of a forward convolution with `terms` non-zero taps per
+    output channel over n pixels, so that the second statistics sum keeps its headroom: sum v*v / q^2 < 2^24, i.e.
+    mean v*v < 2^24 q^2 / n per channel.  An eighth of that is budgeted (the bound holds per channel; bias, residual and the
+    channel means of the operand, which add up coherently over the pixels, weigh on single channels); mean v*v ~ terms * E[w*w] * E[a*a], E[w*w] = 0.625.
+      no prologue    v is a multiple of q = 1/4; E[a*a] ~ d / 2 for a raw operand of density d: d follows, at most 0.6
+      BN prologue    two taps per channel on up to 2048 pixels: the free draw, v a multiple of 1/16;
+                     else the coarse draw of exact_bn() on inputs in {-1, 0, 1} of density 0.6: v a multiple of 1/4, E[a*a] ~ 0.09
+                     on a quiet channel (the ReLU keeps 17 % of it) and ~ 4 on a free one (mean included): the share of free channels follows
+    (estimates only: the bound itself is asserted by check_reference() on the interpreter's result)"""
+    A = 0.125 * 2.0 ** 24 / 16.0 / n / (terms * 0.625)
+    if not use_bn:
+        return min(0.6, 4.0 * A), None
+    if terms == 2 and n <= 2048:
+        return 0.6, None
+    return 0.6, max(0.0, min(1.0, (A - 0.09) / 4.0))
+
+
+def forward(bt, gen, dims, wmode, use_bn, use_res, b=None):
+    """conv (R x R, 'same') + bias (+ residual) + output statistics, behind an exact train-mode BN+ReLU prologue or none."""
+    N, H, W, C, K, R = dims
+    b = b or Built()
+    density, live = budget(N * H * W, C * R * R if wmode == 'dense' else 2, use_bn)
+    xv = small(gen, N, H, W, C, density=density)
+    if live is not None:                                  # coarse draw: {-1, 0, 1}
+        xv = torch.randint(-1, 2, (N, H, W, C), generator=gen).float() * (xv != 0)
+    x = bt.act((N, H, W, C), xv, 'x')
+    w = bt.buf('wlp', (K, R, R, C), weights(gen, wmode, K, R, C))
+    bias = bt.buf('param', (K,), small(gen, K))
+    res = bt.act((N, H, W, K), small(gen, N, H, W, K), 'res') if use_res else None
+    y = bt.act((N, H, W, K), None, 'y')
+    bn = b.bn(bt, gen, C, N * H * W, live=live) if use_bn else None
+    ostats = bt.buf('stats', (RS, 2, K), torch.zeros(RS, 2, K, dtype=torch.float64))
+    op = G.Op('conv', x=x, w=w, wkey='w', bias=bias, bkey='b', residual=res, y=y, out_stats=ostats, bn=bn, epi='plain',
+              epi_x=None, epi_bn=None, epi_stats=None, dims=(N, H, W, C, K, R, R, 1, (R - 1) // 2, H, W))
+    b.ops.append(op)
+    b.compare += [('y', y), ('out_stats', ostats)]
+    return b, op
+
+
+def dgrad(bt, gen, dims, wmode, fold, fuse, b=None):
+    """The op list of tests.test_conv_c1_gpu._dgrad_ops on exact inputs: forward convolution u = conv(relu(bn(x))), C -> K (R x R);
+    its BatchNorm-backward data gradient (K -> C, flipped weights through 'wprep'), optionally behind the folded backward apply
+    of the BN on u, and its weight / bias gradient (fused into the data gradient's launch where the kernel offers it)."""
+    N, H, W, C, K, R = dims
+    b = b or Built()
+    pad, cnt = (R - 1) // 2, N * H * W
+    x = bt.act((N, H, W, C), small(gen, N, H, W, C), 'x')
+    wm = bt.buf('param', (K, R, R, C), weights(gen, wmode, K, R, C))
+    wb = bt.buf('wlp', (C, R, R, K))
+    dz = bt.act((N, H, W, C), None, 'dz')
+    bn = b.bn(bt, gen, C, cnt)
+    bst = bt.buf('stats', (RS, 2, C), torch.zeros(RS, 2, C, dtype=torch.float64))
+    dw = bt.buf('grad', (K, R, R, C), torch.zeros(K, R, R, C))
+    db = bt.buf('grad', (K,), torch.zeros(K))
+    b.ops.append(G.Op('wprep', entries=[{'w': wm, 'w_fwd': None, 'w_bwd': wb}]))
+    b.compare += [('dz', dz), ('bn-backward sums', bst), ('dw', dw), ('dbias', db)]
+    ap = None
+    if fold:
+        u = bt.act((N, H, W, K), small(gen, N, H, W, K), 'u')
+        # (half magnitudes: |g - m1 - (u - mu) m2| <= 1.75, so that the sum of two 'sparse' taps of du stays within 8 bits)
+        g = bt.act((N, H, W, K), 0.5 * small(gen, N, H, W, K), 'g')
+        du = bt.act((N, H, W, K), None, 'du')
+        bn2 = b.bn(bt, gen, K, cnt, 'bn2')
+        bst2, m1, m2 = exact_apply_stats(bt, gen, K, cnt, b.bns[bn2]['mu'])
+        dgam, dbet = bt.buf('grad', (K,), torch.zeros(K)), bt.buf('grad', (K,), torch.zeros(K))
+        ap = G.Op('ew', op='bn_bwd_apply', dims=(N, H, W, K), x=u, x2=None, dy=g, add=None, y=du, out_stats=None, bstats=bst2,
+                  dgamma=dgam, dbeta=dbet, bn=bn2)
+        b.applies[ap] = (m1, m2)
+        b.ops.append(ap)
+        dy = du
+        b.compare += [('dgamma', dgam), ('dbeta', dbet)]
+        b.h['du'] = du
+    else:
+        dy = bt.act((N, H, W, K), small(gen, N, H, W, K), 'dy')
+    wg = G.Op('wgrad', x=x, dy=dy, dw=dw, dbias=db, bn=bn, dims=(N, H, W, C, K, R, R, 1, pad, H, W))
+    dg = G.Op('conv', x=dy, w=wb, wkey='w', bias=None, bkey=None, residual=None, y=dz, out_stats=None, bn=None,
+              epi='bnrelu_bwd', epi_x=x, epi_bn=bn, epi_stats=bst, dims=(N, H, W, K, C, R, R, 1, R - 1 - pad, H, W))
+    if fold:
+        dg.fold_apply, dg.fold_wgrad = ap, wg
+    if fuse:
+        dg.fused_wgrad = wg
+    b.ops += [dg, wg]
+    b.h['dg'] = dg
+    return b
+
+
+def pair(bt, gen, dims, wmode, use_bn, epi):
+    """'conv2': the same convolution at full and at half resolution in one launch, forward ('plain': bias + output statistics,
+    optionally an exact BN prologue) or as a BatchNorm-backward data gradient ('bnrelu_bwd')."""
+    N, H, W, C, K, R = dims
+    b = Built()
+    subs = []
+    for (h, w_) in ((H, W), (H // 2, W // 2)):
+        if epi == 'plain':
+            _, op = forward(bt, gen, (N, h, w_, C, K, R), wmode, use_bn, False, b)
+            b.ops.pop()
+        else:
+            x = bt.act((N, h, w_, C), small(gen, N, h, w_, C), 'x')
+            wt = bt.buf('wlp', (K, R, R, C), weights(gen, wmode, K, R, C))
+            y = bt.act((N, h, w_, K), None, 'y')
+            ex = bt.act((N, h, w_, K), small(gen, N, h, w_, K), 'ex')
+            ebn = b.bn(bt, gen, K, N * h * w_, 'ebn')
+            est = bt.buf('stats', (RS, 2, K), torch.zeros(RS, 2, K, dtype=torch.float64))
+            op = G.Op('conv', x=x, w=wt, wkey='', bias=None, bkey='', residual=None, y=y, bn=None, out_stats=None, epi='bnrelu_bwd',
+                      epi_x=ex, epi_bn=ebn, epi_stats=est, dims=(N, h, w_, C, K, R, R, 1, (R - 1) // 2, h, w_))
+            b.compare += [('dz', y), ('bn-backward sums', est)]
+        subs.append(op)
+    b.ops.append(G.Op('conv2', a=subs[0], b=subs[1]))
+    return b
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the checks on the reference
+def quantum(t):
+    """Smallest power of two that every element of t is a multiple of (1.0 for an all-zero tensor)."""
+    t = t.double().reshape(-1)
+    t = t[t != 0]
+    q = 1.0
+    while t.numel() and not torch.equal(t / q, torch.round(t / q)):
+        q *= 0.5
+        assert q > 2.0 ** -40, 'not a small dyadic tensor'
+    return q
+
+
+def _headroom(total, q, label):
+    worst = float(total.max()) / q if total.numel() else 0.0
+    assert worst < LIMIT, '%s: sum |addend| = %.0f units of 2^%d -- not below 2^24, the fp32 sums are not exact in every grouping' % (
+        label, worst, int(np.log2(q)))
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _check_bn(A, bn, ex, xv, label):
+    scale, shift, mean, invstd = PI._bn_coef(A, bn)
+    assert torch.equal(scale.double(), ex['gamma']) and torch.equal(shift.double(), ex['shift']), label + ': scale / shift not exact'
+    assert torch.equal(mean.double(), ex['mu']) and bool((invstd == 1.0).all()), label + ': mean / invstd not exact'
+    if xv is None:
+        return
+    z = torch.addcmul(shift, xv, scale)
+    on = float((z == 0).float().mean())
+    assert on > 0.01, '%s: only %.2f %% of the elements sit on the mask boundary' % (label, 100 * on)
+    keep = float((z > 0).float().mean())
+    assert 0.1 <= keep <= 0.9, '%s: the ReLU mask keeps %.1f %%' % (label, 100 * keep)
+
+
+def _check_conv(A, b, op, label):
+    n, h, w, C, K, R, S, stride, pad, P, Q = op.dims
+    x = PI._act(A, op.x)
+    if op.bn is not None:
+        _check_bn(A, op.bn, b.bns[op.bn], x, label + ' prologue')
+        x = PI._prologue(A, x, op.bn)
+    wt = A.view(op.w).float()
+    acc = F.conv2d(_nchw(x.abs()).double(), _nchw(wt.abs()).double(), None, padding=pad)
+    extra = [A.view(op.bias).double()] if op.bias is not None else []
+    extra += [PI._act(A, op.residual).double()] if op.residual is not None else []
+    q = min([quantum(x) * quantum(wt)] + [quantum(e) for e in extra])
+    _headroom(acc + 2.0, q, label + ' accumulator')       # (+ |bias| + |residual| <= 2)
+    y = PI._act(A, op.y).double()
+    assert float(y.abs().max()) > 0, label + ': all-zero output'
+    if op.epi == 'bnrelu_bwd':
+        xv = PI._act(A, op.epi_x)
+        _check_bn(A, op.epi_bn, b.bns[op.epi_bn], xv, label + ' epilogue')
+        xhat = (xv.double() - b.bns[op.epi_bn]['mu'])
+        _headroom(y.abs().sum((0, 1, 2)), quantum(y), label + ' sum dz')
+        _headroom((y * xhat).abs().sum((0, 1, 2)), quantum(y) * quantum(xhat), label + ' sum dz*xhat')
+        st = A.view(op.epi_stats).sum(0)
+        assert float(st[0].abs().max()) > 0 and float(st[1].abs().max()) > 0, label + ': all-zero sums'
+    elif op.out_stats is not None:
+        _headroom(y.abs().sum((0, 1, 2)), quantum(y), label + ' sum v')
+        _headroom((y * y).sum((0, 1, 2)), quantum(y) ** 2, label + ' sum v*v')
+
+
+def _check_wgrad(A, b, op, label):
+    n, h, w, C, K, R, S, stride, pad, P, Q = op.dims
+    a = PI._prologue(A, PI._act(A, op.x), op.bn).double()
+    dy = PI._act(A, op.dy).double()
+    tot = torch.nn.grad.conv2d_weight(_nchw(a.abs()), (K, C, R, S), _nchw(dy.abs()), padding=pad)
+    _headroom(tot, quantum(a) * quantum(dy), label + ' dw')
+    _headroom(dy.abs().sum((0, 1, 2)), quantum(dy), label + ' dbias')
+    assert float(A.view(op.dw).abs().max()) > 0 and float(A.view(op.dbias).abs().max()) > 0, label + ': all-zero gradient'
+
+
+def _check_apply(A, b, op, label):
+    m1, m2 = b.applies[op]
+    ex = b.bns[op.bn]
+    _check_bn(A, op.bn, ex, None, label + ' folded BN')       # (coefficients only: a backward apply has no ReLU)
+    u, g = PI._act(A, op.x).double(), PI._act(A, op.dy).double()
+    du = ex['gamma'] * (g - m1 - (u - ex['mu']) * m2)
+    assert torch.equal(PI._act(A, op.y).double(), du), label + ': du is not the exact value'
+    assert torch.equal(du, torch.round(du * 16) / 16) and float(du.abs().max()) <= 4.5
+    assert torch.equal(A.view(op.dgamma).double(), op.bn.count * m2) and torch.equal(A.view(op.dbeta).double(), op.bn.count * m1)
+    assert not bool(((ex['mu'] * m2 - m1 == 0) & (m1 != 0)).any()), label + ': mu*m2 - m1 cancels'
+
+
+def check_reference(A, b, label=''):
+    """The preconditions of a bit-exact comparison, asserted on the arenas the interpreter has run `b.ops` over."""
+    for ex in b.bns.values():
+        assert not bool(((ex['shift'] == 0) & (ex['mu'] != 0)).any()), label + ': beta - mu*gamma cancels'
+    for op in b.ops:
+        for o in ((op.a, op.b) if op.kind == 'conv2' else (op,)):
+            if o.kind == 'conv':
+                _check_conv(A, b, o, label + ' conv')
+            elif o.kind == 'wgrad':
+                _check_wgrad(A, b, o, label + ' wgrad')
+            elif o.kind == 'ew':
+                _check_apply(A, b, o, label + ' apply')
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# case lists (shapes of the random-input tests of the same kernels, capped at 4 x 32 x 32 x 128 elements per tensor)
+def _cap(N, H, W, ch):
+    """At most 2^19 elements and 4096 pixels: the maps keep their width (the tile geometry), lose images, then rows."""
+    while N > 1 and (N * H * W * ch > 2 ** 19 or N * H * W > 4096):
+        N -= 1
+    while N * H * W * ch > 2 ** 19 or N * H * W > 4096:
+        H //= 2
+    return N, H, W
+
+
+# conv_c1 forward: (N, H, W, C, K, blocks).  Every (C, K) of the random-input cases at 16 tiles with ONE block (two rounds in a
+# loop), the ragged / idle-block shapes, more blocks than rounds, an uneven split of 8 rounds (3 / 3 / 2)
+C1_FWD = [(2, 16, 16, c, k, 1) for c, k in sorted({(c[3], c[4]) for c in _c1.FWD_CASES})] + [
+    (1, 4, 40, 128, 64, 2), (3, 4, 8, 64, 128, 1), (1, 8, 52, 64, 64, 3), (2, 32, 32, 32, 128, 256), (2, 32, 32, 128, 64, 3)]
+C1_FWD_VARIANTS = [(True, True), (True, False), (False, True), (False, False)]      # (BN prologue, residual)
+# conv_c1 data gradient: forward convolution C -> K.  (N, H, W, C, K, blocks)
+C1_BWD = [(1, 4, 40, 64, 128, 2), (3, 4, 8, 128, 64, 1), (1, 8, 52, 64, 128, 3), (2, 32, 32, 128, 64, 3), (4, 32, 32, 64, 128, 5)]
+# ... of the score (128 -> 16) and fc_ (128 -> 128) convolutions: taken unfolded, weight gradient a launch of its own
+C1_BWD_UNFUSED = [(3, 16, 16, 128, 16, 2), (2, 32, 32, 128, 16, 3), (3, 16, 16, 128, 128, 2), (2, 32, 32, 128, 128, 3)]
+C1_PAIR = [c[:5] + (c[5] is not None, c[6], c[7]) for c in _c1.PAIR_CASES]          # (N, H, W, C, K, bn, epi, blocks)
+
+
+def _c3_cap(N, H, W):
+    return (1 if H * W == 64 * 64 else N), H, W
+
+
+# conv_c3 (C = K = 64, 3x3): (N, H, W, bn, blocks) / (N, H, W, blocks); 64 x 64 maps at N = 1
+C3_FWD = [_c3_cap(*c[:3]) + (c[3] is not None, c[5]) for c in _c3.FWD_CASES]
+C3_BWD = [_c3_cap(*c[:3]) + (c[3],) for c in _c3.BWD_CASES]
+# (the pair shapes of tests/test_conv_c3_gpu.py test_c3_pair)  (N, H, W, bn, epi, blocks)
+C3_PAIR = [(1, 64, 64, True, 'plain', 6), (3, 32, 32, True, 'plain', 3), (1, 64, 64, False, 'bnrelu_bwd', 5)]
+# forced conv_pp: (N, H, W, C, K, R, bn, residual, blocks)
+PP_FWD = [_cap(c[0], c[1], c[2], max(c[3], c[4])) + (c[3], c[4], c[5], c[6] is not None, c[7], c[8]) for c in _tk.PP_CASES]
+# ... data gradient with fold and fused weight gradient: two 1x1 rows of FOLD_CASES.  (N, H, W, C, K, blocks)
+PP_BWD = [c[:5] + (c[6],) for c in _tk.FOLD_CASES if c in ((3, 20, 48, 64, 32, 1, 3, True), (2, 32, 32, 128, 64, 1, 4, True))]
+assert (len(PP_BWD), len(C1_PAIR), len(C3_FWD), len(C3_BWD), len(PP_FWD)) == (2, 4, 8, 5, 12), 'a case list this module derives from has changed'
+
+
+def seed(*parts):
+    """A generator seeded by the case (ints, bools and short strings)."""
+    s = 0
+    for p in parts:
+        for v in (p if isinstance(p, tuple) else (p,)):
+            s = (s * 31 + (sum(map(ord, v)) if isinstance(v, str) else int(v))) % (2 ** 31 - 1)
+    return torch.Generator().manual_seed(1000 + s)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one builder per test family: (bench, parameters...) -> Built.  FAMILIES lists every parameter tuple of every family, for the
+# device tests and for the precondition tests alike
+def c1_forward(bt, case, wmode, variant):
+    return forward(bt, seed('c1f', case, wmode, variant), case[:5] + (1,), wmode, *variant)[0]
+
+
+def c1_dgrad(bt, case, wmode, fold, fuse):
+    return dgrad(bt, seed('c1b', case, wmode, fold, fuse), case[:5] + (1,), wmode, fold, fuse)
+
+
+def c1_dgrad_unfused(bt, case, wmode):
+    return dgrad(bt, seed('c1u', case, wmode), case[:5] + (1,), wmode, False, True)
+
+
+def c1_pair(bt, case, wmode):
+    return pair(bt, seed('c1p', case, wmode), case[:5] + (1,), wmode, case[5], case[6])
+
+
+def c3_forward(bt, case, wmode):
+    return forward(bt, seed('c3f', case, wmode), case[:3] + (64, 64, 3), wmode, case[3], False)[0]
+
+
+def c3_dgrad(bt, case, wmode, fold):
+    return dgrad(bt, seed('c3b', case, wmode, fold), case[:3] + (64, 64, 3), wmode, fold, False)
+
+
+def c3_pair(bt, case, wmode):
+    return pair(bt, seed('c3p', case, wmode), case[:3] + (64, 64, 3), wmode, case[3], case[4])
+
+
+def pp_forward(bt, case, wmode):
+    return forward(bt, seed('ppf', case, wmode), case[:6], wmode, case[6], case[7])[0]
+
+
+def pp_dgrad(bt, case, wmode):
+    return dgrad(bt, seed('ppb', case, wmode), case[:5] + (1,), wmode, True, True)
+
+
+FAMILIES = [
+    (c1_forward, [(c, m, v) for c in C1_FWD for m in WMODES for v in C1_FWD_VARIANTS]),
+    (c1_dgrad, [(c, m, fo, fu) for c in C1_BWD for m in WMODES for fo in (False, True) for fu in (False, True)]),
+    (c1_dgrad_unfused, [(c, m) for c in C1_BWD_UNFUSED for m in WMODES]),
+    (c1_pair, [(c, m) for c in C1_PAIR for m in WMODES]),
+    (c3_forward, [(c, m) for c in C3_FWD for m in WMODES]),
+    (c3_dgrad, [(c, m, fo) for c in C3_BWD for m in WMODES for fo in (False, True)]),
+    (c3_pair, [(c, m) for c in C3_PAIR for m in WMODES]),
+    (pp_forward, [(c, m) for c in PP_FWD for m in WMODES]),
+    (pp_dgrad, [(c, m) for c in PP_BWD for m in WMODES]),
+]
