@@ -84,6 +84,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_bn_t); SZ(fpd_conv_t); SZ(fpd_wgrad_t); SZ(fpd_stem_t); SZ(fpd_ew_t); SZ(fpd_loss_t); SZ(fpd_adam_t);
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
+    SZ(fpd_loss_ohkm_t);
 #undef SZ
     return -1;
 }
@@ -454,6 +455,38 @@ int fpd_loss(const fpd_loss_t* a, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+static int validate_loss_dims(const fpd_loss_t* a, const char* what) {
+    FPD_REQUIRE(a, "%s: null pointer", what);
+    FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0, "%s: non-positive dimension", what);
+    if (a->J > FPD_MAX_JOINTS || a->S > FPD_MAX_STACKS || a->S < 1)
+        return fpd_fail(-3, "%s: J=%d (<=%d), S=%d (1..%d)", what, a->J, FPD_MAX_JOINTS, a->S, FPD_MAX_STACKS);
+    FPD_REQUIRE((int64_t)a->B * a->H * a->W * a->J < ((int64_t)1 << 31), "%s: tensor too large for 32-bit indexing", what);
+    return 0;
+}
+
+int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a) {
+    const int rc = validate_loss_dims(a, "loss_ohkm_scratch_bytes");
+    return rc ? rc : fpd_loss_ohkm_scratch_size(*a);
+}
+
+int fpd_loss_ohkm(const fpd_loss_ohkm_t* k, fpd_stream_t stream) {
+    FPD_REQUIRE(k, "loss_ohkm: null pointer");
+    const fpd_loss_t* a = &k->base;
+    FPD_REQUIRE(a->teacher && a->target && a->weight && a->losses, "loss_ohkm: null pointer");
+    int rc = validate_loss_dims(a, "loss_ohkm");
+    if (rc) return rc;
+    FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "loss_ohkm: bad dtype %d", a->dtype);
+    for (int s = 0; s < a->S; ++s) FPD_REQUIRE(a->out[s], "loss_ohkm: null map of stack %d", s);
+    FPD_REQUIRE(k->topk_pose >= 1 && k->topk_pose <= a->J && k->topk_kd >= 1 && k->topk_kd <= a->J,
+                "loss_ohkm: topk (%d, %d) outside [1, J=%d]", k->topk_pose, k->topk_kd, a->J);
+    const int64_t need = fpd_loss_ohkm_scratch_size(*a);
+    FPD_REQUIRE(k->scratch && ((uintptr_t)k->scratch & 7) == 0, "loss_ohkm: scratch is null or not 8-byte aligned");
+    FPD_REQUIRE(k->scratch_bytes >= need, "loss_ohkm: scratch of %lld bytes, fpd_loss_ohkm_scratch_bytes() asks for %lld",
+                (long long)k->scratch_bytes, (long long)need);
+    rc = fpd_loss_ohkm_launch(*k, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a && a->param && a->grad && a->m && a->v && a->n >= 0, "adam: null pointer");
     int rc = fpd_adam_launch(*a, (hipStream_t)stream);
@@ -487,7 +520,7 @@ int fpd_nhwc_to_nchw(const void* src, float* dst, int32_t N, int32_t C, int32_t 
 struct fpd_op {
     int32_t type;
     union {
-        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_adam_t adam;
+        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_adam_t adam;
         fpd_memset_t mset; fpd_table_t table;
     } u;
 };
@@ -541,6 +574,7 @@ int fpd_plan_add(fpd_plan* p, int32_t op, const void* args, int64_t bytes) {
         case FPD_OP_STEM_FWD: case FPD_OP_STEM_WGRAD: want = sizeof(fpd_stem_t); break;
         case FPD_OP_EW: want = sizeof(fpd_ew_t); break;
         case FPD_OP_LOSS: want = sizeof(fpd_loss_t); break;
+        case FPD_OP_LOSS_OHKM: want = sizeof(fpd_loss_ohkm_t); break;
         case FPD_OP_ADAM: want = sizeof(fpd_adam_t); break;
         case FPD_OP_MEMSET: case FPD_OP_NOP: want = sizeof(fpd_memset_t); break;
         case FPD_OP_AFFSUM: want = sizeof(fpd_affsum_t); break;
@@ -609,6 +643,7 @@ static void set_op_tag(int idx, const fpd_op& o) {
         case FPD_OP_STEM_FWD: case FPD_OP_STEM_WGRAD: snprintf(t, sizeof(t), "%s N=%d H=%d W=%d K=%d", o.type == FPD_OP_STEM_FWD ? "stem_fwd" : "stem_wgrad", o.u.stem.N, o.u.stem.H, o.u.stem.W, o.u.stem.K); break;
         case FPD_OP_AFFSUM: snprintf(t, sizeof(t), "affsum N=%d H=%d W=%d C=%d terms=%d", o.u.affsum.N, o.u.affsum.H, o.u.affsum.W, o.u.affsum.C, o.u.affsum.nterms); break;
         case FPD_OP_LOSS: snprintf(t, sizeof(t), "loss B=%d J=%d H=%d W=%d S=%d", o.u.loss.B, o.u.loss.J, o.u.loss.H, o.u.loss.W, o.u.loss.S); break;
+        case FPD_OP_LOSS_OHKM: snprintf(t, sizeof(t), "loss_ohkm B=%d J=%d H=%d W=%d S=%d k=%d,%d", o.u.lossk.base.B, o.u.lossk.base.J, o.u.lossk.base.H, o.u.lossk.base.W, o.u.lossk.base.S, o.u.lossk.topk_pose, o.u.lossk.topk_kd); break;
         case FPD_OP_ADAM: snprintf(t, sizeof(t), "adam n=%lld", (long long)o.u.adam.n); break;
         case FPD_OP_WREDUCE: snprintf(t, sizeof(t), "wreduce entries=%d", o.u.table.n); break;
         case FPD_OP_WPREP: snprintf(t, sizeof(t), "wprep entries=%d", o.u.table.n); break;
@@ -636,6 +671,7 @@ static int run_op(const fpd_op& o, fpd_stream_t s) {
         case FPD_OP_STEM_WGRAD: return fpd_stem_wgrad(&o.u.stem, s);
         case FPD_OP_EW: return fpd_elementwise(&o.u.ew, s);
         case FPD_OP_LOSS: return fpd_loss(&o.u.loss, s);
+        case FPD_OP_LOSS_OHKM: return fpd_loss_ohkm(&o.u.lossk, s);
         case FPD_OP_ADAM: return fpd_adam(&o.u.adam, s);
         case FPD_OP_MEMSET: {
             FPD_CHECK_HIP(hipMemsetAsync(o.u.mset.ptr, 0, (size_t)o.u.mset.bytes, (hipStream_t)s));

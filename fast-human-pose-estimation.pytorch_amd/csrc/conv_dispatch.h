@@ -81,6 +81,8 @@ int fpd_elementwise_launch(const fpd_ew_t& a, hipStream_t st);
 int fpd_elementwise_pair_launch(const fpd_ew_t& a, const fpd_ew_t& b, hipStream_t st);
 int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st);
 int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
+int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& a, hipStream_t st);      // csrc/loss_ohkm.hip: two launches
+int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a);
 int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st);
 int fpd_weight_prep_launch(const fpd_wprep_entry_t* table, int n, int64_t max_elems, int dtype, hipStream_t st);
 int fpd_bn_update_running_launch(const fpd_bnupd_entry_t* table, int n, hipStream_t st);

@@ -19,7 +19,7 @@ _EW = {'bnrelu_fwd': R.EW_BNRELU_FWD, 'bnrelu_bwd_r': R.EW_BNRELU_BWD_R, 'bn_bwd
 _ARENA_DTYPE = {'param': torch.float32, 'grad': torch.float32, 'rstat': torch.float32, 'nbt': torch.int64,
                 'stats': torch.int64, 'losses': torch.float64, 'image': torch.float32, 'target': torch.float32,
                 'weight': torch.float32, 'adam_m': torch.float32, 'adam_v': torch.float32, 'fold': torch.float32,
-                'w8': torch.uint8, 'w8s': torch.float32}
+                'w8': torch.uint8, 'w8s': torch.float32, 'ohkm_scratch': torch.float64, 'ohkm_masks': torch.int32}
 
 
 def act_torch_dtype(dtype):
@@ -652,7 +652,7 @@ class FusedFPDStep:
 
     def __init__(self, student_state, student_cfg, teacher_state, teacher_cfg, batch, height, width, alpha,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, world_size=1, adam=None, teacher_chunks=None,
-                 use_target_weight=(True, True)):
+                 use_target_weight=(True, True), ohkm=None):
         dev = student_state.device
         # JointsMSELoss(use_target_weight) of the pose / distillation criterion (tools/fpd_train.py:145-147,177-179):
         # False = that term ignores the loader's target_weight (loss.py:30-37), i.e. a weight buffer of ones
@@ -660,6 +660,13 @@ class FusedFPDStep:
         self.dtype = student_state.dtype
         self.alpha, self.world_size = alpha, world_size
         self.B, self.J = batch, student_cfg['J']
+        # JointsOHKMMSELoss(topk) of the pose / distillation criterion: (k_pose or None, k_kd or None); None (the default) is the
+        # JointsMSELoss pair and the plan of before; a None inside the pair is a JointsMSELoss term = every joint kept
+        self.ohkm = None
+        if ohkm is not None:
+            self.ohkm = tuple(self.J if k is None else int(k) for k in ohkm)
+            if len(self.ohkm) != 2 or not all(1 <= k <= self.J for k in self.ohkm):
+                raise R.FpdError('FusedFPDStep: ohkm=%r: topk must lie in [1, J=%d]' % (ohkm, self.J))
         # teacher first: it owns the image buffer; its last-stack map is read in place by the loss kernel
         self.teacher = None
         self.teachers = []
@@ -701,11 +708,20 @@ class FusedFPDStep:
         if not self.use_w[0]:
             A.tensor('weight').fill_(1.0)
         A.alloc('losses', 4)
+        if self.ohkm is not None:
+            d = R.LossT()
+            d.B, d.J, d.H, d.W, d.S = self.B, self.J, self.hh, self.hw, len(g.outputs)
+            nbytes = R.lib().fpd_loss_ohkm_scratch_bytes(d)
+            if nbytes < 0:
+                R.check(int(nbytes), 'fpd_loss_ohkm_scratch_bytes')
+            A.alloc('ohkm_scratch', nbytes // 8)
+            A.alloc('ohkm_masks', len(g.outputs) * 2 * self.B)
         self.student.mid_ops = [G.Op('loss', extra_in=list(g.outputs), extra_out=list(g.out_grads))]
-        self.student.mid_native = [lambda plan: self._add_loss(plan, 0)]
+        add_loss = self._add_loss if self.ohkm is None else self._add_loss_ohkm
+        self.student.mid_native = [lambda plan: add_loss(plan, 0)]
         self.student.finalize()
         b = len(self.student.plan)                 # second loss op reading the other staged teacher map
-        self._add_loss(self.student.plan, 1)
+        add_loss(self.student.plan, 1)
         self.student.rng['mid1'] = (b, len(self.student.plan))
         # optimizer state (torch.optim.Adam semantics, lib/utils/utils.py:69-73)
         n = student_state.table.sizes['param']
@@ -749,10 +765,9 @@ class FusedFPDStep:
                 A.ptr(g.outputs[-1].buf), A.tensor('target').data_ptr(), A.tensor('losses').data_ptr())
         return self.metric
 
-    def _add_loss(self, plan, slot):
+    def _fill_loss(self, s, slot):
+        """The fpd_loss_t both loss ops share: maps and gradients of every stack, the staged teacher map of `slot`, target, weights."""
         A, g = self.student.A, self.student.g
-        plan.add(*self.student.low.memset('losses'))
-        s = R.LossT()
         s.B, s.J, s.H, s.W, s.S, s.dtype = self.B, self.J, self.hh, self.hw, len(g.outputs), self.dtype
         s.target_nchw, s.alpha = 1, self.alpha
         for i, (o, d) in enumerate(zip(g.outputs, g.out_grads)):
@@ -766,7 +781,30 @@ class FusedFPDStep:
         s.weight_kd = A.tensor('weight_kd').data_ptr() if 'weight_kd' in A.t else None
         s.losses = A.tensor('losses').data_ptr()
         s.grad_scale = 1.0 / self.world_size
+
+    def _add_loss(self, plan, slot):
+        plan.add(*self.student.low.memset('losses'))
+        s = R.LossT()
+        self._fill_loss(s, slot)
         plan.add(R.OP_LOSS, s)
+
+    def _add_loss_ohkm(self, plan, slot):
+        """_add_loss with hard-keypoint mining (csrc/loss_ohkm.hip): the same arguments + topk pair, scratch and masks."""
+        A = self.student.A
+        plan.add(*self.student.low.memset('losses'))
+        k = R.LossOhkmT()
+        self._fill_loss(k.base, slot)
+        k.topk_pose, k.topk_kd = self.ohkm
+        sc = A.tensor('ohkm_scratch')
+        k.scratch, k.scratch_bytes = sc.data_ptr(), sc.numel() * sc.element_size()
+        k.masks = A.tensor('ohkm_masks').data_ptr()
+        plan.add(R.OP_LOSS_OHKM, k)
+
+    def ohkm_masks(self):
+        """[S][2][B] int32 of the last step: bit j = joint j of (stack, {pose, kd}, sample) was kept -- synchronises."""
+        assert self.ohkm is not None
+        n = len(self.student.g.outputs) * 2 * self.B
+        return self.student.A.tensor('ohkm_masks')[:n].view(-1, 2, self.B).cpu()
 
     # ---- data ----
     def set_batch(self, inp, target, target_weight):

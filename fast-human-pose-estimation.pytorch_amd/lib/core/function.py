@@ -6,8 +6,8 @@ student weights).  Like the reference (function.py:150-155) EVERY iteration feed
 device appends {avg_acc, cnt, pose, kd} of each iteration to a ring (csrc/pck.hip) that is drained -- the only host
 synchronisation of the loop -- when a log line is due (PRINT_FREQ) and at the end of the epoch.
 
-Not silently substituted: the fused step implements Adam (lib.utils.utils.FusedAdam) and JointsMSELoss criteria; any
-other optimizer / criterion object raises instead of being ignored."""
+Not silently substituted: the fused step implements Adam (lib.utils.utils.FusedAdam) and JointsMSELoss /
+JointsOHKMMSELoss criteria; any other optimizer / criterion object raises instead of being ignored."""
 import logging
 import time
 
@@ -17,7 +17,7 @@ from ... import executor as E
 from ... import runtime as R
 from ..utils.utils import FusedAdam
 from .evaluate import accuracy  # noqa: F401  (re-exported like the reference's core.function namespace)
-from .loss import JointsMSELoss
+from .loss import JointsMSELoss, JointsOHKMMSELoss
 
 logger = logging.getLogger(__name__)
 
@@ -41,26 +41,30 @@ def _unwrap(m):
 
 
 def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
-    """The fused step runs ITS Adam and ITS JointsMSELoss: refuse objects it would otherwise silently ignore."""
+    """The fused step runs ITS Adam and ITS JointsMSELoss / JointsOHKMMSELoss: refuse objects it would otherwise silently
+    ignore.  Returns the use_target_weight pair and the topk pair (None for a JointsMSELoss criterion; None instead of the
+    pair when neither criterion mines)."""
     if not isinstance(optimizer, FusedAdam):
         raise R.FpdError('fpd_train: the fused MI355X step implements Adam only (utils.get_optimizer with TRAIN.OPTIMIZER '
                          "'adam' -> FusedAdam); got %s -- its update rule and state would be ignored" % type(optimizer).__name__)
     for name, c in (('pose_criterion', pose_criterion), ('kd_pose_criterion', kd_pose_criterion)):
-        if not isinstance(c, JointsMSELoss):
-            raise R.FpdError('fpd_train: %s must be a core.loss.JointsMSELoss (the fused loss kernel evaluates exactly that '
-                             'criterion), got %s' % (name, type(c).__name__))
-    return bool(pose_criterion.use_target_weight), bool(kd_pose_criterion.use_target_weight)
+        if not isinstance(c, (JointsMSELoss, JointsOHKMMSELoss)):
+            raise R.FpdError('fpd_train: %s must be a core.loss.JointsMSELoss or core.loss.JointsOHKMMSELoss (the fused loss '
+                             'kernels evaluate exactly those criteria), got %s' % (name, type(c).__name__))
+    topk = tuple(int(c.topk) if isinstance(c, JointsOHKMMSELoss) else None for c in (pose_criterion, kd_pose_criterion))
+    return ((bool(pose_criterion.use_target_weight), bool(kd_pose_criterion.use_target_weight)),
+            None if topk == (None, None) else topk)
 
 
-def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True)):
+def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True), ohkm=None):
     """One FusedFPDStep per (student, teacher, batch shape); shares Adam state with the FusedAdam optimizer.
-    tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0."""
+    tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair."""
     s, t = _unwrap(model), (_unwrap(tmodel) if tmodel is not None else None)
     # The cache lives ON the student module (not in a module-level dict keyed by id(): ids are recycled once an object
     # is collected, and a global would keep every plan and its arenas alive for the life of the process).  The teacher
     # and optimizer are compared by identity through the references the entry holds, so they cannot be recycled either.
     cache = s.__dict__.setdefault('_fused_steps', {})
-    key = (tuple(batch_shape), float(alpha), world_size, tuple(use_target_weight))
+    key = (tuple(batch_shape), float(alpha), world_size, tuple(use_target_weight)) + ((tuple(ohkm),) if ohkm is not None else ())
     hit = cache.get(key)
     if hit is not None and hit[0] is t and hit[1] is optimizer:
         return hit[2]
@@ -69,14 +73,15 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     step = E.FusedFPDStep(s.device_state(), s.cfg_hg, t.device_state() if t is not None else None,
                           t.cfg_hg if t is not None else None, n, h, w, alpha,
                           lr=float(optimizer.param_groups[0]['lr']), world_size=world_size,
-                          adam=optimizer, use_target_weight=use_target_weight)
+                          adam=optimizer, use_target_weight=use_target_weight, ohkm=ohkm)
     cache[key] = (t, optimizer, step)
     return step
 
 
-def _run_epoch(config, train_loader, model, tmodel, use_w, optimizer, epoch, writer_dict, allreduce, world_size, alpha):
+def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha):
     """The loop shared by fpd_train (function.py:99-187) and train (function.py:28-96; tmodel None, alpha 0)."""
     kd_mode = tmodel is not None
+    use_w, ohkm = crit
     batch_time, data_time = AverageMeter(), AverageMeter()
     losses, pose_losses, kd_pose_losses, acc = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     model.train()          # function.py:110-111
@@ -104,7 +109,7 @@ def _run_epoch(config, train_loader, model, tmodel, use_w, optimizer, epoch, wri
             if step is not None:                       # batch shape changed (last, smaller batch): finish the old step
                 step.flush()
                 drain()
-            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w)
+            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm)
             metric = step.enable_metric(min_slots=config.PRINT_FREQ + 1)   # PCK + losses of every iteration, logged on the device
             metric.drain()
             n_img = inp.size(0)
@@ -162,16 +167,16 @@ def fpd_train(config, train_loader, model, tmodel, pose_criterion, kd_pose_crite
               output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1):
     """function.py:99-187 (same positional signature; allreduce / world_size are the data-parallel extras).  Returns the
     epoch's average loss (the reference returns None)."""
-    use_w = _check_supported(optimizer, pose_criterion, kd_pose_criterion)
-    return _run_epoch(config, train_loader, model, tmodel, use_w, optimizer, epoch, writer_dict, allreduce, world_size,
+    crit = _check_supported(optimizer, pose_criterion, kd_pose_criterion)
+    return _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
                       float(config.KD.ALPHA))['loss']
 
 
 def train(config, train_loader, model, criterion, optimizer, epoch, output_dir, tb_log_dir, writer_dict,
           allreduce=None, world_size=1):
     """function.py:28-96: plain (non-distillation) training = the same fused step without a teacher graph (alpha 0)."""
-    use_w = _check_supported(optimizer, criterion, criterion)
-    return _run_epoch(config, train_loader, model, None, use_w, optimizer, epoch, writer_dict, allreduce, world_size, 0.0)['loss']
+    crit = _check_supported(optimizer, criterion, criterion)
+    return _run_epoch(config, train_loader, model, None, crit, optimizer, epoch, writer_dict, allreduce, world_size, 0.0)['loss']
 
 
 def _to_numpy(v):

@@ -287,6 +287,21 @@ typedef struct {
                              * differs from the pose criterion's (tools/fpd_train.py:145-147,177-179); NULL = `weight` */
 } fpd_loss_t;
 
+/* JointsOHKMMSELoss (online hard keypoint mining, lib/core/loss.py:42-84) for either term of fpd_loss_t, all stacks, forward and
+ * backward in two launches.  Per criterion call (stack s, term, maps p against r = target / teacher map, weights w):
+ *   L[n,j] = 0.5 w[n,j]^2 / hw * sum_x (p - r)^2 ;  sel(n) = the k joints with the largest L[n,:] ;  loss = 1/(B k) sum_n sum_{j in sel(n)} L[n,j]
+ *   dout_s = grad_scale [(1-alpha) m_pose w^2 (p_s-g) / (B k_pose hw) + alpha m_kd w_kd^2 (p_s-t) / (B k_kd hw)],  m = [j in sel(n)].
+ * torch.topk leaves the order of equal values open; here the LOWER joint index wins among equal L.  k = J keeps every joint:
+ * that term is JointsMSELoss (a mixed pair of criteria = one k below J, the other J).  base.losses keeps {pose, kd} (caller
+ * zeroes); no other buffer needs zeroing, every sum is formed in a fixed order (bit-repeatable).  J <= 32. */
+typedef struct {
+    fpd_loss_t base;
+    int32_t topk_pose, topk_kd;   /* in [1, J]; J = every joint = JointsMSELoss */
+    void* scratch;         /* fpd_loss_ohkm_scratch_bytes(&base) bytes, 8-byte aligned: partial row sums, double [B][chunks][S][2][J] */
+    int64_t scratch_bytes;
+    uint32_t* masks;       /* optional [S][2][B]: bit j = joint j of that (stack, term, sample) was kept */
+} fpd_loss_ohkm_t;
+
 /* torch.optim.Adam(lr) step over one flat fp32 arena (lib/utils/utils.py:69-73), optionally
  * emitting the bf16 working copy of the parameters. */
 typedef struct {
@@ -351,6 +366,9 @@ int fpd_elementwise(const fpd_ew_t* a, fpd_stream_t stream);
 typedef struct { fpd_ew_t a, b; } fpd_ew_pair_t;
 int fpd_elementwise_pair(const fpd_ew_pair_t* p, fpd_stream_t stream);
 int fpd_loss(const fpd_loss_t* a, fpd_stream_t stream);
+int fpd_loss_ohkm(const fpd_loss_ohkm_t* a, fpd_stream_t stream);
+/* bytes of fpd_loss_ohkm_t.scratch for these dimensions (B, J, H, W, S are looked at); negative on bad dimensions */
+int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a);
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream);
 int fpd_weight_prep(const fpd_wprep_entry_t* table_dev, int32_t n_entries, int64_t max_elems, int32_t dtype,
                     fpd_stream_t stream);
@@ -489,7 +507,8 @@ enum {
     FPD_OP_LOSS = 5, FPD_OP_ADAM = 6, FPD_OP_MEMSET = 7, FPD_OP_WPREP = 8, FPD_OP_BNUPD = 9, FPD_OP_WREDUCE = 10,
     FPD_OP_BNECK = 11, FPD_OP_BNECK_FOLD = 12, FPD_OP_CONV_PAIR = 13, FPD_OP_BNECK_PAIR = 14, FPD_OP_EW_PAIR = 15, FPD_OP_PCK = 16, FPD_OP_HEAD = 17,
     FPD_OP_HEAD_FOLD = 18, FPD_OP_NOP = 19, FPD_OP_AFFSUM = 20, FPD_OP_NCHW2NHWC = 21, FPD_OP_CONV_F8 = 22,
-    FPD_OP_WQUANT = 23          /* args: fpd_table_t over fpd_wquant_entry_t */
+    FPD_OP_WQUANT = 23,         /* args: fpd_table_t over fpd_wquant_entry_t */
+    FPD_OP_LOSS_OHKM = 24       /* args: fpd_loss_ohkm_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;

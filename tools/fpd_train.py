@@ -9,7 +9,9 @@ teacher from the cloned config merged with --tcfg, strict teacher-checkpoint loa
 Adam + MultiStepLR, epoch loop -> core.function.fpd_train -> checkpoint.  What differs: one process per GPU with an
 RCCL gradient all-reduce instead of nn.DataParallel; the models run on the HIP path; DATASET.DATASET 'synthetic'
 (the default -- MPII/COCO are not available offline) feeds seeded synthetic crops, and KD.TEACHER 'synthetic' builds a
-random teacher with calibrated BN statistics instead of loading a checkpoint.
+random teacher with calibrated BN statistics instead of loading a checkpoint.  LOSS.USE_OHKM of the student config makes
+the pose criterion a JointsOHKMMSELoss(topk=LOSS.TOPK), LOSS.USE_OHKM of the teacher config the distillation criterion
+(make_criterion below); the reference declares both keys and its tools never read them (its class is never instantiated).
 """
 import argparse
 import logging
@@ -29,7 +31,7 @@ from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import fpd_train, train, validate  # noqa: E402
 from fpd_amd.lib.dataset import SyntheticPose  # noqa: E402
-from fpd_amd.lib.core.loss import JointsMSELoss  # noqa: E402
+from fpd_amd.lib.core.loss import JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
 from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
                                      save_checkpoint)
 
@@ -55,6 +57,14 @@ def get_train_type(train_type, checkpoint):
     if train_type == 'FPD':
         sys.exit('ERROR: teacher checkpoint is not existed.')
     sys.exit('ERROR: please change train type {} to NORMAL or FPD.'.format(train_type))
+
+
+def make_criterion(c):
+    """The criterion config `c` asks for: LOSS.USE_OHKM -> JointsOHKMMSELoss(use_target_weight, topk=LOSS.TOPK), else
+    JointsMSELoss(use_target_weight) (:145-147,177-179).  The reference's tools never instantiate its JointsOHKMMSELoss."""
+    if c.LOSS.USE_OHKM:
+        return JointsOHKMMSELoss(use_target_weight=c.LOSS.USE_TARGET_WEIGHT, topk=c.LOSS.TOPK)
+    return JointsMSELoss(use_target_weight=c.LOSS.USE_TARGET_WEIGHT)
 
 
 def main():
@@ -99,8 +109,12 @@ def main():
         if tmodel is not None:
             fdist.broadcast_state(dist, tmodel.module)
 
-    pose_criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)     # :145-147,177-179
-    kd_pose_criterion = JointsMSELoss(use_target_weight=tcfg.LOSS.USE_TARGET_WEIGHT).to(dev)
+    pose_criterion = make_criterion(cfg).to(dev)                                             # :145-147,177-179
+    kd_pose_criterion = make_criterion(tcfg).to(dev)
+    val_criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)      # the validation loss stays plain MSE
+    if cfg.LOSS.USE_OHKM or tcfg.LOSS.USE_OHKM:
+        logger.info('=> hard keypoint mining: pose criterion %s, distillation criterion %s',
+                    'topk %d' % cfg.LOSS.TOPK if cfg.LOSS.USE_OHKM else 'MSE', 'topk %d' % tcfg.LOSS.TOPK if tcfg.LOSS.USE_OHKM else 'MSE')
 
     if cfg.DATASET.DATASET != 'synthetic':
         sys.exit('dataset %r is not available here (CPU-side MPII/COCO pipeline is out of scope); use DATASET.DATASET synthetic'
@@ -150,8 +164,8 @@ def main():
         # (the two "Test:" blocks in front of epoch 0 in its logs).  Both go through core.function.validate; rank 0 only, like
         # the per-epoch validation below.
         if tmodel is not None:
-            validate(cfg, valid_loader, valid_set, tmodel, pose_criterion, out_dir, cfg.LOG_DIR, writer_dict)
-        validate(cfg, valid_loader, valid_set, model, pose_criterion, out_dir, cfg.LOG_DIR, writer_dict)
+            validate(cfg, valid_loader, valid_set, tmodel, val_criterion, out_dir, cfg.LOG_DIR, writer_dict)
+        validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict)
     if world > 1:
         dist.barrier()
     for epoch in range(begin_epoch, cfg.TRAIN.END_EPOCH):                                     # :252-286
@@ -168,7 +182,7 @@ def main():
                     len(loader) * bs * world / max(time.time() - t0, 1e-9), loss)
         if rank == 0:
             # :266-285: evaluate on the validation set (flip test etc. per cfg.TEST), keep the best model
-            perf_indicator = validate(cfg, valid_loader, valid_set, model, pose_criterion, out_dir, cfg.LOG_DIR, writer_dict)
+            perf_indicator = validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict)
             best_model = perf_indicator >= best_perf
             best_perf = max(best_perf, perf_indicator)
             save_checkpoint({'epoch': epoch + 1, 'model': cfg.MODEL.NAME, 'state_dict': model.state_dict(),
