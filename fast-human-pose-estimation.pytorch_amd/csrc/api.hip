@@ -84,7 +84,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_bn_t); SZ(fpd_conv_t); SZ(fpd_wgrad_t); SZ(fpd_stem_t); SZ(fpd_ew_t); SZ(fpd_loss_t); SZ(fpd_adam_t);
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
-    SZ(fpd_loss_ohkm_t);
+    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t);
 #undef SZ
     return -1;
 }
@@ -493,6 +493,17 @@ int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+int fpd_sgd(const fpd_sgd_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->param && a->grad, "sgd: null pointer");
+    FPD_REQUIRE(a->n >= 0, "sgd: n = %lld is negative", (long long)a->n);
+    FPD_REQUIRE(a->momentum >= 0.f, "sgd: invalid momentum value %g", (double)a->momentum);
+    FPD_REQUIRE(a->weight_decay >= 0.f, "sgd: invalid weight_decay value %g", (double)a->weight_decay);
+    FPD_REQUIRE(a->momentum == 0.f || a->buf, "sgd: momentum %g needs a momentum buffer (buf is null)", (double)a->momentum);
+    FPD_REQUIRE(!a->nesterov || a->momentum != 0.f, "sgd: nesterov momentum requires a momentum (and zero dampening)");
+    int rc = fpd_sgd_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
 int fpd_weight_prep(const fpd_wprep_entry_t* t, int32_t n, int64_t max_elems, int32_t dtype, fpd_stream_t stream) {
     int rc = fpd_weight_prep_launch(t, n, max_elems, dtype, (hipStream_t)stream);
     return rc ? rc : check_launch();
@@ -520,7 +531,7 @@ int fpd_nhwc_to_nchw(const void* src, float* dst, int32_t N, int32_t C, int32_t 
 struct fpd_op {
     int32_t type;
     union {
-        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_adam_t adam;
+        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_adam_t adam; fpd_sgd_t sgd;
         fpd_memset_t mset; fpd_table_t table;
     } u;
 };
@@ -576,6 +587,7 @@ int fpd_plan_add(fpd_plan* p, int32_t op, const void* args, int64_t bytes) {
         case FPD_OP_LOSS: want = sizeof(fpd_loss_t); break;
         case FPD_OP_LOSS_OHKM: want = sizeof(fpd_loss_ohkm_t); break;
         case FPD_OP_ADAM: want = sizeof(fpd_adam_t); break;
+        case FPD_OP_SGD: want = sizeof(fpd_sgd_t); break;
         case FPD_OP_MEMSET: case FPD_OP_NOP: want = sizeof(fpd_memset_t); break;
         case FPD_OP_AFFSUM: want = sizeof(fpd_affsum_t); break;
         case FPD_OP_NCHW2NHWC: want = sizeof(fpd_layout_t); break;
@@ -645,6 +657,7 @@ static void set_op_tag(int idx, const fpd_op& o) {
         case FPD_OP_LOSS: snprintf(t, sizeof(t), "loss B=%d J=%d H=%d W=%d S=%d", o.u.loss.B, o.u.loss.J, o.u.loss.H, o.u.loss.W, o.u.loss.S); break;
         case FPD_OP_LOSS_OHKM: snprintf(t, sizeof(t), "loss_ohkm B=%d J=%d H=%d W=%d S=%d k=%d,%d", o.u.lossk.base.B, o.u.lossk.base.J, o.u.lossk.base.H, o.u.lossk.base.W, o.u.lossk.base.S, o.u.lossk.topk_pose, o.u.lossk.topk_kd); break;
         case FPD_OP_ADAM: snprintf(t, sizeof(t), "adam n=%lld", (long long)o.u.adam.n); break;
+        case FPD_OP_SGD: snprintf(t, sizeof(t), "sgd n=%lld momentum=%g wd=%g%s", (long long)o.u.sgd.n, (double)o.u.sgd.momentum, (double)o.u.sgd.weight_decay, o.u.sgd.nesterov ? " nesterov" : ""); break;
         case FPD_OP_WREDUCE: snprintf(t, sizeof(t), "wreduce entries=%d", o.u.table.n); break;
         case FPD_OP_WPREP: snprintf(t, sizeof(t), "wprep entries=%d", o.u.table.n); break;
         case FPD_OP_BNUPD: snprintf(t, sizeof(t), "bnupd entries=%d", o.u.table.n); break;
@@ -673,6 +686,7 @@ static int run_op(const fpd_op& o, fpd_stream_t s) {
         case FPD_OP_LOSS: return fpd_loss(&o.u.loss, s);
         case FPD_OP_LOSS_OHKM: return fpd_loss_ohkm(&o.u.lossk, s);
         case FPD_OP_ADAM: return fpd_adam(&o.u.adam, s);
+        case FPD_OP_SGD: return fpd_sgd(&o.u.sgd, s);
         case FPD_OP_MEMSET: {
             FPD_CHECK_HIP(hipMemsetAsync(o.u.mset.ptr, 0, (size_t)o.u.mset.bytes, (hipStream_t)s));
             return 0;

@@ -84,6 +84,7 @@ int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
 int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& a, hipStream_t st);      // csrc/loss_ohkm.hip: two launches
 int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a);
 int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st);
+int fpd_sgd_launch(const fpd_sgd_t& a, hipStream_t st);
 int fpd_weight_prep_launch(const fpd_wprep_entry_t* table, int n, int64_t max_elems, int dtype, hipStream_t st);
 int fpd_bn_update_running_launch(const fpd_bnupd_entry_t* table, int n, hipStream_t st);
 int fpd_cast_launch(const void* src, void* dst, int64_t n, int sd, int dd, hipStream_t st);

@@ -647,13 +647,15 @@ class GraphInstance:
 class FusedFPDStep:
     """The fused FPD iteration (lib/core/function.py:119-147 of the reference) on one GPU:
          teacher forward (eval BN) -> student forward (train BN) -> fused pose+KD loss fwd/bwd
-         -> student backward -> [RCCL all-reduce of the flat gradient] -> flat Adam.
+         -> student backward -> [RCCL all-reduce of the flat gradient] -> flat Adam (sgd=: flat SGD instead).
     No host synchronisation inside; losses are read back only when asked for."""
 
     def __init__(self, student_state, student_cfg, teacher_state, teacher_cfg, batch, height, width, alpha,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, world_size=1, adam=None, teacher_chunks=None,
-                 use_target_weight=(True, True), ohkm=None):
+                 use_target_weight=(True, True), ohkm=None, sgd=None):
         dev = student_state.device
+        if adam is not None and sgd is not None:
+            raise R.FpdError('FusedFPDStep: adam= and sgd= are mutually exclusive')
         # JointsMSELoss(use_target_weight) of the pose / distillation criterion (tools/fpd_train.py:145-147,177-179):
         # False = that term ignores the loader's target_weight (loss.py:30-37), i.e. a weight buffer of ones
         self.use_w = (bool(use_target_weight[0]), bool(use_target_weight[1]))
@@ -726,6 +728,10 @@ class FusedFPDStep:
         # optimizer state (torch.optim.Adam semantics, lib/utils/utils.py:69-73)
         n = student_state.table.sizes['param']
         self.n_param = n
+        self._dist_work = None
+        if sgd is not None:         # share the momentum buffer / step / lr with a lib.utils.utils.FusedSGD; no Adam moments
+            self._add_sgd(sgd, student_state, n)
+            return
         if adam is not None:        # share moments / step / lr with a lib.utils.utils.FusedAdam (checkpointable state)
             self.m, self.v, self.lr_dev, self.step_dev = adam.m, adam.v, adam.lr_dev, adam.step_dev
             betas, eps = adam.param_groups[0]['betas'], adam.param_groups[0]['eps']
@@ -749,7 +755,26 @@ class FusedFPDStep:
         b = len(self.student.plan)
         self.student.plan.add(R.OP_ADAM, a)
         self.student.rng['adam'] = (b, len(self.student.plan))
-        self._dist_work = None
+
+    def _add_sgd(self, sgd, student_state, n):
+        """The optimizer range ('adam' by name, so that run / capture / phase timing need not know) = one OP_SGD with the
+        hyperparameters of the FusedSGD's param group as they are NOW (core.function keys its step cache on them)."""
+        g = sgd.param_groups[0]
+        self.m = self.v = None
+        self.buf, self.lr_dev, self.step_dev = sgd.buf, sgd.lr_dev, sgd.step_dev
+        a = R.SgdT()
+        a.n = n
+        pa = student_state.A
+        a.param, a.grad = pa.tensor('param').data_ptr(), pa.tensor('grad').data_ptr()
+        a.buf = self.buf.data_ptr() if self.buf is not None else None
+        a.param_lp = None
+        a.lr, a.momentum, a.weight_decay, a.nesterov = g['lr'], g['momentum'], g['weight_decay'], int(g['nesterov'])
+        a.grad_scale = 1.0        # the loss kernel already folds 1/world_size into the gradient
+        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
+        self._sgd_args = a
+        b = len(self.student.plan)
+        self.student.plan.add(R.OP_SGD, a)
+        self.student.rng['adam'] = (b, len(self.student.plan))
 
     def enable_metric(self, min_slots=0):
         """Per-iteration PCK of the last student map against the target, on the device (lib.core.evaluate.DeviceAccuracy).

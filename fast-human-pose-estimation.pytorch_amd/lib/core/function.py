@@ -6,7 +6,7 @@ student weights).  Like the reference (function.py:150-155) EVERY iteration feed
 device appends {avg_acc, cnt, pose, kd} of each iteration to a ring (csrc/pck.hip) that is drained -- the only host
 synchronisation of the loop -- when a log line is due (PRINT_FREQ) and at the end of the epoch.
 
-Not silently substituted: the fused step implements Adam (lib.utils.utils.FusedAdam) and JointsMSELoss /
+Not silently substituted: the fused step implements Adam and SGD (lib.utils.utils.FusedAdam / FusedSGD) and JointsMSELoss /
 JointsOHKMMSELoss criteria; any other optimizer / criterion object raises instead of being ignored."""
 import logging
 import time
@@ -15,7 +15,7 @@ import torch
 
 from ... import executor as E
 from ... import runtime as R
-from ..utils.utils import FusedAdam
+from ..utils.utils import FusedAdam, FusedSGD
 from .evaluate import accuracy  # noqa: F401  (re-exported like the reference's core.function namespace)
 from .loss import JointsMSELoss, JointsOHKMMSELoss
 
@@ -41,12 +41,13 @@ def _unwrap(m):
 
 
 def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
-    """The fused step runs ITS Adam and ITS JointsMSELoss / JointsOHKMMSELoss: refuse objects it would otherwise silently
-    ignore.  Returns the use_target_weight pair and the topk pair (None for a JointsMSELoss criterion; None instead of the
-    pair when neither criterion mines)."""
-    if not isinstance(optimizer, FusedAdam):
-        raise R.FpdError('fpd_train: the fused MI355X step implements Adam only (utils.get_optimizer with TRAIN.OPTIMIZER '
-                         "'adam' -> FusedAdam); got %s -- its update rule and state would be ignored" % type(optimizer).__name__)
+    """The fused step runs ITS Adam or SGD and ITS JointsMSELoss / JointsOHKMMSELoss: refuse objects it would otherwise
+    silently ignore.  Returns the use_target_weight pair and the topk pair (None for a JointsMSELoss criterion; None instead
+    of the pair when neither criterion mines)."""
+    if not isinstance(optimizer, (FusedAdam, FusedSGD)):
+        raise R.FpdError('fpd_train: the fused MI355X step implements Adam and SGD only (utils.get_optimizer with '
+                         "TRAIN.OPTIMIZER 'adam' -> FusedAdam, 'sgd' -> FusedSGD); got %s -- its update rule and state "
+                         'would be ignored' % type(optimizer).__name__)
     for name, c in (('pose_criterion', pose_criterion), ('kd_pose_criterion', kd_pose_criterion)):
         if not isinstance(c, (JointsMSELoss, JointsOHKMMSELoss)):
             raise R.FpdError('fpd_train: %s must be a core.loss.JointsMSELoss or core.loss.JointsOHKMMSELoss (the fused loss '
@@ -57,14 +58,19 @@ def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
 
 
 def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True), ohkm=None):
-    """One FusedFPDStep per (student, teacher, batch shape); shares Adam state with the FusedAdam optimizer.
-    tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair."""
+    """One FusedFPDStep per (student, teacher, batch shape); shares the optimizer state with the FusedAdam / FusedSGD object.
+    tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair.
+    A FusedSGD's (momentum, weight_decay, nesterov) live in the recorded plan op, so they are part of the key."""
     s, t = _unwrap(model), (_unwrap(tmodel) if tmodel is not None else None)
     # The cache lives ON the student module (not in a module-level dict keyed by id(): ids are recycled once an object
     # is collected, and a global would keep every plan and its arenas alive for the life of the process).  The teacher
     # and optimizer are compared by identity through the references the entry holds, so they cannot be recycled either.
     cache = s.__dict__.setdefault('_fused_steps', {})
     key = (tuple(batch_shape), float(alpha), world_size, tuple(use_target_weight)) + ((tuple(ohkm),) if ohkm is not None else ())
+    is_sgd = isinstance(optimizer, FusedSGD)
+    if is_sgd:
+        g = optimizer.param_groups[0]
+        key += (('sgd', float(g['momentum']), float(g['weight_decay']), bool(g['nesterov'])),)
     hit = cache.get(key)
     if hit is not None and hit[0] is t and hit[1] is optimizer:
         return hit[2]
@@ -73,7 +79,7 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     step = E.FusedFPDStep(s.device_state(), s.cfg_hg, t.device_state() if t is not None else None,
                           t.cfg_hg if t is not None else None, n, h, w, alpha,
                           lr=float(optimizer.param_groups[0]['lr']), world_size=world_size,
-                          adam=optimizer, use_target_weight=use_target_weight, ohkm=ohkm)
+                          use_target_weight=use_target_weight, ohkm=ohkm, **{'sgd' if is_sgd else 'adam': optimizer})
     cache[key] = (t, optimizer, step)
     return step
 

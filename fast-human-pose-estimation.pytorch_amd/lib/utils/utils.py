@@ -6,27 +6,51 @@ import torch
 from ... import runtime as R
 
 
-class FusedAdam(torch.optim.Optimizer):
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FusedAdam and FusedSGD share: one param group over the model's flat arenas, the device lr / step scalars the
+    kernels read, and the per-parameter views of a flat state arena in the reference's shapes."""
+
+    def _init_flat(self, model, defaults):
+        self.model = model.module if hasattr(model, 'module') else model
+        super().__init__(list(self.model.parameters()), defaults)
+        flat = self.model._flat['param']         # the flat fp32 arena every parameter is a view of (create the optimizer
+        lr = defaults['lr']                      # AFTER .to(device), like any torch optimizer)
+        self.lr_dev = torch.full((1,), lr, dtype=torch.float32, device=flat.device)
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=flat.device)
+        self._lr_host = lr
+        return flat
+
+    def sync_lr(self):
+        """param_groups[0]['lr'] (what LR schedules write) -> the device scalar the optimizer kernel reads."""
+        lr = float(self.param_groups[0]['lr'])
+        if lr != self._lr_host:
+            self.lr_dev.fill_(lr)
+            self._lr_host = lr
+
+    def zero_grad(self, set_to_none=True):
+        st = self.model.device_state()
+        st.A.tensor('grad').zero_()
+
+    def _views(self, flat):
+        """Per trainable tensor, the slice of a flat arena in the reference's shape (OIHW for conv weights)."""
+        m = self.model
+        out = []
+        for key in m.table.trainable_keys():
+            b = m.table[key]
+            v = flat[b.off:b.off + b.numel].view(b.shape)
+            out.append(v.permute(0, 3, 1, 2) if len(b.shape) == 4 else v)
+        return out
+
+
+class FusedAdam(_FlatOptimizer):
     """torch.optim.Adam(lr) semantics (utils.py:69-73: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad) as ONE
     HIP launch over the model's flat parameter / gradient arenas instead of 752 per-tensor launches.  lr is read from
     param_groups[0]['lr'] at every step, so torch LR schedulers (MultiStepLR, tools/fpd_train.py:236-239) work."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        self.model = model.module if hasattr(model, 'module') else model
-        super().__init__(list(self.model.parameters()), dict(lr=lr, betas=betas, eps=eps))
-        flat = self.model._flat['param']         # the flat fp32 arena every parameter is a view of (create the optimizer
-        self.m = torch.zeros_like(flat)          # AFTER .to(device), like any torch optimizer)
+        flat = self._init_flat(model, dict(lr=lr, betas=betas, eps=eps))
+        self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
-        self.lr_dev = torch.full((1,), lr, dtype=torch.float32, device=flat.device)
-        self.step_dev = torch.zeros(1, dtype=torch.int64, device=flat.device)
-        self._lr_host = lr
-
-    def sync_lr(self):
-        """param_groups[0]['lr'] (what LR schedules write) -> the device scalar the Adam kernel reads."""
-        lr = float(self.param_groups[0]['lr'])
-        if lr != self._lr_host:
-            self.lr_dev.fill_(lr)
-            self._lr_host = lr
 
     def adam_args(self):
         st = self.model.device_state()
@@ -46,22 +70,9 @@ class FusedAdam(torch.optim.Optimizer):
         self.sync_lr()
         R.check(R.lib().fpd_adam(self.adam_args(), R.current_stream()), 'fpd_adam')
 
-    def zero_grad(self, set_to_none=True):
-        st = self.model.device_state()
-        st.A.tensor('grad').zero_()
-
     # ---- checkpoint interop: the state dict has torch.optim.Adam's layout (per-parameter exp_avg / exp_avg_sq in the
     #      reference's OIHW shapes), so `checkpoint['optimizer']` written here loads into the reference's Adam and a
     #      reference checkpoint resumes here (tools/fpd_train.py:224-234, AUTO_RESUME) ----
-    def _views(self, flat):
-        m = self.model
-        out = []
-        for key in m.table.trainable_keys():
-            b = m.table[key]
-            v = flat[b.off:b.off + b.numel].view(b.shape)
-            out.append(v.permute(0, 3, 1, 2) if len(b.shape) == 4 else v)
-        return out
-
     def state_dict(self):
         step = self.step_dev.to(torch.float32).reshape(())
         state = {}
@@ -102,6 +113,86 @@ class FusedAdam(torch.optim.Optimizer):
         self.sync_lr()
 
 
+class FusedSGD(_FlatOptimizer):
+    """torch.optim.SGD(lr, momentum, dampening 0, weight_decay, nesterov) semantics (utils.py:61-67) as ONE HIP launch
+    (csrc/loss_adam.hip sgd_kernel) over the flat parameter / gradient arenas.  The decay covers every parameter, BN
+    gamma / beta included: the reference hands model.parameters() over as one group.  lr is read from
+    param_groups[0]['lr'] at every step like FusedAdam's."""
+
+    def __init__(self, model, lr=1e-3, momentum=0, weight_decay=0, nesterov=False):
+        if lr < 0.0:
+            raise ValueError('Invalid learning rate: %r' % (lr,))
+        if momentum < 0.0:
+            raise ValueError('Invalid momentum value: %r' % (momentum,))
+        if weight_decay < 0.0:
+            raise ValueError('Invalid weight_decay value: %r' % (weight_decay,))
+        if nesterov and momentum <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        flat = self._init_flat(model, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay,
+                                           nesterov=bool(nesterov), maximize=False, foreach=None, differentiable=False,
+                                           fused=None))
+        self.buf = torch.zeros_like(flat) if momentum != 0 else None
+        self._resumed = False                    # a loaded state carries buffers but no step count
+
+    def sgd_args(self):
+        st = self.model.device_state()
+        g = self.param_groups[0]
+        a = R.SgdT()
+        a.n = st.table.sizes['param']
+        a.param, a.grad = st.A.tensor('param').data_ptr(), st.A.tensor('grad').data_ptr()
+        a.buf, a.param_lp = (self.buf.data_ptr() if self.buf is not None else None), None
+        a.lr, a.momentum, a.weight_decay, a.nesterov = g['lr'], g['momentum'], g['weight_decay'], int(g['nesterov'])
+        a.grad_scale = 1.0
+        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
+        return a
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        self.sync_lr()
+        R.check(R.lib().fpd_sgd(self.sgd_args(), R.current_stream()), 'fpd_sgd')
+
+    # ---- checkpoint interop: torch.optim.SGD's layout (one momentum_buffer per parameter in the reference's OIHW shapes,
+    #      no step count), so the reference's SGD loads what is written here and a reference checkpoint resumes here ----
+    def state_dict(self):
+        state = {}
+        if self.buf is not None and (self._resumed or int(self.step_dev.item()) > 0):
+            for i, b in enumerate(self._views(self.buf)):
+                state[i] = {'momentum_buffer': b.clone()}
+        g = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
+        g['params'] = list(range(len(self.param_groups[0]['params'])))
+        return {'state': state, 'param_groups': [g]}
+
+    def load_state_dict(self, sd):
+        g = sd['param_groups'][0]
+        if g.get('dampening', 0) != 0 or g.get('maximize', False):
+            raise ValueError('FusedSGD implements dampening 0 and maximize False; the state has dampening %r, maximize %r'
+                             % (g.get('dampening', 0), g.get('maximize', False)))
+        momentum, nesterov = g.get('momentum', self.param_groups[0]['momentum']), g.get('nesterov', self.param_groups[0]['nesterov'])
+        if nesterov and momentum <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        st = sd.get('state', {})
+        n = len(self.param_groups[0]['params'])
+        if len(st) not in (0, n):
+            raise ValueError('optimizer state has %d parameter entries, the model has %d' % (len(st), n))
+        if momentum != 0 and self.buf is None:
+            self.buf = torch.zeros_like(self.model._flat['param'])
+        self.step_dev.zero_()
+        self._resumed = False
+        if self.buf is not None:
+            self.buf.zero_()
+            for dst, pid in zip(self._views(self.buf), g['params']):
+                b = (st.get(pid) or {}).get('momentum_buffer')
+                if b is not None:                # None: what torch keeps before a parameter's first step = a zero buffer
+                    dst.copy_(b)
+                    self._resumed = True
+        for k in ('lr', 'momentum', 'weight_decay', 'nesterov', 'initial_lr'):   # initial_lr: what torch's LR schedulers resume from
+            if k in g:
+                self.param_groups[0][k] = g[k]
+        self.param_groups[0].setdefault('initial_lr', self.param_groups[0]['lr'])
+        self._lr_host = None
+        self.sync_lr()
+
+
 def multistep_lr(base_lr, milestones, gamma, epoch):
     """Learning rate the reference trains epoch `epoch` with (tools/fpd_train.py:236-239,253: MultiStepLR built with
     last_epoch = -1 and stepped at the START of every epoch, so epoch e runs at the scheduler's value for e + 1, i.e.
@@ -117,9 +208,8 @@ def get_optimizer(cfg, model):
     if cfg.TRAIN.OPTIMIZER == 'adam':
         return FusedAdam(model, lr=cfg.TRAIN.LR)
     if cfg.TRAIN.OPTIMIZER == 'sgd':
-        # usable through the module API (autograd + .grad views); core.function.fpd_train refuses it (fused Adam only)
-        return torch.optim.SGD(model.parameters(), lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM,
-                               weight_decay=cfg.TRAIN.WD, nesterov=cfg.TRAIN.NESTEROV)
+        return FusedSGD(model, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM, weight_decay=cfg.TRAIN.WD,
+                        nesterov=cfg.TRAIN.NESTEROV)
     raise ValueError('unknown optimizer %r' % cfg.TRAIN.OPTIMIZER)
 
 

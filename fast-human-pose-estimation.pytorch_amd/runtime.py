@@ -17,7 +17,7 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
  EW_ADD, EW_RELU_MASK, EW_DILATE2) = range(10)
 (OP_CONV, OP_WGRAD, OP_STEM_FWD, OP_STEM_WGRAD, OP_EW, OP_LOSS, OP_ADAM, OP_MEMSET, OP_WPREP, OP_BNUPD,
  OP_WREDUCE, OP_BNECK, OP_BNECK_FOLD, OP_CONV_PAIR, OP_BNECK_PAIR, OP_EW_PAIR, OP_PCK, OP_HEAD, OP_HEAD_FOLD,
- OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM) = range(25)
+ OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD) = range(26)
 AFFSUM_MAX = 4
 MAX_STACKS = 8
 MAXC = 512
@@ -150,6 +150,12 @@ class AdamT(C.Structure):
                 ('bias_corr2', _f32), ('grad_scale', _f32), ('_pad', _i32), ('lr_dev', _vp), ('step_dev', _vp)]
 
 
+class SgdT(C.Structure):
+    _fields_ = [('n', _i64), ('param', _vp), ('grad', _vp), ('buf', _vp), ('param_lp', _vp), ('lr', _f32),
+                ('momentum', _f32), ('weight_decay', _f32), ('grad_scale', _f32), ('nesterov', _i32), ('_pad', _i32),
+                ('lr_dev', _vp), ('step_dev', _vp)]
+
+
 class WprepEntryT(C.Structure):
     _fields_ = [('w', _vp), ('w_fwd', _vp), ('w_bwd', _vp), ('K', _i32), ('R', _i32), ('S', _i32), ('C', _i32)]
 
@@ -176,7 +182,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_bnupd_entry_t': BnupdEntryT, 'fpd_memset_t': MemsetT, 'fpd_table_t': TableT,
             'fpd_wreduce_entry_t': WreduceEntryT, 'fpd_bneck_t': BneckT, 'fpd_conv_pair_t': ConvPairT, 'fpd_bneck_pair_t': BneckPairT, 'fpd_ew_pair_t': EwPairT, 'fpd_pck_t': PckT, 'fpd_head_t': HeadT, 'fpd_affsum_t': AffsumT, 'fpd_layout_t': LayoutT,
             'fpd_conv_f8_t': ConvF8T, 'fpd_wquant_entry_t': WquantEntryT, 'fpd_flipmerge_t': FlipMergeT, 'fpd_finalpreds_t': FinalPredsT, 'fpd_targets_t': TargetsT,
-            'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT}
+            'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -215,6 +221,7 @@ SYMBOLS = {
     'fpd_loss_ohkm': (C.c_int, [C.POINTER(LossOhkmT), _vp]),
     'fpd_loss_ohkm_scratch_bytes': (C.c_int64, [C.POINTER(LossT)]),
     'fpd_adam': (C.c_int, [C.POINTER(AdamT), _vp]),
+    'fpd_sgd': (C.c_int, [C.POINTER(SgdT), _vp]),
     'fpd_weight_prep': (C.c_int, [_vp, _i32, _i64, _i32, _vp]),
     'fpd_bn_update_running': (C.c_int, [_vp, _i32, _vp]),
     'fpd_cast': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),

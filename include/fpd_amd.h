@@ -316,6 +316,24 @@ typedef struct {
     int64_t* step_dev;     /* optional: device step counter t (bias corrections use t+1; incremented after) */
 } fpd_adam_t;
 
+/* torch.optim.SGD(lr, momentum, dampening = 0, weight_decay, nesterov, maximize = False) step over one flat fp32 arena
+ * (lib/utils/utils.py:61-67), one launch:
+ *   g = grad * grad_scale [+ weight_decay * param];  momentum != 0: buf = momentum * buf + g, g = nesterov ? g + momentum * buf : buf;
+ *   param -= lr * g.
+ * `buf` starts at zero (= torch's "first step copies the gradient" under dampening 0); momentum == 0 touches no buffer and
+ * buf may be NULL.  The decay covers the whole arena (BN gamma / beta included: the reference passes one parameter group). */
+typedef struct {
+    int64_t n;
+    float* param; const float* grad; float* buf;
+    void* param_lp;        /* optional bf16 copy [n], round to nearest even */
+    float lr, momentum, weight_decay;
+    float grad_scale;      /* multiply grads first (1/world_size) */
+    int32_t nesterov;
+    int32_t _pad;
+    const float* lr_dev;   /* optional: read lr from device memory (graph-replay safe) */
+    int64_t* step_dev;     /* optional: device step counter, incremented once per step */
+} fpd_sgd_t;
+
 /* Per-conv working copies of the weights: cast to `dtype` in K,R,S,C order (forward operand)
  * and the flipped, IO-swapped C,R,S,K copy (data-gradient operand).  One launch for a table. */
 typedef struct {
@@ -370,6 +388,8 @@ int fpd_loss_ohkm(const fpd_loss_ohkm_t* a, fpd_stream_t stream);
 /* bytes of fpd_loss_ohkm_t.scratch for these dimensions (B, J, H, W, S are looked at); negative on bad dimensions */
 int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a);
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream);
+/* refuses (before any launch) null param / grad, n < 0, momentum < 0, weight_decay < 0, momentum != 0 without buf, nesterov without momentum */
+int fpd_sgd(const fpd_sgd_t* a, fpd_stream_t stream);
 int fpd_weight_prep(const fpd_wprep_entry_t* table_dev, int32_t n_entries, int64_t max_elems, int32_t dtype,
                     fpd_stream_t stream);
 int fpd_bn_update_running(const fpd_bnupd_entry_t* table_dev, int32_t n_entries, fpd_stream_t stream);
@@ -508,7 +528,8 @@ enum {
     FPD_OP_BNECK = 11, FPD_OP_BNECK_FOLD = 12, FPD_OP_CONV_PAIR = 13, FPD_OP_BNECK_PAIR = 14, FPD_OP_EW_PAIR = 15, FPD_OP_PCK = 16, FPD_OP_HEAD = 17,
     FPD_OP_HEAD_FOLD = 18, FPD_OP_NOP = 19, FPD_OP_AFFSUM = 20, FPD_OP_NCHW2NHWC = 21, FPD_OP_CONV_F8 = 22,
     FPD_OP_WQUANT = 23,         /* args: fpd_table_t over fpd_wquant_entry_t */
-    FPD_OP_LOSS_OHKM = 24       /* args: fpd_loss_ohkm_t */
+    FPD_OP_LOSS_OHKM = 24,      /* args: fpd_loss_ohkm_t */
+    FPD_OP_SGD = 25             /* args: fpd_sgd_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;

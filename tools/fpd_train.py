@@ -36,10 +36,11 @@ from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_chec
                                      save_checkpoint)
 
 
-def parse_args():
-    p = argparse.ArgumentParser(description='Train keypoints network (FPD)')
-    p.add_argument('--cfg', help='student experiment configure file name', required=True, type=str)
-    p.add_argument('--tcfg', help='teacher experiment configure file name', default='', type=str)
+def parse_args(description='Train keypoints network (FPD)', with_teacher=True):
+    p = argparse.ArgumentParser(description=description)
+    p.add_argument('--cfg', help='%sexperiment configure file name' % ('student ' if with_teacher else ''), required=True, type=str)
+    if with_teacher:
+        p.add_argument('--tcfg', help='teacher experiment configure file name', default='', type=str)
     p.add_argument('opts', help='Modify config options using the command-line', default=None, nargs=argparse.REMAINDER)
     p.add_argument('--modelDir', default='', type=str)
     p.add_argument('--logDir', default='', type=str)
@@ -67,8 +68,9 @@ def make_criterion(c):
     return JointsMSELoss(use_target_weight=c.LOSS.USE_TARGET_WEIGHT)
 
 
-def main():
-    args = parse_args()
+def run(args, normal=False):
+    """The training run both entry points share.  normal: tools/train.py -- plain training whatever KD.TRAIN_TYPE says, no
+    teacher config (`args` has no tcfg)."""
     update_config(cfg, args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -82,7 +84,7 @@ def main():
         import torch.distributed as dist
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('nccl', rank=rank, world_size=world, device_id=dev)
-    train_type = get_train_type(cfg.KD.TRAIN_TYPE, cfg.KD.TEACHER)
+    train_type = 'NORMAL' if normal else get_train_type(cfg.KD.TRAIN_TYPE, cfg.KD.TEACHER)
     out_dir = os.path.join(cfg.OUTPUT_DIR, cfg.DATASET.DATASET, cfg.MODEL.NAME,
                            os.path.basename(args.cfg).split('.')[0])
     os.makedirs(out_dir, exist_ok=True)
@@ -90,7 +92,7 @@ def main():
     torch.manual_seed(1)
     model = eval('models.' + cfg.MODEL.NAME + '.get_pose_net')(cfg, is_train=True)          # :122-124
     tcfg = cfg.clone()                                                                        # :128-131
-    if args.tcfg:
+    if getattr(args, 'tcfg', ''):
         tcfg.merge_from_file(args.tcfg)
     if rank == 0:                                                                             # :162-167 (shape-only walk)
         logger.info(get_model_summary(model, torch.empty(1, 3, cfg.MODEL.IMAGE_SIZE[1], cfg.MODEL.IMAGE_SIZE[0], device='meta')))
@@ -195,6 +197,10 @@ def main():
         torch.save(model.module.state_dict(), os.path.join(out_dir, 'final_state.pth'))      # :288-294
     if world > 1:
         dist.destroy_process_group()
+
+
+def main():
+    run(parse_args())
 
 
 if __name__ == '__main__':
