@@ -52,6 +52,10 @@ static int validate_conv_dims(int N, int H, int W, int C, int K, int R, int S, i
     return 0;
 }
 
+// grid caps of the persistent teacher kernels (bneck_fused.hip, head_fused.hip); return the previous value
+int fpd_bneck_blocks_option(int value);
+int fpd_head_blocks_option(int value);
+
 extern "C" {
 
 const char* fpd_last_error(void) { return g_err; }
@@ -75,6 +79,8 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c3")) return fpd_conv_c3_option(0, value);
     if (!strcmp(name, "conv_c3_blocks")) return fpd_conv_c3_option(1, value);
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);
+    if (!strcmp(name, "bneck_blocks")) return fpd_bneck_blocks_option(value);
+    if (!strcmp(name, "head_blocks")) return fpd_head_blocks_option(value);
     if (!strcmp(name, "wgrad_tile_only")) { g_wgrad_tile_only = value; return 0; }
     return fpd_fail(-2, "set_option: unknown option '%s'", name);
 }

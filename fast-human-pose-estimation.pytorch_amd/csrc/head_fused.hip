@@ -9,6 +9,7 @@
 // double-buffered in LDS with two register sets in flight, persistent capped grid, wave-private staged epilogue.
 // Domain: bf16, C = 256, J = 16 (K of score_ = one MFMA k-step).  Specification: oracle/plan_interp.py run_head.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -320,17 +321,26 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
 template <int C>
 __global__ void head_fold_kernel(const fpd_head_t a, float* out) { head_tables<C>(a, out, threadIdx.x, blockDim.x); }
 
+static std::atomic<int> g_head_cap{0};        // 0 = not set yet: the environment supplies the default
 static int head_block_cap() {
-    static int cap = 0;
+    int cap = g_head_cap.load(std::memory_order_relaxed);
     if (!cap) {
         const char* e = getenv("FPD_HEAD_BLOCKS");
         cap = e ? atoi(e) : 160;                 // same argument as the fused Bottleneck: leave CUs to the student chain
         if (cap < 8) cap = 8;
+        int unset = 0;                           // (a value set through fpd_set_option in the meantime wins)
+        if (!g_head_cap.compare_exchange_strong(unset, cap, std::memory_order_relaxed)) cap = unset;
     }
     return cap;
 }
 
 }  // namespace
+
+// fpd_set_option("head_blocks", n): the grid cap, any n >= 1 (tests); returns the previous value
+int fpd_head_blocks_option(int value) {
+    head_block_cap();                           // (the default is in place: what the exchange returns is the value in force)
+    return g_head_cap.exchange(value < 1 ? 1 : value, std::memory_order_relaxed);
+}
 
 static bool head_in_domain(const fpd_head_t& a) {
     return a.dtype == FPD_BF16 && a.C == 256 && a.J == 16;

@@ -181,6 +181,12 @@ def test_host_side_dispatch_predicates_of_round_3_without_a_device(runtime):
     assert lib.fpd_set_option(b'no_such_option', 1) < 0 and b'unknown' in lib.fpd_last_error()
     prev = lib.fpd_set_option(b'conv_pp_blocks', 64)
     assert prev == 256 and lib.fpd_set_option(b'conv_pp_blocks', prev) == 64
+    # grid caps of the persistent teacher kernels: the default comes from the environment (clamped to >= 8), any n >= 1 is honoured
+    for name, env, default in ((b'bneck_blocks', 'FPD_BNECK_BLOCKS', 128), (b'head_blocks', 'FPD_HEAD_BLOCKS', 160)):
+        default = max(8, int(os.environ[env])) if os.environ.get(env) else default
+        prev = lib.fpd_set_option(name, 1)
+        assert prev == default and lib.fpd_set_option(name, 3) == 1 and lib.fpd_set_option(name, prev) == 3
+        assert lib.fpd_set_option(name, prev) == default
 
 
 def test_exact_statistics_encoding_round_trip_and_order_independence():

@@ -100,6 +100,14 @@ class Bench:
                 self.n_c1 = R.set_option('conv_c1_launches', 0) - n0
                 R.set_option('conv_c1', cm)
                 R.set_option('conv_c1_blocks', cb)
+        if isinstance(backend, tuple) and backend[0] in ('bneck', 'head'):
+            # ('bneck', n) / ('head', n): grid cap of the persistent fused Bottleneck / head kernel (csrc/bneck_fused.hip,
+            # csrc/head_fused.hip), so that a block walks several tiles even on small tensors
+            prev = R.set_option(backend[0] + '_blocks', backend[1])
+            try:
+                return self.run(ops, 0, partials)
+            finally:
+                R.set_option(backend[0] + '_blocks', prev)
         if partials:                         # slab reduction of all weight gradients of the list (one gradient bucket)
             wg = [o for o in ops if o.kind == 'wgrad']
             ops = list(ops) + [G.Op('wreduce', bucket=0, wgrads=wg, bufs=[x for w in wg for x in (w.dw, w.dbias) if x is not None])]
