@@ -76,6 +76,8 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c1")) return fpd_conv_c1_option(0, value);
     if (!strcmp(name, "conv_c1_blocks")) return fpd_conv_c1_option(1, value);
     if (!strcmp(name, "conv_c1_launches")) return fpd_conv_c1_option(2, value);      // (read-only: launches served so far)
+    if (!strcmp(name, "conv_skip")) return fpd_conv_c1_option(3, value);             // second 1x1 source (fpd_conv_t.x2) offered at all
+    if (!strcmp(name, "stem_act")) return fpd_stem_s2d_option(0, value);             // eval-mode BN + ReLU in the stem's epilogue (fpd_stem_t.act)
     if (!strcmp(name, "conv_c3")) return fpd_conv_c3_option(0, value);
     if (!strcmp(name, "conv_c3_blocks")) return fpd_conv_c3_option(1, value);
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);
@@ -105,6 +107,8 @@ static int validate_conv(const fpd_conv_t* a) {
     FPD_REQUIRE(a->bn.mode != FPD_BN_EVAL || (a->bn.running_mean && a->bn.running_var), "conv: eval-mode BN without running stats");
     FPD_REQUIRE(a->epi == FPD_EPI_PLAIN || (a->epi_x && a->epi_stats && a->epi_bn.mode == FPD_BN_TRAIN && a->epi_bn.stats),
                 "conv: BNRELU_BWD epilogue needs epi_x, epi_stats and a train-mode epi_bn");
+    FPD_REQUIRE(a->x2 == nullptr || (a->w2 != nullptr && a->C2 > 0), "conv: a second source (x2) needs w2 and C2");
+    FPD_REQUIRE(a->x2 == nullptr || a->residual == nullptr, "conv: a second source (x2) and a residual exclude each other");
     return 0;
 }
 
@@ -130,7 +134,7 @@ static bool eligible(unsigned backends) { return (backends >> g_fpd_backend & 1u
 // The backend that serves the launch (b != nullptr: the pair launch) carrying `ask`, and what it offers there.  The walk ends at
 // the first generic backend: whichever of them launches, it offers nothing.  nullptr: a pair that no kernel pairs.
 static const ConvBackend* route_conv(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
-    r = ConvRoute{false, 0, 0};
+    r = ConvRoute{false, 0, 0, false};
     for (const ConvBackend& e : g_conv_backends) {
         if (!eligible(e.backends)) continue;
         if (e.route == nullptr ? b == nullptr : e.route(a, b, ask, r) == 0) return &e;
@@ -152,6 +156,8 @@ static int launch_conv(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st)
     FPD_REQUIRE(r.folds || (a.fold_x == nullptr && (b == nullptr || b->fold_x == nullptr)),
                 "conv: the launch asks for a folded BN-backward apply (fold_x), which its route (%s) does not offer; %s() reports 0 for it",
                 e->name, b ? "fpd_conv_pair_fold_supported" : "fpd_conv_fold_supported");
+    FPD_REQUIRE(r.skips || (a.x2 == nullptr && (b == nullptr || b->x2 == nullptr)),
+                "conv: the launch carries a second 1x1 source (x2), which its route (%s) does not offer; fpd_conv_skip_supported() reports 0 for it", e->name);
     int rc = e->launch(a, b, st);
     for (++e; rc == 1 && e != std::end(g_conv_backends); ++e)      // a generic kernel declines inside its launch: on to the next one
         if (e->route == nullptr && eligible(e->backends)) rc = e->launch(a, b, st);
@@ -169,20 +175,28 @@ int fpd_conv_forward(const fpd_conv_t* a, fpd_stream_t stream) {
 int fpd_conv_fold_supported(const fpd_conv_t* a) {
     ConvRoute r;
     if (!a || validate_conv(a) != 0) return 0;
-    route_conv(*a, nullptr, ConvAsk{true, a->wg_partial != nullptr}, r);
+    route_conv(*a, nullptr, ConvAsk{true, a->wg_partial != nullptr, a->x2 != nullptr}, r);
     return r.folds ? 1 : 0;
 }
 int fpd_conv_pair_fold_supported(const fpd_conv_pair_t* p) {
     ConvRoute r;
     if (!p || validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
-    if (route_conv(p->a, &p->b, ConvAsk{true, fpd_conv_ask(p->a, &p->b).wg}, r) != nullptr) return r.folds ? 1 : 0;
+    if (route_conv(p->a, &p->b, ConvAsk{true, fpd_conv_ask(p->a, &p->b).wg, fpd_conv_ask(p->a, &p->b).skip}, r) != nullptr) return r.folds ? 1 : 0;
     return (fpd_conv_fold_supported(&p->a) && fpd_conv_fold_supported(&p->b)) ? 1 : 0;      // two single launches
+}
+
+// (the second source is read from the fields: x2, w2, bias2, C2 as they will be launched)
+int fpd_conv_skip_supported(const fpd_conv_t* a) {
+    ConvRoute r;
+    if (!a || validate_conv(a) != 0) return 0;
+    route_conv(*a, nullptr, ConvAsk{a->fold_x != nullptr, a->wg_partial != nullptr, true}, r);
+    return r.skips ? 1 : 0;
 }
 
 int fpd_conv_fused_wgrad_partials(const fpd_conv_t* a) {
     ConvRoute r;
     if (!a || validate_conv(a) != 0) return 0;
-    route_conv(*a, nullptr, ConvAsk{a->fold_x != nullptr, true}, r);
+    route_conv(*a, nullptr, ConvAsk{a->fold_x != nullptr, true, a->x2 != nullptr}, r);
     return r.slabs_a;
 }
 int fpd_conv_pair_fused_wgrad_partials(const fpd_conv_pair_t* p, int32_t* n_a, int32_t* n_b) {
@@ -190,7 +204,7 @@ int fpd_conv_pair_fused_wgrad_partials(const fpd_conv_pair_t* p, int32_t* n_a, i
     *n_a = *n_b = 0;
     if (validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
     ConvRoute r;
-    route_conv(p->a, &p->b, ConvAsk{fpd_conv_ask(p->a, &p->b).fold, true}, r);      // (a pair that nothing pairs: two launches without the fusion)
+    route_conv(p->a, &p->b, ConvAsk{fpd_conv_ask(p->a, &p->b).fold, true, fpd_conv_ask(p->a, &p->b).skip}, r);      // (a pair that nothing pairs: two launches without the fusion)
     *n_a = r.slabs_a; *n_b = r.slabs_b;
     return 0;
 }
@@ -221,6 +235,7 @@ int fpd_conv_forward_pair(const fpd_conv_pair_t* p, fpd_stream_t stream) {
     if (rc) return rc;
     rc = validate_conv(&p->b);
     if (rc) return rc;
+    FPD_REQUIRE(p->a.x2 == nullptr && p->b.x2 == nullptr, "conv_pair: a pair launch takes no second source (x2)");
     rc = launch_conv(p->a, &p->b, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
@@ -313,14 +328,15 @@ int fpd_wgrad_num_partials(const fpd_wgrad_t* a) {
 // ---- stem backends, in dispatch order (forward and weight gradient) ----
 struct StemBackend {
     unsigned backends;
+    bool (*takes_act)(const fpd_stem_t& a);      // the forward launch applies fpd_stem_t.act in its epilogue (nullptr: it never does)
     int (*forward)(const fpd_stem_t& a, hipStream_t st);
     int (*wgrad_partials)(const fpd_stem_t& a);
     int (*wgrad)(const fpd_stem_t& a, hipStream_t st);
 };
 static const StemBackend g_stem_backends[] = {
-    {ON_MFMA, fpd_stem_forward_s2d_launch, fpd_stem_wgrad_s2d_partials, fpd_stem_wgrad_s2d_launch},      // space-to-depth 4x4 form (round 5)
-    {ON_MFMA, fpd_stem_forward_mfma_launch, fpd_stem_wgrad_mfma_partials, fpd_stem_wgrad_mfma_launch},
-    {ON_ANY, fpd_stem_forward_launch, fpd_stem_wgrad_partials, fpd_stem_wgrad_launch},
+    {ON_MFMA, fpd_stem_forward_s2d_takes_act, fpd_stem_forward_s2d_launch, fpd_stem_wgrad_s2d_partials, fpd_stem_wgrad_s2d_launch},      // space-to-depth 4x4 form (round 5)
+    {ON_MFMA, nullptr, fpd_stem_forward_mfma_launch, fpd_stem_wgrad_mfma_partials, fpd_stem_wgrad_mfma_launch},
+    {ON_ANY, nullptr, fpd_stem_forward_launch, fpd_stem_wgrad_partials, fpd_stem_wgrad_launch},
 };
 
 int fpd_stem_wgrad_num_partials(const fpd_stem_t* a) {
@@ -335,9 +351,20 @@ int fpd_wgrad_reduce(const fpd_wreduce_entry_t* t, int32_t n, int64_t max_elems,
     return rc ? rc : check_launch();
 }
 
+// The first eligible backend decides: only the space-to-depth kernel applies `act`, and a launch it declines goes on to
+// kernels that do not.
+int fpd_stem_act_supported(const fpd_stem_t* a) {
+    if (!a || a->act.mode != FPD_BN_EVAL || !a->act.gamma || !a->act.beta || !a->act.running_mean || !a->act.running_var || a->out_stats != nullptr) return 0;
+    for (const StemBackend& e : g_stem_backends)
+        if (eligible(e.backends)) return (e.takes_act != nullptr && e.takes_act(*a)) ? 1 : 0;
+    return 0;
+}
+
 int fpd_stem_forward(const fpd_stem_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a && a->x && a->w && a->bias && a->y, "stem: null pointer");
     FPD_REQUIRE(a->P == (a->H + 6 - 7) / 2 + 1 && a->Q == (a->W + 6 - 7) / 2 + 1, "stem: bad output size");
+    FPD_REQUIRE(a->act.mode == FPD_BN_NONE || fpd_stem_act_supported(a) == 1,
+                "stem: the launch asks for BN + ReLU in its epilogue (act), which is not offered for it; fpd_stem_act_supported() reports 0");
     int rc = 1;
     for (const StemBackend& e : g_stem_backends)
         if (rc == 1 && eligible(e.backends)) rc = e.forward(*a, (hipStream_t)stream);
@@ -634,8 +661,9 @@ int fpd_plan_wait_op(fpd_plan* p, int32_t op, fpd_stream_t stream) {
 }
 
 static void conv_tag(char* p, size_t n, const char* what, const fpd_conv_t& c) {
-    snprintf(p, n, "%s N=%d H=%d W=%d C=%d K=%d R=%d s=%d %s%s%s%s", what, c.N, c.H, c.W, c.C, c.K, c.R, c.stride,
-             c.epi == FPD_EPI_BNRELU_BWD ? "dgrad" : "fwd", c.bn.mode == FPD_BN_EVAL ? " evalbn" : "", c.wg_partial ? " +wgrad" : "", c.fold_x ? " +fold" : "");
+    snprintf(p, n, "%s N=%d H=%d W=%d C=%d K=%d R=%d s=%d %s%s%s%s%s", what, c.N, c.H, c.W, c.C, c.K, c.R, c.stride,
+             c.epi == FPD_EPI_BNRELU_BWD ? "dgrad" : "fwd", c.bn.mode == FPD_BN_EVAL ? " evalbn" : "", c.wg_partial ? " +wgrad" : "", c.fold_x ? " +fold" : "",
+             c.x2 ? " +skip" : "");
 }
 // "<plan op index> <what> <shape>": the key tools/profile_summarize.py groups trace rows by
 static void set_op_tag(int idx, const fpd_op& o) {
@@ -658,7 +686,8 @@ static void set_op_tag(int idx, const fpd_op& o) {
         case FPD_OP_HEAD: snprintf(t, sizeof(t), "head N=%d H=%d W=%d C=%d J=%d", o.u.head.N, o.u.head.H, o.u.head.W, o.u.head.C, o.u.head.J); break;
         case FPD_OP_EW: snprintf(t, sizeof(t), "ew %s N=%d H=%d W=%d C=%d", ewn(o.u.ew.op), o.u.ew.N, o.u.ew.H, o.u.ew.W, o.u.ew.C); break;
         case FPD_OP_EW_PAIR: snprintf(t, sizeof(t), "ew2 %s N=%d H=%d W=%d C=%d | H=%d W=%d", ewn(o.u.epair.a.op), o.u.epair.a.N, o.u.epair.a.H, o.u.epair.a.W, o.u.epair.a.C, o.u.epair.b.H, o.u.epair.b.W); break;
-        case FPD_OP_STEM_FWD: case FPD_OP_STEM_WGRAD: snprintf(t, sizeof(t), "%s N=%d H=%d W=%d K=%d", o.type == FPD_OP_STEM_FWD ? "stem_fwd" : "stem_wgrad", o.u.stem.N, o.u.stem.H, o.u.stem.W, o.u.stem.K); break;
+        case FPD_OP_STEM_FWD: case FPD_OP_STEM_WGRAD: snprintf(t, sizeof(t), "%s N=%d H=%d W=%d K=%d%s", o.type == FPD_OP_STEM_FWD ? "stem_fwd" : "stem_wgrad", o.u.stem.N, o.u.stem.H, o.u.stem.W, o.u.stem.K,
+                                                              (o.type == FPD_OP_STEM_FWD && o.u.stem.act.mode != FPD_BN_NONE) ? " +act" : ""); break;
         case FPD_OP_AFFSUM: snprintf(t, sizeof(t), "affsum N=%d H=%d W=%d C=%d terms=%d", o.u.affsum.N, o.u.affsum.H, o.u.affsum.W, o.u.affsum.C, o.u.affsum.nterms); break;
         case FPD_OP_LOSS: snprintf(t, sizeof(t), "loss B=%d J=%d H=%d W=%d S=%d", o.u.loss.B, o.u.loss.J, o.u.loss.H, o.u.loss.W, o.u.loss.S); break;
         case FPD_OP_LOSS_OHKM: snprintf(t, sizeof(t), "loss_ohkm B=%d J=%d H=%d W=%d S=%d k=%d,%d", o.u.lossk.base.B, o.u.lossk.base.J, o.u.lossk.base.H, o.u.lossk.base.W, o.u.lossk.base.S, o.u.lossk.topk_pose, o.u.lossk.topk_kd); break;

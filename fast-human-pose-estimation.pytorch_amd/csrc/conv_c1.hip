@@ -51,8 +51,9 @@ __device__ __forceinline__ unsigned c1_floor(unsigned w, short lo) {
 
 // C, K: channels in / out of THIS launch.  BWD: BNRELU_BWD epilogue (no bias, no residual, no prologue BN).  FOLD (BWD only):
 // the operand is a folded BN-backward apply (fold_x).  WG (BWD only): also the weight / bias gradient of the forward
-// convolution this launch is the data gradient of.
-template <int C, int K, bool BWD, bool WG>
+// convolution this launch is the data gradient of.  SKIP (forward only, no RES): a second 1x1 source of C channels (fpd_conv_t.x2,
+// the downsample branch of a Bottleneck) whose rounded result is the residual: its weights and bias sit behind the first ones.
+template <int C, int K, bool BWD, bool WG, bool SKIP = false>
 struct C1Geo {
     static constexpr int CV = C / 8, KV = K / 8;         // 16-byte chunks per operand / output pixel
     static constexpr int NV = C / 16, NK = K / 16;       // operand / output vectors per lane and tile (32 px * CV / 64)
@@ -63,12 +64,13 @@ struct C1Geo {
     static constexpr int WAVE_LDS = WG ? TILE_A + TILE_O : (TILE_A > TILE_O ? TILE_A : TILE_O);
     static constexpr int FLUSH = C1_NW * 64 * 16 * 4 + C1_NW * K * 4 + 8 * 2 * K * 8;      // statistics records + common shifts + partial sums
     static constexpr int REGION = C1_NW * WAVE_LDS > FLUSH ? C1_NW * WAVE_LDS : FLUSH;
-    static constexpr int TABLES = (2 * C + (BWD ? 3 * C + 4 * K : 0) + K) * 4;
-    static constexpr int LDS = TABLES + K * C * 2 + REGION;
+    static constexpr int TABLES = (2 * C + (BWD ? 3 * C + 4 * K : 0) + K + (SKIP ? K : 0)) * 4;
+    static constexpr int LDS = TABLES + (SKIP ? 2 : 1) * K * C * 2 + REGION;
     static constexpr int NT = (C / 32) * (K / 32);       // 32x32 tiles of dW
     static constexpr int NTW = NT / C1_NW;               // ... per wave
     static_assert(!WG || (BWD && NT % C1_NW == 0 && NTW >= 1), "fused weight gradient: every wave owns whole tiles of dW");
     static_assert(64 % CV == 0 && 64 % KV == 0, "a lane keeps its channel chunk");
+    static_assert(!SKIP || (!BWD && !WG && K == 2 * C), "second source: forward launches C -> 2C only");
 };
 
 // the compiler may not move LDS accesses across the phases of a tile: the phases of ONE wave communicate through its private
@@ -83,9 +85,10 @@ struct C1Geo {
 #define C1_STAMP() do { } while (0)
 #endif
 
-template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES>
+template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES, bool SKIP>
 __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const int nblk) {
-    using G = C1Geo<C, K, BWD, WG>;
+    static_assert(!(SKIP && RES), "the second source IS the residual");
+    using G = C1Geo<C, K, BWD, WG, SKIP>;
     constexpr int CV = G::CV, KV = G::KV, NV = G::NV, NK = G::NK, KT = G::KT, KS = G::KS, PXA = G::PXA, PXO = G::PXO;
     constexpr int RPB = CV >= 16 ? 1 : 16 / CV;           // weight rows per 256-byte bank row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -102,13 +105,17 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
     float* s_fold = s_shift + C;                          // BWD: [3][C] coefficients of a folded BN-backward apply
     float* s_epi = s_fold + (BWD ? 3 * C : 0);            // BWD: [4][K] scale, shift, mean, invstd of epi_bn
     float* s_bias = s_epi + (BWD ? 4 * K : 0);            // [K]
-    unsigned char* sW = reinterpret_cast<unsigned char*>(s_bias + K);     // [K][C] bf16, 16-byte chunk c of row n at c ^ sw(n)
-    unsigned char* sT = sW + K * C * 2;                   // the waves' tiles
+    float* s_bias2 = s_bias + K;                          // SKIP: [K] bias of the second source
+    unsigned char* sW = reinterpret_cast<unsigned char*>(s_bias + K + (SKIP ? K : 0));     // [K][C] bf16, 16-byte chunk c of row n at c ^ sw(n)
+    unsigned char* sW2 = sW + K * C * 2;                  // SKIP: the second source's weights, same layout
+    unsigned char* sT = sW + (SKIP ? 2 : 1) * K * C * 2;  // the waves' tiles
     unsigned char* tA = sT + wave * G::WAVE_LDS;          // operand tile [32 px][PXA]
     unsigned char* tO = WG ? tA + G::TILE_A : tA;         // output tile [32 px][PXO] (no fused weight gradient: the operand tile is dead by then)
 
     const bf16_t* __restrict__ x = reinterpret_cast<const bf16_t*>(a.x);
     const bf16_t* __restrict__ w = reinterpret_cast<const bf16_t*>(a.w);
+    const bf16_t* __restrict__ x2 = reinterpret_cast<const bf16_t*>(a.x2);      // SKIP
+    const bf16_t* __restrict__ w2 = reinterpret_cast<const bf16_t*>(a.w2);
     bf16_t* y = reinterpret_cast<bf16_t*>(a.y);           // (the residual may alias it)
     const bf16_t* res = reinterpret_cast<const bf16_t*>(a.residual);
     const bf16_t* ex = reinterpret_cast<const bf16_t*>(a.epi_x);
@@ -129,7 +136,7 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
 
     // ---- prologue: the table chains (loads -> fp64 -> LDS) on different waves, requested before the long loads ----
     BnRaw braw;
-    float bias_raw;                                      // (set in the r_bias branch only: a default written here is sunk by hipcc
+    float bias_raw, bias2_raw;                           // (set in the r_bias branch only: a default written here is sunk by hipcc
                                                           //  behind the other branches' loads, where it needs vmcnt(0) -- see bn_request)
     const int te = tid - 128, tb = tid - 256;
     const bool r_bn = has_bn && tid < C;
@@ -144,13 +151,22 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
         stat_request(a.fold_stats, C, 1, tid, fs2);
     }
     else if (r_epi) bn_request(a.epi_bn, te, K, braw);
-    else if (r_bias) { bias_raw = 0.f; if (a.bias != nullptr) bias_raw = a.bias[tb]; }
+    else if (r_bias) {
+        bias_raw = 0.f; if (a.bias != nullptr) bias_raw = a.bias[tb];
+        if constexpr (SKIP) { bias2_raw = 0.f; if (a.bias2 != nullptr) bias2_raw = a.bias2[tb]; }
+    }
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- the tile's vectors: vector i of a lane is 16 bytes at (tile base) + (i * 64 + lane) * 16 -- whole 1 KB lines ----
     uint4 rx[NV];                                         // operand (fold: the masked gradient g)
     uint4 ru[FOLD ? NV : 1];                              // fold: the BN input u
-    uint4 rr[NK];                                         // forward: residual; backward: epi_x
+    uint4 rr[SKIP ? 1 : NK];                              // forward: residual; backward: epi_x
+    uint4 rx2[SKIP ? NV : 1];                             // SKIP: the second source (C channels: half the registers of the residual)
+    auto load_x2 = [&](int t) {
+        const uint4* px = reinterpret_cast<const uint4*>(x2) + ((size_t)t * 32 * CV + lane);
+#pragma unroll
+        for (int i = 0; i < (SKIP ? NV : 1); ++i) rx2[i] = px[i * 64];
+    };
     auto load_x = [&](int t) {
         const uint4* px = reinterpret_cast<const uint4*>(x) + ((size_t)t * 32 * CV + lane);
 #pragma unroll
@@ -164,25 +180,30 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
     auto load_r = [&](int t) {                            // (callers test has_res in forward mode)
         const uint4* pr = reinterpret_cast<const uint4*>(BWD ? ex : res) + ((size_t)t * 32 * KV + lane);
 #pragma unroll
-        for (int i = 0; i < NK; ++i) rr[i] = pr[i * 64];
+        for (int i = 0; i < (SKIP ? 1 : NK); ++i) rr[i] = pr[i * 64];
     };
     int tile = r_beg * C1_NW + wave;
     {
         // requested in the order they are needed: tables (above), weights -- the first barrier waits for both --, then the
         // first tile (100+ KB per block: at the chip's ~12 bytes per cycle and CU it takes 6-11 k cycles to arrive; stamps)
         constexpr int NWV = (K * CV + 511) / 512;         // weight vectors per thread
-        uint4 rw[NWV];
+        uint4 rw[NWV], rw2[SKIP ? NWV : 1];
 #pragma unroll
         for (int i = 0; i < NWV; ++i) {
             const int v = tid + i * 512;
             rw[i] = make_uint4(0, 0, 0, 0);
             if (v < K * CV) rw[i] = *reinterpret_cast<const uint4*>(w + (size_t)v * 8);
+            if constexpr (SKIP) {
+                rw2[i] = make_uint4(0, 0, 0, 0);
+                if (v < K * CV) rw2[i] = *reinterpret_cast<const uint4*>(w2 + (size_t)v * 8);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         {
             // (unconditionally, a wave without a tile re-reads the last one: behind a branch hipcc waits for EVERY load in
             //  flight -- vmcnt(0) -- before the weights go to the LDS, i.e. the first barrier waited for the whole first tile)
             const int t0 = min(tile, ntile - 1);
+            if constexpr (SKIP) load_x2(t0);             // (needed first)
             load_x(t0);
             if constexpr (BWD || has_res) load_r(t0);
         }
@@ -213,6 +234,7 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
             s_epi[te] = sc; s_epi[K + te] = sh; s_epi[2 * K + te] = mu; s_epi[3 * K + te] = is;
         } else if (r_bias) {
             s_bias[tb] = bias_raw;
+            if constexpr (SKIP) s_bias2[tb] = bias2_raw;
         }
 #pragma unroll
         for (int i = 0; i < NWV; ++i) {
@@ -221,6 +243,7 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
                 const int k = v / CV, ch = v % CV;
                 const int sw = (k / RPB) & (CV - 1);
                 *reinterpret_cast<uint4*>(sW + (k * CV + (ch ^ sw)) * 16) = rw[i];
+                if constexpr (SKIP) *reinterpret_cast<uint4*>(sW2 + (k * CV + (ch ^ sw)) * 16) = rw2[i];
             }
         }
     }
@@ -294,9 +317,15 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
             for (int i = 0; i < NV; ++i) po[i * 64] = rx[i];
         }
     };
+    // SKIP: the second source's lines go into the tile raw (same geometry as the operand: C channels)
+    auto stage2 = [&]() {
+#pragma unroll
+        for (int i = 0; i < (SKIP ? NV : 1); ++i)
+            *reinterpret_cast<uint4*>(tA + (pxa0 + i * (64 / CV)) * PXA + cch * 16) = make_uint4(rx2[i].x, rx2[i].y, rx2[i].z, rx2[i].w);
+    };
     // ---- 3. + residual + bias in fp32, ONE rounding, into the wave's bf16 output tile (lane: pixel l31, channels
-    //         kt * 32 + 8 q + 4 hh .. + 3) ----
-    auto finish = [&](const f32x16& accv, const int kt, auto resc) {
+    //         kt * 32 + 8 q + 4 hh .. + 3); sb: the bias table (SKIP: of the source being finished) ----
+    auto finish = [&](const f32x16& accv, const int kt, auto resc, const float* sb) {
         constexpr bool HASRES = decltype(resc)::value;
         {
 #pragma unroll
@@ -309,7 +338,7 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
                         v0 += c1_unpack(r2.x);
                         v1 += c1_unpack(r2.y);
                     }
-                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(s_bias + kt * 32 + 8 * q + 4 * hh);
+                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(sb + kt * 32 + 8 * q + 4 * hh);
                     v0 += f32x2{b4[0], b4[1]};
                     v1 += f32x2{b4[2], b4[3]};
                 }
@@ -433,6 +462,18 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
         const bool live = tile < ntile;                   // (wave-uniform)
         const bool pf = round + 1 < r_end && tile + C1_NW < ntile;      // a next tile to prefetch
         if (live) {
+            bf16x8 bf2[SKIP ? KS : 1];
+            if constexpr (SKIP) {
+                // ---- 0. the second source passes through the tile first: raw lines in, fragments out, then the operand proper
+                //         takes the tile over (the output tile aliases it: both sets of fragments are registers before the first
+                //         finish) ----
+                stage2();
+                if (pf) load_x2(tile + C1_NW);
+                C1_PHASE();
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk) bf2[kk] = *reinterpret_cast<const bf16x8*>(tA + l31 * PXA + kk * 32 + hh * 16);
+                C1_PHASE();
+            }
             if (FOLD && fold) { if constexpr (FOLD) stage(tile, std::integral_constant<int, 2>{}); }
             else if (has_bn) { if constexpr (!BWD) stage(tile, std::integral_constant<int, 1>{}); }
             else stage(tile, std::integral_constant<int, 0>{});
@@ -448,6 +489,28 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
 #pragma unroll
                 for (int i = 0; i < NK; ++i)
                     *reinterpret_cast<uint4*>(tO + (pxo0 + i * (64 / KV)) * PXO + kch * 16) = make_uint4(rr[i].x, rr[i].y, rr[i].z, rr[i].w);
+                C1_PHASE();
+            }
+            if constexpr (SKIP) {
+                // skip = round(W2 x2 + bias2) into the output tile -- what the plain launch of the downsample convolution stores --
+                // and the products below add it like any residual
+                C1_PHASE();
+#pragma unroll
+                for (int k0 = 0; k0 < KT; k0 += 2) {
+                    f32x16 acc0, acc1;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
+                    const unsigned char* wrow0 = sW2 + (k0 * 32 + l31) * (C * 2);
+#pragma unroll
+                    for (int kk = 0; kk < KS; ++kk) {
+                        const bf16x8 wf0 = *reinterpret_cast<const bf16x8*>(wrow0 + ((2 * kk + hh) ^ wsw) * 16);
+                        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf0, bf2[kk], acc0, 0, 0, 0);
+                        const bf16x8 wf1 = *reinterpret_cast<const bf16x8*>(wrow0 + 32 * (C * 2) + ((2 * kk + hh) ^ wsw) * 16);
+                        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf1, bf2[kk], acc1, 0, 0, 0);
+                    }
+                    finish(acc0, k0, std::false_type{}, s_bias2);
+                    finish(acc1, k0 + 1, std::false_type{}, s_bias2);
+                }
                 C1_PHASE();
             }
             // two 32-channel tiles of the output at a time: the accumulators of one pair are finished (step 3) while the next
@@ -467,8 +530,8 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
                         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf1, bf[kk], acc1, 0, 0, 0);
                     }
                 }
-                finish(acc0, k0, std::integral_constant<bool, has_res>{});
-                if (k0 + 1 < KT) finish(acc1, k0 + 1, std::integral_constant<bool, has_res>{});
+                finish(acc0, k0, std::integral_constant<bool, has_res || SKIP>{}, s_bias);
+                if (k0 + 1 < KT) finish(acc1, k0 + 1, std::integral_constant<bool, has_res || SKIP>{}, s_bias);
             }
             if constexpr (!BWD && has_res) { if (pf) load_r(tile + C1_NW); }
             C1_PHASE();
@@ -591,23 +654,28 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
 // over the grid (Bresenham) so that whatever part of the grid is resident first serves both in proportion.
 struct C1Args { fpd_conv_t c[2]; int nblk[2]; };
 
-template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES>
+template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES, bool SKIP = false>
 __global__ __launch_bounds__(512, 2) void c1_kernel(const C1Args p) {
     const int bid = blockIdx.x, n = gridDim.x, nb = p.nblk[1];
     const int fb0 = fpd_cut(bid, nb, n), fb1 = fpd_cut(bid + 1, nb, n);
     const int isb = fb1 > fb0 ? 1 : 0;
     const int u = isb ? fb0 : bid - fb0;
-    c1_body<C, K, BWD, FOLD, WG, RES>(p.c[isb], u, p.nblk[isb]);
+    c1_body<C, K, BWD, FOLD, WG, RES, SKIP>(p.c[isb], u, p.nblk[isb]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // FPD_C1: 0 = never, 1 = launches of >= FPD_C1_MIN_PX pixels (default), 2 = whenever the shape is in the domain (tests:
 // fpd_set_option("conv_c1", v)); FPD_C1_BLOCKS: persistent blocks of a launch (default 192 of the 256 CUs, see c1_blocks()).
-int g_c1_mode = -1, g_c1_blocks = -1;
+int g_c1_mode = -1, g_c1_blocks = -1, g_c1_skip = -1;
 std::atomic<int> g_c1_launches{0};                       // launches this kernel has served (tests: "conv_c1_launches")
 int c1_mode() {
     if (g_c1_mode < 0) { const char* e = getenv("FPD_C1"); g_c1_mode = e ? atoi(e) : 1; }
     return g_c1_mode;
+}
+// FPD_FUSE_SKIP (default 1; tests: fpd_set_option("conv_skip", v)): 0 = the second source (fpd_conv_t.x2) is not offered
+int c1_skip() {
+    if (g_c1_skip < 0) { const char* e = getenv("FPD_FUSE_SKIP"); g_c1_skip = e ? atoi(e) : 1; }
+    return g_c1_skip;
 }
 int c1_blocks() {
     // (192, not 256: a resident block owns most of its CU's LDS, and the frozen teacher's fused Bottlenecks -- 128 blocks of 151 KB on
@@ -637,8 +705,14 @@ int c1_fuse_wgrad() { return 1; }
 bool c1_chan(int c) { return c == 32 || c == 64 || c == 128; }
 bool c1_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// fold: decide for the launch as it will be made WITH a folded BN-backward apply, whatever a.fold_x holds now (ConvAsk)
-bool c1_domain(const fpd_conv_t& a, bool fold) {
+// fold: decide for the launch as it will be made WITH a folded BN-backward apply, whatever a.fold_x holds now (ConvAsk); skip: WITH
+// the second source the fields describe (forward C -> 2C, C in {32, 64}: K = 256 is outside c1_chan and stays two launches)
+bool c1_domain(const fpd_conv_t& a, bool fold, bool skip = false) {
+    if (skip) {
+        if (c1_skip() == 0 || a.epi != FPD_EPI_PLAIN || a.residual != nullptr || a.x2 == nullptr || a.w2 == nullptr) return false;
+        if (a.C2 != a.C || a.K != 2 * a.C || a.C > 64 || !c1_chan(a.C)) return false;
+        if (!c1_aligned(a.x2) || !c1_aligned(a.w2) || a.y == a.x2) return false;
+    }
     if (a.dtype != FPD_BF16 || a.R != 1 || a.S != 1 || a.stride != 1 || a.pad != 0 || a.P != a.H || a.Q != a.W) return false;
     // (16 -> 128: the inter-stack score_ convolution and the data gradient of the score convolution, hourglass.py:136-137, one k-step)
     if (!(c1_chan(a.C) || (a.C == 16 && a.K == 128)) || !c1_chan(a.K)) return false;
@@ -666,7 +740,7 @@ struct C1Plan { int na, nb, grid; bool wg; };
 // variant: their folded launch goes on to the next kernel); the fused weight gradient needs a dW tile for every wave.
 bool c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, C1Plan& pl) {
     const int mode = c1_mode();
-    if (mode == 0 || !c1_domain(a, ask.fold)) return false;
+    if (mode == 0 || !c1_domain(a, ask.fold, ask.skip) || (ask.skip && b != nullptr)) return false;
     const bool bwd = a.epi == FPD_EPI_BNRELU_BWD;
     long long px = (long long)a.N * a.H * a.W;
     if (b != nullptr) {
@@ -689,24 +763,25 @@ bool c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& 
     pl.grid = total;
     pl.wg = ask.wg && c1_fuse_wgrad() != 0 && bwd && (a.C / 32) * (a.K / 32) == C1_NW;      // (a pair: same C, K, epilogue)
     r.folds = ask.fold && bwd;
+    r.skips = ask.skip;
     r.slabs_a = pl.wg ? pl.na : 0;
     r.slabs_b = pl.wg ? pl.nb : 0;
     return true;
 }
 
-template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES>
+template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES, bool SKIP = false>
 int c1_launch_t(const fpd_conv_t& a, const fpd_conv_t* b, const C1Plan& pl, hipStream_t st) {
     static LdsAttr configured;
 #ifdef FPD_C1_TIMING
-    constexpr size_t lds = C1Geo<C, K, BWD, WG>::LDS + 1024;
+    constexpr size_t lds = C1Geo<C, K, BWD, WG, SKIP>::LDS + 1024;
 #else
-    constexpr size_t lds = C1Geo<C, K, BWD, WG>::LDS;
+    constexpr size_t lds = C1Geo<C, K, BWD, WG, SKIP>::LDS;
 #endif
     static_assert(lds <= 160 * 1024, "conv_c1: LDS budget");
-    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&c1_kernel<C, K, BWD, FOLD, WG, RES>), lds)) return rc_;
+    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&c1_kernel<C, K, BWD, FOLD, WG, RES, SKIP>), lds)) return rc_;
     C1Args args;
     args.c[0] = a; args.c[1] = b ? *b : a; args.nblk[0] = pl.na; args.nblk[1] = pl.nb;
-    FPD_LAUNCH((c1_kernel<C, K, BWD, FOLD, WG, RES>), dim3(pl.grid), dim3(512), lds, st, args);
+    FPD_LAUNCH((c1_kernel<C, K, BWD, FOLD, WG, RES, SKIP>), dim3(pl.grid), dim3(512), lds, st, args);
     g_c1_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
@@ -724,6 +799,10 @@ int c1_launch_ck(const fpd_conv_t& a, const fpd_conv_t* b, const C1Plan& pl, hip
             return 1;
         }
     }
+    if (a.x2 != nullptr) {
+        if constexpr (K == 2 * C && C >= 32 && C <= 64) return c1_launch_t<C, K, false, false, false, false, true>(a, nullptr, pl, st);
+        else return 1;
+    }
     if (a.residual != nullptr) return c1_launch_t<C, K, false, false, false, true>(a, b, pl, st);
     return c1_launch_t<C, K, false, false, false, false>(a, b, pl, st);
 }
@@ -739,8 +818,9 @@ int c1_launch_c(const fpd_conv_t& a, const fpd_conv_t* b, const C1Plan& pl, hipS
 
 }  // namespace
 
-int fpd_conv_c1_option(int which, int value) {      // which: 0 = mode, 1 = blocks (returns the previous value), 2 = launches served so far
+int fpd_conv_c1_option(int which, int value) {      // which: 0 = mode, 1 = blocks, 3 = second source offered (returns the previous value), 2 = launches served so far
     if (which == 2) return g_c1_launches.load(std::memory_order_relaxed);
+    if (which == 3) { const int prev = c1_skip(); g_c1_skip = value; return prev; }
     int& g = which == 0 ? g_c1_mode : g_c1_blocks;
     const int prev = which == 0 ? c1_mode() : c1_blocks();
     g = value;

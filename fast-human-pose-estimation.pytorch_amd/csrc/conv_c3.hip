@@ -533,7 +533,7 @@ int c3_launch_t(const fpd_conv_t& a, const fpd_conv_t* b, const C3Plan& pl, hipS
 // The ONE decision of this unit, for the launch and for the queries.  A data gradient evaluates a folded BN-backward apply on its
 // operand; the weight gradient of a 3x3 convolution stays a separate launch that reads fold_out (0 slabs).
 bool c3_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, C3Plan& pl) {
-    if (!c3_takes(a, b) || !c3_plan(a, b, pl)) return false;
+    if (ask.skip || !c3_takes(a, b) || !c3_plan(a, b, pl)) return false;
     r = ConvRoute{ask.fold && a.epi == FPD_EPI_BNRELU_BWD, 0, 0};
     return true;
 }

@@ -8,10 +8,12 @@
 //      queries of api.hip (fold, slab count) both go through ----
 // What the launch (b != nullptr: the pair launch) WILL carry, whatever the descriptor fields hold now: the queries are asked
 // before the caller fills in the fold and slab fields.
-struct ConvAsk { bool fold, wg; };         // some convolution of the launch folds a BN-backward apply / forms a weight gradient
-struct ConvRoute { bool folds; int slabs_a, slabs_b; };      // the fold is evaluated; weight-gradient slabs written for a / b (0: none)
+// (skip: the launch carries a second 1x1 source, fpd_conv_t.x2 -- only conv_c1 offers it, every other route declines such a launch)
+struct ConvAsk { bool fold, wg, skip; };   // some convolution of the launch folds a BN-backward apply / forms a weight gradient / has a second source
+struct ConvRoute { bool folds; int slabs_a, slabs_b; bool skips; };      // the fold is evaluated; weight-gradient slabs written for a / b (0: none); the second source is formed
 inline ConvAsk fpd_conv_ask(const fpd_conv_t& a, const fpd_conv_t* b) {
-    return ConvAsk{a.fold_x != nullptr || (b != nullptr && b->fold_x != nullptr), a.wg_partial != nullptr || (b != nullptr && b->wg_partial != nullptr)};
+    return ConvAsk{a.fold_x != nullptr || (b != nullptr && b->fold_x != nullptr), a.wg_partial != nullptr || (b != nullptr && b->wg_partial != nullptr),
+                   a.x2 != nullptr || (b != nullptr && b->x2 != nullptr)};
 }
 // the slab fields of a launch against the slab count of its route (the count was asked for when the workspace was sized; a
 // geometry that has changed since would write past the workspace or leave slabs unwritten)
@@ -56,6 +58,8 @@ int fpd_wreduce_launch(const fpd_wreduce_entry_t* table, int n, int64_t max_elem
 
 // ---- stem ----
 int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st);
+bool fpd_stem_forward_s2d_takes_act(const fpd_stem_t& a);
+int fpd_stem_s2d_option(int which, int value);
 int fpd_stem_wgrad_s2d_partials(const fpd_stem_t& a);
 int fpd_stem_wgrad_s2d_launch(const fpd_stem_t& a, hipStream_t st);
 int fpd_stem_forward_mfma_launch(const fpd_stem_t& a, hipStream_t st);

@@ -853,7 +853,7 @@ static bool pp_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
 // a folded BN-backward apply on the way into the operand image; the fold is decided before the fused weight gradient is, so it is
 // offered only where the launch exists both with and without that fusion (the slab count does not depend on the fold).
 static bool pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, PPPlan& pl) {
-    if (!pp_takes(a, b) || !pp_plan(a, b, ask, pl)) return false;
+    if (ask.skip || !pp_takes(a, b) || !pp_plan(a, b, ask, pl)) return false;
     auto foldable = [](const fpd_conv_t& c) { return c.epi == FPD_EPI_BNRELU_BWD && c.bn.mode == FPD_BN_NONE; };
     PPPlan other;
     r.folds = ask.fold && foldable(a) && (b == nullptr || foldable(*b)) &&

@@ -457,7 +457,7 @@ struct TilePlan { int esz, bk, tn, tiles; bool allw, fold; size_t lds; };
 // (fpd_conv_t.fold_x) by the FOLD variants, which are compiled for TN <= 2 (register budget) and kept to channel counts for
 // which the LDS never runs out.
 static bool tile_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, TilePlan& pl) {
-    if (!tile_domain(a)) return false;
+    if (ask.skip || !tile_domain(a)) return false;
     if (b != nullptr && (!tile_domain(*b) || a.dtype != b->dtype || a.K != b->K || a.C != b->C || a.R != b->R)) return false;
     pl.esz = a.dtype == FPD_BF16 ? 2 : 4;
     const int vec = 16 / pl.esz;

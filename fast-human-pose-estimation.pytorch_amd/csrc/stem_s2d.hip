@@ -38,7 +38,10 @@ __shared__ int s2_ns;
 #define S2_STAMP() do { } while (0)
 #endif
 
-template <int TN>
+// ACT: the frozen network's bn1 + ReLU in the epilogue (fpd_stem_t.act, eval mode; no statistics): the value is rounded as the
+// plain launch stores it, then scale / shift / ReLU and the second rounding of the elementwise launch this replaces
+// (bn_act() on the coefficients of bn_coef(): the same floats) -- one pass over the 128x128 map instead of three.
+template <int TN, bool ACT>
 __global__ __launch_bounds__(256) void stem_s2d_fwd_kernel(const fpd_stem_t a, const int logQ, const int ntiles) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -134,16 +137,34 @@ __global__ __launch_bounds__(256) void stem_s2d_fwd_kernel(const fpd_stem_t a, c
 
     // epilogue state: accumulator element 4 j + i of tile tn is channel 32 tn + 8 j + 4 hh + i of pixel ml
     bf16_t* __restrict__ y = reinterpret_cast<bf16_t*>(a.y);
-    const bool want_stats = a.out_stats != nullptr;
+    const bool want_stats = !ACT && a.out_stats != nullptr;
+    // ACT: f1 / f2 hold the channel's scale / shift instead of the statistics partials (there are none)
     f32x4 bias4[TN][4], f1[TN][4], f2[TN][4];
+    const int act_relu = a.act.relu;
+    if constexpr (ACT) {
+        float* s_act = reinterpret_cast<float*>(sW + 32 * TN * S2_WROW);      // [2][32 TN] behind the weights
+        if (tid < 32 * TN) {
+            float sc = 0.f, sh = 0.f, mu, is;
+            if (tid < K) bn_coef(a.act, tid, K, 1.0, sc, sh, mu, is);
+            s_act[tid] = sc;
+            s_act[32 * TN + tid] = sh;
+        }
+        __syncthreads();
+    }
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int k = 32 * tn + 8 * j + 4 * hh;
             bias4[tn][j] = (k < K) ? f32x4{a.bias[k], a.bias[k + 1], a.bias[k + 2], a.bias[k + 3]} : f32x4{0.f, 0.f, 0.f, 0.f};      // K % 8 == 0
-            f1[tn][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            f2[tn][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (ACT) {
+                const float* s_act = reinterpret_cast<const float*>(sW + 32 * TN * S2_WROW);
+                f1[tn][j] = *reinterpret_cast<const f32x4*>(s_act + k);
+                f2[tn][j] = *reinterpret_cast<const f32x4*>(s_act + 32 * TN + k);
+            } else {
+                f1[tn][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                f2[tn][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
         }
 
     int ring_n = -1, ring_hi = 0;      // rows [.., ring_hi) of image ring_n are in the ring (as far as the current tile needs them)
@@ -198,7 +219,14 @@ __global__ __launch_bounds__(256) void stem_s2d_fwd_kernel(const fpd_stem_t a, c
                 if (32 * tn + 8 * j < K) {
                     const f32x4 b = bias4[tn][j];
                     const float v0 = acc[tn][4 * j] + b[0], v1 = acc[tn][4 * j + 1] + b[1], v2 = acc[tn][4 * j + 2] + b[2], v3 = acc[tn][4 * j + 3] + b[3];
-                    const unsigned p0 = f2bf_pk(v0, v1), p1 = f2bf_pk(v2, v3);
+                    unsigned p0 = f2bf_pk(v0, v1), p1 = f2bf_pk(v2, v3);
+                    if constexpr (ACT) {
+                        const f32x4 sc = f1[tn][j], sh = f2[tn][j];
+                        const float r0 = bn_act(__uint_as_float(p0 << 16), sc[0], sh[0], act_relu), r1 = bn_act(__uint_as_float(p0 & 0xffff0000u), sc[1], sh[1], act_relu);
+                        const float r2 = bn_act(__uint_as_float(p1 << 16), sc[2], sh[2], act_relu), r3 = bn_act(__uint_as_float(p1 & 0xffff0000u), sc[3], sh[3], act_relu);
+                        p0 = f2bf_pk(r0, r1);
+                        p1 = f2bf_pk(r2, r3);
+                    }
                     *reinterpret_cast<uint2*>(yrow + 32 * tn + 8 * j) = make_uint2(p0, p1);
                     if (want_stats) {
                         const f32x4 d = {__uint_as_float(p0 << 16) - b[0], __uint_as_float(p0 & 0xffff0000u) - b[1],
@@ -455,29 +483,60 @@ __global__ __launch_bounds__(256) void stem_s2d_wgrad_kernel(const fpd_stem_t a,
 
 }  // namespace
 
+// FPD_STEM_ACT (default 1; tests: fpd_set_option("stem_act", v)): 0 = the epilogue BN + ReLU (fpd_stem_t.act) is not offered
+static int g_stem_act = -1;
+static int stem_act_mode() {
+    if (g_stem_act < 0) { const char* e = getenv("FPD_STEM_ACT"); g_stem_act = e ? atoi(e) : 1; }
+    return g_stem_act;
+}
+int fpd_stem_s2d_option(int which, int value) {
+    (void)which;
+    const int prev = stem_act_mode();
+    g_stem_act = value;
+    return prev;
+}
+
+// the forward kernel's domain; logQ of the launch
+static bool s2d_fwd_ok(const fpd_stem_t& a, int& logQ) {
+    if (a.dtype != FPD_BF16 || a.K % 8 != 0 || a.K > 64) return false;
+    if (a.Q > 128 || a.Q < 16 || (a.Q & (a.Q - 1)) != 0 || a.H != 2 * a.P || a.W != 2 * a.Q) return false;
+    logQ = 0;
+    while ((1 << logQ) < a.Q) ++logQ;
+    return a.P % (128 >> logQ) == 0;
+}
+bool fpd_stem_forward_s2d_takes_act(const fpd_stem_t& a) {
+    int logQ;
+    return stem_act_mode() != 0 && a.act.mode == FPD_BN_EVAL && a.out_stats == nullptr && s2d_fwd_ok(a, logQ);
+}
+
 // return 1 = not applicable (the caller falls through to stem_fwd_mfma / the direct kernels)
 int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st) {
-    if (a.dtype != FPD_BF16 || a.K % 8 != 0 || a.K > 64) return 1;
-    if (a.Q > 128 || a.Q < 16 || (a.Q & (a.Q - 1)) != 0 || a.H != 2 * a.P || a.W != 2 * a.Q) return 1;
-    int logQ = 0;
-    while ((1 << logQ) < a.Q) ++logQ;
+    int logQ;
+    if (!s2d_fwd_ok(a, logQ)) return 1;
+    const bool act = a.act.mode != FPD_BN_NONE;
+    if (act && !fpd_stem_forward_s2d_takes_act(a)) return 1;
     const int rows = 128 >> logQ;
-    if (a.P % rows != 0) return 1;
     const int TN = a.K > 32 ? 2 : 1;
     const int ring = 2 * rows + 3;
-    const size_t lds = std::max((size_t)ring * (a.Q + 3) * S2_PIXB + (size_t)32 * TN * S2_WROW,
-                                (size_t)4 * 32 * TN * 2 * (33 * sizeof(float) + sizeof(double)));      // tiles | block-end statistics transposition
+    const size_t lds = std::max((size_t)ring * (a.Q + 3) * S2_PIXB + (size_t)32 * TN * S2_WROW + (act ? (size_t)2 * 32 * TN * sizeof(float) : 0),
+                                (size_t)4 * 32 * TN * 2 * (33 * sizeof(float) + sizeof(double)));      // tiles (+ scale / shift) | block-end statistics transposition
     const int tiles = a.N * a.P * a.Q / 128;
     static const int cap = 0;        // (0 = the per-K defaults below; the FPD_STEM_BLOCKS knob of round 5 is gone)
     // K = 32: two blocks per CU (35.6 us at 512 blocks, 47.6 at 256, 44.1 at 1024); K = 64: 62.2 us at 256, 71.8 at 512 (r05, one box)
     const int blocks = std::max(1, std::min(tiles, cap > 0 ? cap : (TN == 1 ? 512 : 256)));
-    static LdsAttr cfg1, cfg2;
-    if (TN == 1) {
-        if (int rc_ = cfg1.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<1>), lds)) return rc_;
-        FPD_LAUNCH((stem_s2d_fwd_kernel<1>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
+    static LdsAttr cfg1, cfg2, cfg1a, cfg2a;
+    if (TN == 1 && !act) {
+        if (int rc_ = cfg1.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<1, false>), lds)) return rc_;
+        FPD_LAUNCH((stem_s2d_fwd_kernel<1, false>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
+    } else if (!act) {
+        if (int rc_ = cfg2.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<2, false>), lds)) return rc_;
+        FPD_LAUNCH((stem_s2d_fwd_kernel<2, false>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
+    } else if (TN == 1) {
+        if (int rc_ = cfg1a.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<1, true>), lds)) return rc_;
+        FPD_LAUNCH((stem_s2d_fwd_kernel<1, true>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
     } else {
-        if (int rc_ = cfg2.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<2>), lds)) return rc_;
-        FPD_LAUNCH((stem_s2d_fwd_kernel<2>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
+        if (int rc_ = cfg2a.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<2, true>), lds)) return rc_;
+        FPD_LAUNCH((stem_s2d_fwd_kernel<2, true>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
     }
     return 0;
 }

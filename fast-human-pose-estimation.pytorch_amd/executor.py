@@ -162,6 +162,10 @@ class Lowering:
         s.bn = self.bn(op.bn)
         s.epi_x, s.epi_bn, s.epi_stats = p(_abuf(op.epi_x)), self.bn(op.epi_bn), p(op.epi_stats)
         s.wg_partial, s.wg_stride, s.wg_bias, s.wg_count = None, 0, 0, 0
+        if not plain and getattr(op, 'skip_fused', False):  # formed inside the launch of the conv3 it is the residual of (plan_skips)
+            return R.OP_NOP, R.MemsetT()
+        if not plain and getattr(op, 'skip_active', False):
+            self._fill_skip(op, s)
         if not plain and getattr(op, 'fused_wgrad', None) is not None and self.use_partials:
             n = R.lib().fpd_conv_fused_wgrad_partials(C.byref(s))
             if n > 0:
@@ -219,6 +223,64 @@ class Lowering:
                 for m in cands:
                     m.fold_active = True
                     m.fold_apply.folded = True
+
+    def _fill_skip(self, op, s):
+        """Second 1x1 source of a conv3 that forms its Bottleneck's downsample convolution itself (fpd_conv_t.x2)."""
+        sc, p = op.skip_conv, self.A.ptr
+        assert _abuf(sc.y) is _abuf(op.residual) and sc.bn is None, 'skip: the downsample convolution must produce exactly this residual'
+        s.x2, s.w2, s.bias2, s.C2 = p(_abuf(sc.x)), p(sc.w), p(sc.bias), sc.dims[3]
+        s.residual = None
+
+    def plan_skips(self, ops, readers=None):
+        """Decide, BEFORE the forward list is lowered, which downsample convolutions (graph: conv3.skip_conv) are formed inside
+        the conv3 launch they are the residual of (include/fpd_amd.h: fpd_conv_t.x2): the skip tensor has no other reader
+        (among `readers`, default `ops`), both ops run on one lane, neither is an fp8 convolution, and the library serves the
+        launch as it will be made.  The downsample op is then lowered as a no-op (`skip_fused`), conv3 is `skip_active`."""
+        if os.environ.get('FPD_FUSE_SKIP', '1') == '0':
+            return
+        l = R.lib()
+        readers = ops if readers is None else readers
+        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
+        for op in ops:
+            sc = getattr(op, 'skip_conv', None) if op is not None and op.kind == 'conv' else None
+            if sc is None or not any(o is sc for o in ops) or (op.lane or 0) != (sc.lane or 0):
+                continue
+            if getattr(op, 'w8', None) is not None or getattr(sc, 'w8', None) is not None or sc.bn is not None:
+                continue
+            if _abuf(sc.y) is not _abuf(op.residual) or sc.out_stats is not None:
+                continue
+            y = _abuf(sc.y)
+            if any(o is not op and any(_abuf(t) is y for t in o.acts_in()) for top in readers if top is not None for o in members_of(top)):
+                continue
+            s = self.conv(op, plain=True)[1]
+            self._fill_skip(op, s)
+            if l.fpd_conv_skip_supported(C.byref(s)) == 1:
+                op.skip_active = True
+                sc.skip_fused = True
+
+    def plan_stem_act(self, ops, readers=None):
+        """The same for a frozen stem's BN + ReLU (graph: stem_fwd.act_ew; fpd_stem_t.act): the elementwise op becomes a no-op and
+        the stem writes the activation, where the BN is in eval mode, the stem output has no other reader and the library
+        serves the launch."""
+        if os.environ.get('FPD_STEM_ACT', '1') == '0':
+            return
+        readers = ops if readers is None else readers
+        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
+        for op in ops:
+            ae = getattr(op, 'act_ew', None) if op is not None and op.kind == 'stem_fwd' else None
+            if ae is None or not any(o is ae for o in ops) or (op.lane or 0) != (ae.lane or 0):
+                continue
+            if ae.op != 'bnrelu_fwd' or ae.bn is None or ae.bn.mode != 'eval' or _abuf(ae.x) is not _abuf(op.y):
+                continue
+            if op.out_stats is not None or ae.out_stats is not None:
+                continue
+            y = _abuf(op.y)
+            if any(o is not ae and any(_abuf(t) is y for t in o.acts_in()) for top in readers if top is not None for o in members_of(top)):
+                continue
+            op.act_active = True
+            ok = R.lib().fpd_stem_act_supported(C.byref(self.stem(op)[1])) == 1
+            op.act_active = ok
+            ae.stem_fused = ok
 
     def _fill_fold(self, op, s):
         """Fold fields of a data gradient that evaluates its BN-backward apply itself (plan_folds decided)."""
@@ -350,6 +412,8 @@ class Lowering:
         s.x = p(op.image)
         if op.kind == 'stem_fwd':
             s.w, s.bias, s.y, s.out_stats = p(op.w), p(op.bias), p(_abuf(op.y)), p(op.out_stats)
+            if getattr(op, 'act_active', False):           # bn1 + ReLU in the epilogue: the stem writes the activation (plan_stem_act)
+                s.act, s.y = self.bn(op.act_ew.bn), p(_abuf(op.act_ew.y))
             return R.OP_STEM_FWD, s
         s.dy, s.dw, s.dbias = p(_abuf(op.dy)), p(op.dw), p(op.dbias)
         s.partial, s.partial_stride = None, 0
@@ -364,6 +428,8 @@ class Lowering:
 
     def ew(self, op):
         if getattr(op, 'folded', False):                   # evaluated by the data gradient that consumes it (plan_folds)
+            return R.OP_NOP, R.MemsetT()
+        if getattr(op, 'stem_fused', False):               # applied in the epilogue of the stem that produces its input (plan_stem_act)
             return R.OP_NOP, R.MemsetT()
         s = R.EwT()
         s.op, s.dtype = _EW[op.op], self.dtype
@@ -499,6 +565,8 @@ class GraphInstance:
                                       num_blocks=cfg.get('num_blocks', 1), wlp_is_master=(self.dtype == R.F32),
                                       fuse_bneck=(self.dtype == R.BF16 and not train and env('FPD_FUSE_BNECK', '1') != '0'),
                                       pair_branches=env('FPD_PAIR', '1') != '0', fuse_head=env('FPD_FUSE_HEAD', '1') != '0',
+                                      fuse_skip=(self.dtype == R.BF16 and env('FPD_FUSE_SKIP', '1') != '0'),
+                                      fuse_stem_act=(self.dtype == R.BF16 and env('FPD_STEM_ACT', '1') != '0'),
                                       wgrad_batch=int(env('FPD_WGRAD_BATCH')) if env('FPD_WGRAD_BATCH') else None)
         self.A = Arenas(state.device, self.dtype, parent=state.A)
         self.low = Lowering(self.A, self.dtype)
@@ -575,6 +643,8 @@ class GraphInstance:
         self.rng['prep'] = (b, len(p))
         b = len(p)
         self.op_index = {}                         # id(IR op) -> plan op (bench.py times single recorded ops through it)
+        self.low.plan_skips(g.fwd, readers=ops)
+        self.low.plan_stem_act(g.fwd, readers=ops)
         for op in g.fwd:
             self.op_index[id(op)] = p.add(*self.low.op(op))
         self.rng['fwd'] = (b, len(p))

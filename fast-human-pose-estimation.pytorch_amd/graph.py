@@ -129,6 +129,9 @@ class Op:
                 # apply's inputs and writes its outputs
                 rd += [b(fa.x), b(fa.dy), fa.bstats] + bn_bufs(fa.bn)
                 wr += [b(fa.y), fa.dgamma, fa.dbeta]
+            sc = getattr(self, 'skip_conv', None)          # conv3 of a downsample Bottleneck may form the skip convolution itself
+            if sc is not None and getattr(self, 'skip_active', False):      # (executor.plan_skips): then it reads that op's inputs
+                rd += [b(sc.x), sc.w, sc.bias]
         elif k == 'head':
             rd = [b(self.y0), b(self.x), self.w_fc, self.b_fc, self.w_score, self.b_score, self.w_fc2, self.b_fc2,
                   self.w_score2, self.b_score2] + bn_bufs(self.bn)
@@ -153,6 +156,10 @@ class Op:
             rd, wr = [self.region], []
         elif k == 'stem_fwd':
             rd, wr = [self.image, self.w, self.bias], [b(self.y), self.out_stats]
+            ae = getattr(self, 'act_ew', None)             # the frozen stem may apply its BN + ReLU itself (executor.plan_stem_act)
+            if ae is not None and getattr(self, 'act_active', False):
+                rd += bn_bufs(ae.bn)
+                wr += [b(ae.y)]
         elif k == 'stem_wgrad':
             rd, wr = [self.image, b(self.dy)], [self.dw, self.dbias]
         elif k == 'ew':
@@ -169,6 +176,9 @@ class Op:
             return [t for t in (self.y0, self.x) if t is not None]
         fa = getattr(self, 'fold_apply', None)
         folded = [t for t in (fa.x, fa.dy) if isinstance(t, Act)] if fa is not None else []
+        sc = getattr(self, 'skip_conv', None)              # (conservatively, whatever the lowering decides: x stays alive up to conv3)
+        if sc is not None and isinstance(sc.x, Act):
+            folded = folded + [sc.x]
         return [getattr(self, f) for f in ('x', 'x2', 'dy', 'add', 'residual', 'epi_x') if
                 isinstance(getattr(self, f, None), Act)] + [a for a in getattr(self, 'extra_in', []) if a is not None] + folded
 
@@ -177,8 +187,9 @@ class Op:
             return self.a.acts_out() + self.b.acts_out()
         if self.kind == 'head':
             return [t for t in (self.score, self.next) if t is not None]
+        ae = getattr(self, 'act_ew', None)                 # (conservatively: the activation's buffer exists when the stem runs)
         return [getattr(self, f) for f in ('y',) if isinstance(getattr(self, f, None), Act)] + \
-               [a for a in getattr(self, 'extra_out', []) if a is not None]
+               [a for a in getattr(self, 'extra_out', []) if a is not None] + ([ae.y] if ae is not None else [])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -342,7 +353,8 @@ class HourglassGraph:
     """Op lists for one (model, batch shape, train|eval) instance."""
 
     def __init__(self, params, num_feats, num_stacks, num_joints, batch, height, width, train, num_blocks=1,
-                 depth=4, wlp_is_master=True, lane_levels=None, wgrad_batch=None, fuse_bneck=False, pair_branches=True, fuse_head=True):
+                 depth=4, wlp_is_master=True, lane_levels=None, wgrad_batch=None, fuse_bneck=False, pair_branches=True, fuse_head=True,
+                 fuse_skip=False, fuse_stem_act=False):
         self.p = params
         self.F, self.S, self.J = num_feats, num_stacks, num_joints
         self.N, self.H, self.W = batch, height, width
@@ -354,6 +366,10 @@ class HourglassGraph:
         # shapes: their convolutions (and their data gradients) are issued pairwise as ONE launch ('conv2' ops), which
         # takes ~100 launches off the latency-bound critical chain of a training step.
         self.pair_branches = pair_branches
+        # graphs built for the device mark two relations the lowering may fuse (the op lists keep every op): the downsample 1x1
+        # of layer1 / layer2 formed inside conv3's launch, a frozen stem's bn1 + ReLU applied in the stem's epilogue.  Marking
+        # keeps the tensors involved alive one op longer, so a graph built only for the interpreter leaves it off.
+        self.fuse_skip, self.fuse_stem_act = fuse_skip, fuse_stem_act and not train
         self._pair_op = None
         self._pair_ew = None
         self.stats_size = 0
@@ -495,7 +511,12 @@ class HourglassGraph:
         if (p + 'downsample.0.weight') in self.p.entries:
             assert sink is None
             skip = self.conv(x, p + 'downsample.0')
-        return self.conv(t, p + 'conv3', bn=self._bn(p + 'bn3', planes), residual=skip, sink=sink)
+        y = self.conv(t, p + 'conv3', bn=self._bn(p + 'bn3', planes), residual=skip, sink=sink)
+        if skip is not x and getattr(self, 'fuse_skip', False):
+            # the relation only: the lowering may form the skip convolution inside this launch (fpd_conv_t.x2, executor.plan_skips);
+            # the op lists keep both convolutions
+            y.producer.skip_conv = skip.producer
+        return y
 
     def _fused(self, x, p):
         planes = self.p[p + 'conv1.weight'].shape[0]
@@ -565,6 +586,9 @@ class HourglassGraph:
         bn1 = self._bn('bn1', K)
         self._use_bn(x, bn1)
         x = self.ew('bnrelu_fwd', x.shape, x.shape, 'stem_act', x=x, bn=bn1)
+        if bn1.mode == 'eval' and self.fuse_stem_act:
+            # the relation only: a frozen stem may apply bn1 + ReLU in its epilogue (fpd_stem_t.act, executor.plan_stem_act)
+            op.act_ew = x.producer
         x = self.residual_seq(x, 'layer1.', 1)
         x = self.maxpool(x, 'pool1')
         x = self.residual_seq(x, 'layer2.', 1)

@@ -36,7 +36,8 @@ class ConvT(C.Structure):
                 ('_pad', _i32), ('x', _vp), ('w', _vp), ('bias', _vp), ('residual', _vp), ('y', _vp),
                 ('out_stats', _vp), ('bn', BnT), ('epi_x', _vp), ('epi_bn', BnT), ('epi_stats', _vp),
                 ('wg_partial', _vp), ('wg_stride', _i64), ('wg_bias', _i32), ('wg_count', _i32),
-                ('fold_x', _vp), ('fold_bn', BnT), ('fold_stats', _vp), ('fold_out', _vp), ('fold_dgamma', _vp), ('fold_dbeta', _vp)]
+                ('fold_x', _vp), ('fold_bn', BnT), ('fold_stats', _vp), ('fold_out', _vp), ('fold_dgamma', _vp), ('fold_dbeta', _vp),
+                ('x2', _vp), ('w2', _vp), ('bias2', _vp), ('C2', _i32), ('_pad2', _i32)]
 
 
 class ConvF8T(C.Structure):
@@ -70,7 +71,7 @@ class WgradT(C.Structure):
 class StemT(C.Structure):
     _fields_ = [('N', _i32), ('H', _i32), ('W', _i32), ('K', _i32), ('P', _i32), ('Q', _i32), ('dtype', _i32),
                 ('_pad', _i32), ('x', _vp), ('w', _vp), ('bias', _vp), ('y', _vp), ('out_stats', _vp), ('dy', _vp),
-                ('dw', _vp), ('dbias', _vp), ('partial', _vp), ('partial_stride', _i64)]
+                ('dw', _vp), ('dbias', _vp), ('partial', _vp), ('partial_stride', _i64), ('act', BnT)]
 
 
 class EwT(C.Structure):
@@ -199,6 +200,8 @@ SYMBOLS = {
     'fpd_conv_fused_wgrad_partials': (C.c_int, [C.POINTER(ConvT)]),
     'fpd_conv_fold_supported': (C.c_int, [_vp]),
     'fpd_conv_pair_fold_supported': (C.c_int, [_vp]),
+    'fpd_conv_skip_supported': (C.c_int, [_vp]),
+    'fpd_stem_act_supported': (C.c_int, [_vp]),
     'fpd_conv_pair_fused_wgrad_partials': (C.c_int, [C.POINTER(ConvPairT), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'fpd_conv_wgrad': (C.c_int, [C.POINTER(WgradT), _vp]),
     'fpd_wgrad_num_partials': (C.c_int, [C.POINTER(WgradT)]),

@@ -119,6 +119,18 @@ typedef struct {
     void* fold_out;
     float* fold_dgamma;
     float* fold_dbeta;
+    /* SECOND 1x1 SOURCE (optional; forward FPD_EPI_PLAIN launches of the streaming 1x1 kernel only): the downsample branch of a
+     * Bottleneck (hourglass.py:45-50) formed in the launch of conv3 instead of a launch of its own.  Exactly the two launches
+     * it replaces, rounding points included:
+     *     skip = round(W2 * x2 + bias2)              (the plain launch: x2 raw, no prologue)
+     *     y    = round((W * a(x) + skip) + bias)     (the launch with residual = skip)
+     * residual must be NULL.  Domain: BF16, C2 == C in {32, 64}, K == 2C, every pointer 16-byte aligned, no pair launch.
+     * fpd_conv_skip_supported() tells whether a launch is served (0: leave x2 NULL and issue the two launches). */
+    const void* x2;        /* [N,H,W,C2] */
+    const void* w2;        /* [K][1][1][C2] */
+    const float* bias2;    /* [K] or NULL */
+    int32_t C2;
+    int32_t _pad2;
 } fpd_conv_t;
 
 /* A whole pre-activation Bottleneck of a FROZEN network in one launch (hourglass.py:32-52 with eval-mode BN, no
@@ -210,6 +222,11 @@ typedef struct {
     float* dbias;          /* wgrad: [K] */
     float* partial;        /* wgrad: slabs of the two-stage reduction (see fpd_wgrad_t), fpd_stem_wgrad_num_partials() of them, or NULL */
     int64_t partial_stride; /* floats between slabs, >= K*147 + K */
+    /* forward, optional (mode FPD_BN_EVAL; FPD_BN_NONE = off): the frozen network's bn1 + ReLU (hourglass.py:173-174) applied in
+     * the epilogue, y = round(relu?(scale * float(round(acc + bias)) + shift)) -- the inner rounding is kept, so y holds the
+     * bits of fpd_stem_forward() followed by FPD_EW_BNRELU_FWD.  out_stats must be NULL.  fpd_stem_act_supported() tells whether
+     * the launch is served (0: leave the mode NONE and issue the elementwise op). */
+    fpd_bn_t act;
 } fpd_stem_t;
 
 /* Elementwise / pooling ops on NHWC tensors.  `op` selects the function:
@@ -372,11 +389,17 @@ int fpd_conv_fused_wgrad_partials(const fpd_conv_t* a);
  * or not: only the dimensions, epilogue and prologue are looked at); 0 otherwise. */
 int fpd_conv_fold_supported(const fpd_conv_t* a);
 int fpd_conv_pair_fold_supported(const fpd_conv_pair_t* p);
+/* 1 if fpd_conv_forward() would serve this launch WITH its second source (x2, w2, bias2, C2 filled in as they will be
+ * launched); 0 otherwise.  Process-wide switch: FPD_FUSE_SKIP=0 / fpd_set_option("conv_skip", 0). */
+int fpd_conv_skip_supported(const fpd_conv_t* a);
 int fpd_conv_pair_fused_wgrad_partials(const fpd_conv_pair_t* p, int32_t* n_a, int32_t* n_b);
 int fpd_conv_wgrad(const fpd_wgrad_t* a, fpd_stream_t stream);
 int fpd_wgrad_num_partials(const fpd_wgrad_t* a);   /* slabs fpd_conv_wgrad writes when a->partial is set */
 int fpd_wgrad_reduce(const fpd_wreduce_entry_t* table_dev, int32_t n_entries, int64_t max_elems, fpd_stream_t stream);
 int fpd_stem_forward(const fpd_stem_t* a, fpd_stream_t stream);
+/* 1 if fpd_stem_forward() would serve this launch WITH the eval-mode BN + ReLU of a->act in its epilogue; 0 otherwise.
+ * Process-wide switch: FPD_STEM_ACT=0 / fpd_set_option("stem_act", 0). */
+int fpd_stem_act_supported(const fpd_stem_t* a);
 int fpd_stem_wgrad(const fpd_stem_t* a, fpd_stream_t stream);
 int fpd_stem_wgrad_num_partials(const fpd_stem_t* a);   /* slabs fpd_stem_wgrad writes when a->partial is set */
 int fpd_elementwise(const fpd_ew_t* a, fpd_stream_t stream);
@@ -569,7 +592,8 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * tiles (default) / 2 whenever in its domain: use of the persistent convolution kernel for big maps (csrc/conv_pp.hip);
  * "conv_pp_blocks" = its persistent blocks per occupancy slot (default 256); "bneck_blocks" / "head_blocks" = grid caps of the
  * persistent fpd_bottleneck_forward / fpd_head_forward kernels (defaults 128 / 160, any n >= 1); "wgrad_tile_only" = 1: fpd_conv_wgrad() fails
- * instead of falling through to the generic kernels when the halo-tile kernel declines a shape (tests).  Returns the
+ * instead of falling through to the generic kernels when the halo-tile kernel declines a shape (tests); "conv_skip" / "stem_act" =
+ * 0: fpd_conv_skip_supported() / fpd_stem_act_supported() answer 0 and such launches are refused (default 1).  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */
 int fpd_set_option(const char* name, int32_t value);
 int fpd_abi_sizeof(const char* struct_name);  /* sizeof of a struct above, -1 if unknown */
