@@ -28,15 +28,7 @@ namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // native vector: typed loads/stores (a uint4 struct
                                                                   // copy is a memcpy, which keeps its array in scratch)
-// compile-time loop: register arrays indexed through it are scalarised at the first SROA run (a `#pragma unroll`
-// loop is unrolled too late for the 512-thread register budget and the array ends up in scratch)
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
+// (register arrays are indexed through static_for: common.h)
 
 #ifdef FPD_BNECK_TIMING          // probe build only (tools/bneck_bench.py): cycle stamps of block 0 at the phase boundaries
 #define STAMP(i) do { if (tid == 0 && bid_in == 0) stamps[i] = clock64(); } while (0)

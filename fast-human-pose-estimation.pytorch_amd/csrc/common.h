@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "fpd_amd.h"
 
@@ -73,6 +74,30 @@ __device__ __forceinline__ int fpd_cut(int i, int n, int d) {
 #endif
     return (int)((long long)i * n / d);
 }
+
+// One or two INDEPENDENT convolutions in one launch (conv_c1 / conv_c3 / conv_pp): nb of the n blocks work on descriptor 1 (isb = 1),
+// spread evenly over the grid (Bresenham) so that whatever part of the grid is resident first serves both in proportion; u = the
+// block's index among those of its descriptor.  nb == 0: a single convolution.
+__device__ __forceinline__ void pair_block(const int bid, const int n, const int nb, int& isb, int& u) {
+    const int fb0 = fpd_cut(bid, nb, n), fb1 = fpd_cut(bid + 1, nb, n);
+    isb = fb1 > fb0 ? 1 : 0;                              // (the descriptor is indexed, not branched on: ONE copy of the body)
+    u = isb ? fb0 : bid - fb0;
+}
+
+// compile-time loop: register arrays indexed through it are scalarised at the first SROA run (a `#pragma unroll`
+// loop is unrolled too late for the 512-thread register budget and the array ends up in scratch)
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (N > 0) {
+        static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// floor(log2 v); v / d by a multiply-high reciprocal (exact for the small indices divided in the tile kernels: v * d < 2^32)
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
+__device__ __forceinline__ int qdiv(int v, unsigned magic) { return (int)__umulhi((unsigned)v, magic); }
+static inline unsigned magic_of(int d) { return (unsigned)((0x100000000ull / (unsigned long long)d) + 1ull); }
 
 __device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float(((uint32_t)u) << 16); }
 // two floats -> packed bf16x2 (lo = a), round to nearest even: one v_cvt_pk_bf16_f32 on gfx950

@@ -29,25 +29,12 @@
 #include <type_traits>
 
 #include "conv_dispatch.h"
+#include "conv_stream.h"
 #include "mfma_frag.h"
 
 namespace {
 
 constexpr int C1_NW = 8;                                 // waves per block = tiles per round
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 c1_unpack(unsigned w) {
-    f32x2 r = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-    return r;
-}
-__device__ __forceinline__ unsigned c1_pack(f32x2 v) { return f2bf_pk(v[0], v[1]); }
-// max of the two signed 16-bit halves with `lo`: lo = 0 is ReLU on a packed bf16 pair, lo = -32768 the identity (conv_pp.hip)
-__device__ __forceinline__ unsigned c1_floor(unsigned w, short lo) {
-    s16x2 a = *reinterpret_cast<const s16x2*>(&w);
-    const s16x2 b = {lo, lo};
-    a = __builtin_elementwise_max(a, b);
-    return *reinterpret_cast<const unsigned*>(&a);
-}
 
 // C, K: channels in / out of THIS launch.  BWD: BNRELU_BWD epilogue (no bias, no residual, no prologue BN).  FOLD (BWD only):
 // the operand is a folded BN-backward apply (fold_x).  WG (BWD only): also the weight / bias gradient of the forward
@@ -134,27 +121,9 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
 #endif
     C1_STAMP();
 
-    // ---- prologue: the table chains (loads -> fp64 -> LDS) on different waves, requested before the long loads ----
-    BnRaw braw;
-    float bias_raw, bias2_raw;                           // (set in the r_bias branch only: a default written here is sunk by hipcc
-                                                          //  behind the other branches' loads, where it needs vmcnt(0) -- see bn_request)
-    const int te = tid - 128, tb = tid - 256;
-    const bool r_bn = has_bn && tid < C;
-    const bool r_fold = fold && tid < C;
-    const bool r_epi = BWD && te >= 0 && te < K;
-    const bool r_bias = tb >= 0 && tb < K;
-    StatRaw fs1, fs2;
-    if (r_bn) bn_request(a.bn, tid, C, braw);
-    else if (r_fold) {
-        bn_request(a.fold_bn, tid, C, braw);
-        stat_request(a.fold_stats, C, 0, tid, fs1);
-        stat_request(a.fold_stats, C, 1, tid, fs2);
-    }
-    else if (r_epi) bn_request(a.epi_bn, te, K, braw);
-    else if (r_bias) {
-        bias_raw = 0.f; if (a.bias != nullptr) bias_raw = a.bias[tb];
-        if constexpr (SKIP) { bias2_raw = 0.f; if (a.bias2 != nullptr) bias2_raw = a.bias2[tb]; }
-    }
+    // ---- prologue: the table chains requested before the long loads (StreamTables, conv_stream.h) ----
+    StreamTables<C, K, BWD, SKIP> tab;
+    tab.request(a, tid, has_bn, fold);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- the tile's vectors: vector i of a lane is 16 bytes at (tile base) + (i * 64 + lane) * 16 -- whole 1 KB lines ----
@@ -208,34 +177,7 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
             if constexpr (BWD || has_res) load_r(t0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (r_bn) {
-            float sc, sh, mu, is;
-            bn_resolve(braw, (double)M, sc, sh, mu, is);
-            s_scale[tid] = sc;
-            s_shift[tid] = sh;
-        } else if (r_fold) {
-            // dy = gamma*is*(g - m1 - xhat*m2), xhat = (u - mu)*is  ==  A g + B u + D   (coefficients formed in fp64, as conv_pp)
-            const double s1 = stat_resolve(braw.s1), s2 = stat_resolve(braw.s2), b1 = stat_resolve(fs1), b2 = stat_resolve(fs2);
-            const double cnt = (double)M, mu = s1 / cnt;
-            double var = s2 / cnt - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const double is = 1.0 / sqrt(var + (double)braw.eps), gi = (double)braw.g * is;
-            const double m1 = b1 / cnt, m2 = b2 / cnt;
-            s_fold[tid] = (float)gi;
-            s_fold[C + tid] = (float)(-gi * is * m2);
-            s_fold[2 * C + tid] = (float)(gi * (mu * is * m2 - m1));
-            if (bi == 0) {                                // the affine parameters' gradients fall out of the two sums
-                if (a.fold_dgamma != nullptr) a.fold_dgamma[tid] = (float)b2;
-                if (a.fold_dbeta != nullptr) a.fold_dbeta[tid] = (float)b1;
-            }
-        } else if (r_epi) {
-            float sc, sh, mu, is;
-            bn_resolve(braw, (double)M, sc, sh, mu, is);
-            s_epi[te] = sc; s_epi[K + te] = sh; s_epi[2 * K + te] = mu; s_epi[3 * K + te] = is;
-        } else if (r_bias) {
-            s_bias[tb] = bias_raw;
-            if constexpr (SKIP) s_bias2[tb] = bias2_raw;
-        }
+        tab.resolve(a, tid, M, bi == 0, s_scale, s_shift, s_fold, s_epi, s_bias, s_bias2);
 #pragma unroll
         for (int i = 0; i < NWV; ++i) {
             const int v = tid + i * 512;
@@ -298,15 +240,15 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
                 unsigned ow[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const f32x2 tt = __builtin_elementwise_fma(f_b[e], c1_unpack(uw[e]), f_d[e]);
-                    ow[e] = c1_pack(__builtin_elementwise_fma(f_a[e], c1_unpack(gw[e]), tt));
+                    const f32x2 tt = __builtin_elementwise_fma(f_b[e], bf2_unpack(uw[e]), f_d[e]);
+                    ow[e] = bf2_pack(__builtin_elementwise_fma(f_a[e], bf2_unpack(gw[e]), tt));
                 }
                 val = make_uint4(ow[0], ow[1], ow[2], ow[3]);
             } else if constexpr (MODE == 1) {
-                val.x = c1_floor(c1_pack(__builtin_elementwise_fma(c1_unpack(val.x), p_sc[0], p_sh[0])), relu_floor);
-                val.y = c1_floor(c1_pack(__builtin_elementwise_fma(c1_unpack(val.y), p_sc[1], p_sh[1])), relu_floor);
-                val.z = c1_floor(c1_pack(__builtin_elementwise_fma(c1_unpack(val.z), p_sc[2], p_sh[2])), relu_floor);
-                val.w = c1_floor(c1_pack(__builtin_elementwise_fma(c1_unpack(val.w), p_sc[3], p_sh[3])), relu_floor);
+                val.x = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.x), p_sc[0], p_sh[0])), relu_floor);
+                val.y = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.y), p_sc[1], p_sh[1])), relu_floor);
+                val.z = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.z), p_sc[2], p_sh[2])), relu_floor);
+                val.w = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.w), p_sc[3], p_sh[3])), relu_floor);
             }
             rx[i] = val;
             *reinterpret_cast<uint4*>(tA + (pxa0 + i * (64 / CV)) * PXA + cch * 16) = val;
@@ -335,14 +277,14 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
                 if constexpr (!BWD) {
                     if constexpr (HASRES) {
                         const uint2 r2 = *reinterpret_cast<const uint2*>(p);
-                        v0 += c1_unpack(r2.x);
-                        v1 += c1_unpack(r2.y);
+                        v0 += bf2_unpack(r2.x);
+                        v1 += bf2_unpack(r2.y);
                     }
                     const f32x4 b4 = *reinterpret_cast<const f32x4*>(sb + kt * 32 + 8 * q + 4 * hh);
                     v0 += f32x2{b4[0], b4[1]};
                     v1 += f32x2{b4[2], b4[3]};
                 }
-                *reinterpret_cast<uint2*>(p) = make_uint2(c1_pack(v0), c1_pack(v1));
+                *reinterpret_cast<uint2*>(p) = make_uint2(bf2_pack(v0), bf2_pack(v1));
             }
         }
     };
@@ -350,21 +292,10 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
     auto perchan = [&](const int t, const bool first, auto statc) {
         constexpr bool STATS = decltype(statc)::value;
         uint4* py = reinterpret_cast<uint4*>(y) + ((size_t)t * 32 * KV + lane);
-        f32x2 e_sc[4], e_sh[4], e_mu[4], e_is[4];         // BWD: epilogue BN of this lane's 8 output channels
-        if constexpr (BWD) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                e_sc[e] = *reinterpret_cast<const f32x2*>(s_epi + kch * 8 + 2 * e);
-                e_sh[e] = *reinterpret_cast<const f32x2*>(s_epi + K + kch * 8 + 2 * e);
-                e_mu[e] = *reinterpret_cast<const f32x2*>(s_epi + 2 * K + kch * 8 + 2 * e);
-                e_is[e] = *reinterpret_cast<const f32x2*>(s_epi + 3 * K + kch * 8 + 2 * e);
-            }
-        }
-        if (!BWD && STATS && first) {
-            // common shift of the wave's shifted sums: the value of its first pixel (every lane of a chunk reads it)
-            const uint4 c4 = *reinterpret_cast<const uint4*>(tO + kch * 16);
-            CS[0] = c1_unpack(c4.x); CS[1] = c1_unpack(c4.y); CS[2] = c1_unpack(c4.z); CS[3] = c1_unpack(c4.w);
-        }
+        EpiTab et;                                        // BWD: epilogue BN of this lane's 8 output channels
+        if constexpr (BWD) epi_tab_read<K>(s_epi, kch, et);
+        if (!BWD && STATS && first)                       // common shift of the wave's shifted sums: the value of its first pixel
+            bf2_unpack4(*reinterpret_cast<const uint4*>(tO + kch * 16), CS);      // (every lane of a chunk reads it)
 #pragma unroll
         for (int i = 0; i < NK; ++i) {
             unsigned char* p = tO + (pxo0 + i * (64 / KV)) * PXO + kch * 16;
@@ -372,37 +303,16 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
             unsigned ow[4] = {o4.x, o4.y, o4.z, o4.w};
             if constexpr (BWD) {
                 const unsigned xw[4] = {rr[i].x, rr[i].y, rr[i].z, rr[i].w};
-                unsigned aw[4];
+                unsigned aw[4];                           // WG: the forward operand a(u) takes the gradient's place in the tile
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const f32x2 xv = c1_unpack(xw[e]);
-                    const f32x2 z = __builtin_elementwise_fma(xv, e_sc[e], e_sh[e]);
-                    // ReLU mask of the forward tensor (it commutes with the rounding), then the two BatchNorm-backward sums of
-                    // the stored (rounded) gradient
-                    const unsigned keep = (z[0] > relu_gate ? 0x0000ffffu : 0u) | (z[1] > relu_gate ? 0xffff0000u : 0u);
-                    ow[e] &= keep;
-                    const f32x2 g = c1_unpack(ow[e]);
-                    F1[e] += g;
-                    F2[e] = __builtin_elementwise_fma(g, (xv - e_mu[e]) * e_is[e], F2[e]);
-                    if constexpr (WG) aw[e] = c1_floor(c1_pack(z), epi_floor);     // the forward operand as the forward convolution staged it
+                    const f32x2 z = epi_bwd_pair(ow[e], xw[e], et, e, relu_gate, F1[e], F2[e]);
+                    if constexpr (WG) aw[e] = bf2_floor(bf2_pack(z), epi_floor);     // as the forward convolution staged it
                 }
                 if constexpr (WG) *reinterpret_cast<uint4*>(p) = make_uint4(aw[0], aw[1], aw[2], aw[3]);
-            } else if constexpr (STATS) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const f32x2 d = c1_unpack(ow[e]) - CS[e];
-                    F1[e] += d;
-                    F2[e] = __builtin_elementwise_fma(d, d, F2[e]);
-                }
-            }
+            } else if constexpr (STATS) epi_fwd_step(ow, CS, F1, F2);
             py[i * 64] = make_uint4(ow[0], ow[1], ow[2], ow[3]);
-            if constexpr (BWD || STATS) {
-                // one vector at a time, its sums formed HERE: hipcc otherwise sinks the statistics arithmetic of all vectors
-                // behind the loop and keeps every unpacked operand alive until then (more registers than the kernel has)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(F1[e]), "+v"(F2[e]));
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            if constexpr (BWD || STATS) epi_sums_fence(F1, F2);
         }
     };
 
@@ -569,66 +479,14 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
         }
     }
 
-    // ---- statistics: one flush per block.  A lane holds fp32 partial sums of 8 channels over its pixels (forward: shifted by
-    //      the wave's common shift; backward {sum dz, sum dz * xhat}); fixed-order fp64 sums per channel, exact limbs out ----
-    if (want_stats) {
-        __syncthreads();                                  // every wave is done with its tiles
-        float* rec = reinterpret_cast<float*>(sT);        // [8 waves][64 lanes][16]
-        float* shf = rec + C1_NW * 64 * 16;               // [8 waves][K]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            *reinterpret_cast<f32x2*>(rec + (wave * 64 + lane) * 16 + 2 * e) = F1[e];
-            *reinterpret_cast<f32x2*>(rec + (wave * 64 + lane) * 16 + 8 + 2 * e) = F2[e];
-        }
-        if (!BWD && lane < KV) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) *reinterpret_cast<f32x2*>(shf + wave * K + lane * 8 + 2 * e) = CS[e];
-        }
-        __syncthreads();
-        fpd_stat_t* st = BWD ? a.epi_stats : a.out_stats;
-        // stage A (all threads): thread (part, which, ch) sums the records of NPW waves in a fixed order in fp64 and un-shifts
-        // them; stage B: the parts in order, one exact pair of limbs per (sum, channel) out.  (One thread per sum over all
-        // eight waves took 6.4 k cycles at the end of every block: stamps, round 6.)
-        constexpr int NPART = 512 / (2 * K) > C1_NW ? C1_NW : 512 / (2 * K);      // 2 (K = 128), 4 (K = 64), 8 (K = 32)
-        constexpr int NPW = C1_NW / NPART;
-        double* s_part = reinterpret_cast<double*>(shf + C1_NW * K);             // [NPART][2 K]
-        {
-            const int part = tid / (2 * K), rem = tid % (2 * K);
-            const int ch = rem % K, which = rem / K;      // which: 0 = first sum, 1 = second
-            const int chunk = ch >> 3, e = ch & 7;
-            if (part < NPART) {
-                double tot = 0.0;
-#pragma unroll
-                for (int q = 0; q < NPW; ++q) {
-                    const int wv = part * NPW + q;
-                    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                    for (int jj = 0; jj < 64 / KV; ++jj) {
-                        const float* rp = rec + (wv * 64 + chunk + KV * jj) * 16;
-                        t1 += (double)rp[e];
-                        t2 += (double)rp[8 + e];
-                    }
-                    if (BWD) tot += which ? t2 : t1;
-                    else {
-                        // tiles wave wv has processed: rounds r of this block with r * 8 + wv < ntile
-                        const int last = (ntile - 1 - wv) >= 0 ? (ntile - 1 - wv) / C1_NW : -1;
-                        const int hi = min(r_end - 1, last);
-                        const int nt = hi >= r_beg ? hi - r_beg + 1 : 0;
-                        const double c = (double)shf[wv * K + ch], nn = 32.0 * nt;
-                        tot += which ? (t2 + 2.0 * c * t1 + nn * c * c) : (t1 + nn * c);
-                    }
-                }
-                s_part[part * 2 * K + rem] = tot;
-            }
-        }
-        __syncthreads();
-        if (tid < 2 * K) {
-            double tot = 0.0;
-#pragma unroll
-            for (int q = 0; q < NPART; ++q) tot += s_part[q * 2 * K + tid];
-            stat_atomic_add(st, K, tid / K, tid % K, tot);
-        }
-    }
+    // ---- statistics: one flush per block (stream_stats_flush, conv_stream.h) ----
+    if (want_stats)
+        stream_stats_flush<C1_NW, K, BWD>(reinterpret_cast<float*>(sT), BWD ? a.epi_stats : a.out_stats, F1, F2, CS, wave, lane, tid, [&](const int wv) {
+            // tiles wave wv has processed: rounds r of this block with r * 8 + wv < ntile
+            const int last = (ntile - 1 - wv) >= 0 ? (ntile - 1 - wv) / C1_NW : -1;
+            const int hi = min(r_end - 1, last);
+            return hi >= r_beg ? hi - r_beg + 1 : 0;
+        });
 #ifdef FPD_C1_TIMING
     C1_STAMP();
     if (lane == 0 && (wave == 0 || wave == 7)) c1_stamp[(wave ? 40 : 0) + 39] = c1_ns;
@@ -651,55 +509,33 @@ __device__ __forceinline__ void c1_body(const fpd_conv_t& a, const int bi, const
 
 // One or two INDEPENDENT convolutions of the same template configuration in one launch (the up- / low-branch Bottleneck
 // convolutions of an hourglass level): blocks [0, nblk[0]) work on descriptor 0, the rest on descriptor 1, spread evenly
-// over the grid (Bresenham) so that whatever part of the grid is resident first serves both in proportion.
+// over the grid (pair_block, common.h).
 struct C1Args { fpd_conv_t c[2]; int nblk[2]; };
 
 template <int C, int K, bool BWD, bool FOLD, bool WG, bool RES, bool SKIP = false>
 __global__ __launch_bounds__(512, 2) void c1_kernel(const C1Args p) {
-    const int bid = blockIdx.x, n = gridDim.x, nb = p.nblk[1];
-    const int fb0 = fpd_cut(bid, nb, n), fb1 = fpd_cut(bid + 1, nb, n);
-    const int isb = fb1 > fb0 ? 1 : 0;
-    const int u = isb ? fb0 : bid - fb0;
+    int isb, u;
+    pair_block(blockIdx.x, gridDim.x, p.nblk[1], isb, u);
     c1_body<C, K, BWD, FOLD, WG, RES, SKIP>(p.c[isb], u, p.nblk[isb]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // FPD_C1: 0 = never, 1 = launches of >= FPD_C1_MIN_PX pixels (default), 2 = whenever the shape is in the domain (tests:
-// fpd_set_option("conv_c1", v)); FPD_C1_BLOCKS: persistent blocks of a launch (default 192 of the 256 CUs, see c1_blocks()).
-int g_c1_mode = -1, g_c1_blocks = -1, g_c1_skip = -1;
-std::atomic<int> g_c1_launches{0};                       // launches this kernel has served (tests: "conv_c1_launches")
-int c1_mode() {
-    if (g_c1_mode < 0) { const char* e = getenv("FPD_C1"); g_c1_mode = e ? atoi(e) : 1; }
-    return g_c1_mode;
-}
+// fpd_set_option("conv_c1", v)); FPD_C1_BLOCKS: persistent blocks of a launch, default 192 of the 256 CUs
+// (192, not 256: a resident block owns most of its CU's LDS, and the frozen teacher's fused Bottlenecks -- 128 blocks of 151 KB on
+//  another stream -- need compute units of their own; r06 sweep inside the step, one box: 160 / 192 / 224 / 256 blocks ->
+//  9.21 / 9.15 / 9.17-9.45 / 9.25 ms)
+EnvOpt g_c1_mode{"FPD_C1", 1}, g_c1_blocks{"FPD_C1_BLOCKS", 192, 1};
 // FPD_FUSE_SKIP (default 1; tests: fpd_set_option("conv_skip", v)): 0 = the second source (fpd_conv_t.x2) is not offered
-int c1_skip() {
-    if (g_c1_skip < 0) { const char* e = getenv("FPD_FUSE_SKIP"); g_c1_skip = e ? atoi(e) : 1; }
-    return g_c1_skip;
-}
-int c1_blocks() {
-    // (192, not 256: a resident block owns most of its CU's LDS, and the frozen teacher's fused Bottlenecks -- 128 blocks of 151 KB on
-    //  another stream -- need compute units of their own; r06 sweep inside the step, one box: 160 / 192 / 224 / 256 blocks ->
-    //  9.21 / 9.15 / 9.17-9.45 / 9.25 ms)
-    if (g_c1_blocks < 0) { const char* e = getenv("FPD_C1_BLOCKS"); g_c1_blocks = e ? atoi(e) : 192; }
-    return g_c1_blocks < 1 ? 1 : g_c1_blocks;
-}
+EnvOpt g_c1_skip{"FPD_FUSE_SKIP", 1};
+std::atomic<int> g_c1_launches{0};                       // launches this kernel has served (tests: "conv_c1_launches")
 // Smallest launch (pixels) the kernel takes in mode 1, forward launches and data gradients apart.  Kernels alone on the small maps
 // (profiles/r06_c1_small_maps.txt): the forward 128 -> 64 wins at every size (7.5 vs 8.9-9.2 us down to 4x4 = 512 pixels), the data
 // gradients with their fused weight gradient lose 1 us to conv_tile's plain data gradient below 32x32 -- but take the weight gradient
 // off the lane.  Inside the step (one box, three interleaved runs each): forward / backward 2048 / 2048 -> 8.763, 8.823, 8.764 ms;
 // 512 / 2048 -> 8.762, 8.760, 8.747; 512 / 8192 -> 8.755, 8.750, 8.768; 512 / 16384 -> 8.796, 8.763, 8.807; the earlier sweep of
 // both together: 32768 / 8192 / 2048 / 512 -> 9.669 / 9.60 / 9.574 / 9.581.
-int c1_min_px() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FPD_C1_MIN_PX"); v = e ? atoi(e) : 512; }
-    return v;
-}
-int c1_min_px_bwd() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FPD_C1_MIN_PX_BWD"); v = e ? atoi(e) : 2048; }
-    return v;
-}
+EnvOpt g_c1_min_px{"FPD_C1_MIN_PX", 512}, g_c1_min_px_bwd{"FPD_C1_MIN_PX_BWD", 2048};
 int c1_fuse_wgrad() { return 1; }
 
 bool c1_chan(int c) { return c == 32 || c == 64 || c == 128; }
@@ -709,7 +545,7 @@ bool c1_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) ==
 // the second source the fields describe (forward C -> 2C, C in {32, 64}: K = 256 is outside c1_chan and stays two launches)
 bool c1_domain(const fpd_conv_t& a, bool fold, bool skip = false) {
     if (skip) {
-        if (c1_skip() == 0 || a.epi != FPD_EPI_PLAIN || a.residual != nullptr || a.x2 == nullptr || a.w2 == nullptr) return false;
+        if (g_c1_skip.get() == 0 || a.epi != FPD_EPI_PLAIN || a.residual != nullptr || a.x2 == nullptr || a.w2 == nullptr) return false;
         if (a.C2 != a.C || a.K != 2 * a.C || a.C > 64 || !c1_chan(a.C)) return false;
         if (!c1_aligned(a.x2) || !c1_aligned(a.w2) || a.y == a.x2) return false;
     }
@@ -739,7 +575,7 @@ struct C1Plan { int na, nb, grid; bool wg; };
 // which grid, and which of the two fusions does it offer.  16 -> 128 and 128 x 128 data gradients are taken only unfolded (no FOLD
 // variant: their folded launch goes on to the next kernel); the fused weight gradient needs a dW tile for every wave.
 bool c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r, C1Plan& pl) {
-    const int mode = c1_mode();
+    const int mode = g_c1_mode.get();
     if (mode == 0 || !c1_domain(a, ask.fold, ask.skip) || (ask.skip && b != nullptr)) return false;
     const bool bwd = a.epi == FPD_EPI_BNRELU_BWD;
     long long px = (long long)a.N * a.H * a.W;
@@ -748,19 +584,9 @@ bool c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& 
         if ((a.residual != nullptr) != (b->residual != nullptr)) return false;      // (the residual is a template parameter)
         px += (long long)b->N * b->H * b->W;
     }
-    if (mode == 1 && px < (bwd ? c1_min_px_bwd() : c1_min_px())) return false;
-    const int ra = c1_rounds(a), rb = b ? c1_rounds(*b) : 0;
-    // blocks under the cap, balanced: every block runs the same number of rounds (512 rounds under a cap of 192 -> 171 blocks of 3,
-    // not 192 blocks of which two thirds run 3 and the rest 2)
-    int total = std::max(1, std::min(c1_blocks(), ra + rb));
-    total = cdiv(ra + rb, cdiv(ra + rb, total));
-    pl.nb = 0;
-    if (b != nullptr) {
-        if (total < 2) return false;
-        pl.nb = std::max(1, std::min(total - 1, (int)((long long)total * rb / (ra + rb))));
-    }
-    pl.na = total - pl.nb;
-    pl.grid = total;
+    if (mode == 1 && px < (bwd ? g_c1_min_px_bwd : g_c1_min_px).get()) return false;
+    if (!fpd_split_blocks(c1_rounds(a), b ? c1_rounds(*b) : 0, b != nullptr, g_c1_blocks.get(), pl.na, pl.nb)) return false;
+    pl.grid = pl.na + pl.nb;
     pl.wg = ask.wg && c1_fuse_wgrad() != 0 && bwd && (a.C / 32) * (a.K / 32) == C1_NW;      // (a pair: same C, K, epilogue)
     r.folds = ask.fold && bwd;
     r.skips = ask.skip;
@@ -820,11 +646,7 @@ int c1_launch_c(const fpd_conv_t& a, const fpd_conv_t* b, const C1Plan& pl, hipS
 
 int fpd_conv_c1_option(int which, int value) {      // which: 0 = mode, 1 = blocks, 3 = second source offered (returns the previous value), 2 = launches served so far
     if (which == 2) return g_c1_launches.load(std::memory_order_relaxed);
-    if (which == 3) { const int prev = c1_skip(); g_c1_skip = value; return prev; }
-    int& g = which == 0 ? g_c1_mode : g_c1_blocks;
-    const int prev = which == 0 ? c1_mode() : c1_blocks();
-    g = value;
-    return prev;
+    return (which == 3 ? g_c1_skip : which == 0 ? g_c1_mode : g_c1_blocks).set(value);
 }
 
 int fpd_conv_c1_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {

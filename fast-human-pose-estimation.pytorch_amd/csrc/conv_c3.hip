@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "conv_dispatch.h"
+#include "conv_stream.h"
 
 namespace {
 
@@ -40,19 +41,7 @@ constexpr int C3_TILE_O = 32 * C3_C * 2;                  // a wave's output til
 constexpr int C3_TABLES = (2 * C3_C + 3 * C3_C + 4 * C3_C + C3_C) * 4;
 constexpr int C3_FLUSH = C3_NW * 64 * 16 * 4 + C3_NW * C3_C * 4 + 8 * 2 * C3_C * 8;
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x2 c3_unpack(unsigned w) {
-    f32x2 r = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-    return r;
-}
-__device__ __forceinline__ unsigned c3_pack(f32x2 v) { return f2bf_pk(v[0], v[1]); }
-__device__ __forceinline__ unsigned c3_floor(unsigned w, short lo) {      // lo = 0: ReLU on a packed bf16 pair, -32768: identity (conv_pp.hip)
-    s16x2 a = *reinterpret_cast<const s16x2*>(&w);
-    const s16x2 b = {lo, lo};
-    a = __builtin_elementwise_max(a, b);
-    return *reinterpret_cast<const unsigned*>(&a);
-}
 // swizzle of the 16-byte chunks of pixel p (128-byte pixels, two per 256-byte bank row): 16 consecutive pixels put one chunk
 // column on 16 different 16-byte slots -- conflict-free b128 reads without padding
 __device__ __forceinline__ int c3_sw(int p) { return (p >> 1) & 7; }
@@ -93,24 +82,9 @@ __device__ __forceinline__ void c3_body(const fpd_conv_t& a, const C3Geo g, cons
     const bool has_bn = !BWD && a.bn.mode != FPD_BN_NONE;
     const bool want_stats = BWD || a.out_stats != nullptr;
 
-    // ---- prologue: table chains requested first, then the weights, then the first strip (conv_c1.hip) ----
-    BnRaw braw;
-    float bias_raw;                                      // (set in the r_bias branch only: a default written here is sunk by hipcc
-                                                          //  behind the other branches' loads, where it needs vmcnt(0) -- see bn_request)
-    const int te = tid - 128, tb = tid - 256;
-    const bool r_bn = has_bn && tid < C;
-    const bool r_fold = fold && tid < C;
-    const bool r_epi = BWD && te >= 0 && te < K;
-    const bool r_bias = tb >= 0 && tb < K;
-    StatRaw fs1, fs2;
-    if (r_bn) bn_request(a.bn, tid, C, braw);
-    else if (r_fold) {
-        bn_request(a.fold_bn, tid, C, braw);
-        stat_request(a.fold_stats, C, 0, tid, fs1);
-        stat_request(a.fold_stats, C, 1, tid, fs2);
-    }
-    else if (r_epi) bn_request(a.epi_bn, te, K, braw);
-    else if (r_bias) { bias_raw = 0.f; if (a.bias != nullptr) bias_raw = a.bias[tb]; }
+    // ---- prologue: table chains requested first (StreamTables, conv_stream.h), then the weights, then the first strip ----
+    StreamTables<C, K, BWD, false> tab;
+    tab.request(a, tid, has_bn, fold);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- the strip's operand vectors: vector v = tid + 512 i of its (RS + 2) rows x W pixels x 8 chunks is 16 bytes at
@@ -152,33 +126,7 @@ __device__ __forceinline__ void c3_body(const fpd_conv_t& a, const C3Geo g, cons
             if constexpr (BWD) load_r(st0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (r_bn) {
-            float sc, sh, mu, is;
-            bn_resolve(braw, (double)M, sc, sh, mu, is);
-            s_scale[tid] = sc;
-            s_shift[tid] = sh;
-        } else if (r_fold) {
-            // dy = gamma*is*(g - m1 - xhat*m2), xhat = (u - mu)*is  ==  A g + B u + D   (coefficients formed in fp64, as conv_pp)
-            const double s1 = stat_resolve(braw.s1), s2 = stat_resolve(braw.s2), b1 = stat_resolve(fs1), b2 = stat_resolve(fs2);
-            const double cnt = (double)M, mu = s1 / cnt;
-            double var = s2 / cnt - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const double is = 1.0 / sqrt(var + (double)braw.eps), gi = (double)braw.g * is;
-            const double m1 = b1 / cnt, m2 = b2 / cnt;
-            s_fold[tid] = (float)gi;
-            s_fold[C + tid] = (float)(-gi * is * m2);
-            s_fold[2 * C + tid] = (float)(gi * (mu * is * m2 - m1));
-            if (bi == 0) {
-                if (a.fold_dgamma != nullptr) a.fold_dgamma[tid] = (float)b2;
-                if (a.fold_dbeta != nullptr) a.fold_dbeta[tid] = (float)b1;
-            }
-        } else if (r_epi) {
-            float sc, sh, mu, is;
-            bn_resolve(braw, (double)M, sc, sh, mu, is);
-            s_epi[te] = sc; s_epi[K + te] = sh; s_epi[2 * K + te] = mu; s_epi[3 * K + te] = is;
-        } else if (r_bias) {
-            s_bias[tb] = bias_raw;
-        }
+        tab.resolve(a, tid, M, bi == 0, s_scale, s_shift, s_fold, s_epi, s_bias, nullptr);
         // weights: global [k][tap][c] -> LDS row tap * 64 + k
 #pragma unroll
         for (int i = 0; i < NWV; ++i) {
@@ -256,17 +204,17 @@ __device__ __forceinline__ void c3_body(const fpd_conv_t& a, const C3Geo g, cons
                     unsigned ow[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const f32x2 tt = __builtin_elementwise_fma(f_b[e], c3_unpack(uw[e]), f_d[e]);
-                        ow[e] = c3_pack(__builtin_elementwise_fma(f_a[e], c3_unpack(gw[e]), tt));
+                        const f32x2 tt = __builtin_elementwise_fma(f_b[e], bf2_unpack(uw[e]), f_d[e]);
+                        ow[e] = bf2_pack(__builtin_elementwise_fma(f_a[e], bf2_unpack(gw[e]), tt));
                     }
                     val = make_uint4(ow[0], ow[1], ow[2], ow[3]);
                     // the evaluated operand is written out once (rows of the strip proper: halo rows belong to the neighbours)
                     if (fo != nullptr && row >= 1 && row <= RS) reinterpret_cast<uint4*>(fo)[v0 + v] = val;
                 } else if constexpr (MODE == 1) {
-                    val.x = c3_floor(c3_pack(__builtin_elementwise_fma(c3_unpack(val.x), p_sc[0], p_sh[0])), relu_floor);
-                    val.y = c3_floor(c3_pack(__builtin_elementwise_fma(c3_unpack(val.y), p_sc[1], p_sh[1])), relu_floor);
-                    val.z = c3_floor(c3_pack(__builtin_elementwise_fma(c3_unpack(val.z), p_sc[2], p_sh[2])), relu_floor);
-                    val.w = c3_floor(c3_pack(__builtin_elementwise_fma(c3_unpack(val.w), p_sc[3], p_sh[3])), relu_floor);
+                    val.x = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.x), p_sc[0], p_sh[0])), relu_floor);
+                    val.y = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.y), p_sc[1], p_sh[1])), relu_floor);
+                    val.z = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.z), p_sc[2], p_sh[2])), relu_floor);
+                    val.w = bf2_floor(bf2_pack(__builtin_elementwise_fma(bf2_unpack(val.w), p_sc[3], p_sh[3])), relu_floor);
                 }
                 // rows outside the image are exactly zero (the filter pads the ACTIVATION)
                 val.x = in ? val.x : 0u; val.y = in ? val.y : 0u; val.z = in ? val.z : 0u; val.w = in ? val.w : 0u;
@@ -286,27 +234,17 @@ __device__ __forceinline__ void c3_body(const fpd_conv_t& a, const C3Geo g, cons
                 v0 += f32x2{b4[0], b4[1]};
                 v1 += f32x2{b4[2], b4[3]};
             }
-            *reinterpret_cast<uint2*>(p) = make_uint2(c3_pack(v0), c3_pack(v1));
+            *reinterpret_cast<uint2*>(p) = make_uint2(bf2_pack(v0), bf2_pack(v1));
         }
     };
     // ---- 4. per channel: whole vectors of 8 channels (vector i: pixel pxo0 + 8 i of the tile, chunk kch) ----
     auto perchan = [&](const int tile, const bool first, auto statc) {
         constexpr bool STATS = decltype(statc)::value;
         uint4* py = reinterpret_cast<uint4*>(y) + ((size_t)tile * 32 * CV + lane);
-        f32x2 e_sc[4], e_sh[4], e_mu[4], e_is[4];
-        if constexpr (BWD) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                e_sc[e] = *reinterpret_cast<const f32x2*>(s_epi + kch * 8 + 2 * e);
-                e_sh[e] = *reinterpret_cast<const f32x2*>(s_epi + K + kch * 8 + 2 * e);
-                e_mu[e] = *reinterpret_cast<const f32x2*>(s_epi + 2 * K + kch * 8 + 2 * e);
-                e_is[e] = *reinterpret_cast<const f32x2*>(s_epi + 3 * K + kch * 8 + 2 * e);
-            }
-        }
-        if (!BWD && STATS && first) {                      // common shift of the wave's shifted sums: its first pixel (sw(0) = 0)
-            const uint4 c4 = *reinterpret_cast<const uint4*>(tO + kch * 16);
-            CS[0] = c3_unpack(c4.x); CS[1] = c3_unpack(c4.y); CS[2] = c3_unpack(c4.z); CS[3] = c3_unpack(c4.w);
-        }
+        EpiTab et;
+        if constexpr (BWD) epi_tab_read<K>(s_epi, kch, et);
+        if (!BWD && STATS && first)                        // common shift of the wave's shifted sums: its first pixel (sw(0) = 0)
+            bf2_unpack4(*reinterpret_cast<const uint4*>(tO + kch * 16), CS);
 #pragma unroll
         for (int i = 0; i < NK; ++i) {
             const int px = pxo0 + 8 * i;
@@ -315,29 +253,10 @@ __device__ __forceinline__ void c3_body(const fpd_conv_t& a, const C3Geo g, cons
             if constexpr (BWD) {
                 const unsigned xw[4] = {rr[i].x, rr[i].y, rr[i].z, rr[i].w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const f32x2 xv = c3_unpack(xw[e]);
-                    const f32x2 z = __builtin_elementwise_fma(xv, e_sc[e], e_sh[e]);
-                    const unsigned keep = (z[0] > relu_gate ? 0x0000ffffu : 0u) | (z[1] > relu_gate ? 0xffff0000u : 0u);
-                    ow[e] &= keep;                         // (the ReLU mask commutes with the rounding)
-                    const f32x2 gq = c3_unpack(ow[e]);
-                    F1[e] += gq;
-                    F2[e] = __builtin_elementwise_fma(gq, (xv - e_mu[e]) * e_is[e], F2[e]);
-                }
-            } else if constexpr (STATS) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const f32x2 d = c3_unpack(ow[e]) - CS[e];
-                    F1[e] += d;
-                    F2[e] = __builtin_elementwise_fma(d, d, F2[e]);
-                }
-            }
+                for (int e = 0; e < 4; ++e) epi_bwd_pair(ow[e], xw[e], et, e, relu_gate, F1[e], F2[e]);
+            } else if constexpr (STATS) epi_fwd_step(ow, CS, F1, F2);
             py[i * 64] = make_uint4(ow[0], ow[1], ow[2], ow[3]);
-            if constexpr (BWD || STATS) {                  // (conv_c1.hip: the sums are formed here, one vector at a time)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(F1[e]), "+v"(F2[e]));
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            if constexpr (BWD || STATS) epi_sums_fence(F1, F2);
         }
     };
 
@@ -376,90 +295,30 @@ __device__ __forceinline__ void c3_body(const fpd_conv_t& a, const C3Geo g, cons
         first = false;
     }
 
-    // ---- statistics: one flush per block (conv_c1.hip) ----
-    if (want_stats) {
-        __syncthreads();
-        float* rec = reinterpret_cast<float*>(sI);        // [8 waves][64 lanes][16]
-        float* shf = rec + C3_NW * 64 * 16;               // [8 waves][K]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            *reinterpret_cast<f32x2*>(rec + (wave * 64 + lane) * 16 + 2 * e) = F1[e];
-            *reinterpret_cast<f32x2*>(rec + (wave * 64 + lane) * 16 + 8 + 2 * e) = F2[e];
-        }
-        if (!BWD && lane < CV) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) *reinterpret_cast<f32x2*>(shf + wave * K + lane * 8 + 2 * e) = CS[e];
-        }
-        __syncthreads();
-        fpd_stat_t* st = BWD ? a.epi_stats : a.out_stats;
-        constexpr int NPART = 4, NPW = C3_NW / NPART;     // 512 threads = 4 parts x 2 sums x 64 channels
-        double* s_part = reinterpret_cast<double*>(shf + C3_NW * K);
-        {
-            const int part = tid / (2 * K), rem = tid % (2 * K);
-            const int ch = rem % K, which = rem / K;
-            const int chunk = ch >> 3, e = ch & 7;
-            double tot = 0.0;
-#pragma unroll
-            for (int qv = 0; qv < NPW; ++qv) {
-                const int wv = part * NPW + qv;
-                double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-                for (int jj = 0; jj < 64 / CV; ++jj) {
-                    const float* rp = rec + (wv * 64 + chunk + CV * jj) * 16;
-                    t1 += (double)rp[e];
-                    t2 += (double)rp[8 + e];
-                }
-                if (BWD) tot += which ? t2 : t1;
-                else {
-                    const double c = (double)shf[wv * K + ch], nn = 32.0 * (s_end - s_beg);      // every wave has a tile in every strip
-                    tot += which ? (t2 + 2.0 * c * t1 + nn * c * c) : (t1 + nn * c);
-                }
-            }
-            s_part[part * 2 * K + rem] = tot;
-        }
-        __syncthreads();
-        if (tid < 2 * K) {
-            double tot = 0.0;
-#pragma unroll
-            for (int qv = 0; qv < NPART; ++qv) tot += s_part[qv * 2 * K + tid];
-            stat_atomic_add(st, K, tid / K, tid % K, tot);
-        }
-    }
+    // ---- statistics: one flush per block; every wave has a tile in every strip ----
+    if (want_stats)
+        stream_stats_flush<C3_NW, K, BWD>(reinterpret_cast<float*>(sI), BWD ? a.epi_stats : a.out_stats, F1, F2, CS, wave, lane, tid,
+                                          [&](int) { return s_end - s_beg; });
 }
 
 // One or two INDEPENDENT convolutions (the up- / low-branch Bottleneck convolutions of an hourglass level) in one launch: the
-// blocks of descriptor 1 are spread evenly over the grid (Bresenham), as in conv_c1 / conv_pp.
+// blocks of descriptor 1 are spread evenly over the grid (pair_block, common.h).
 struct C3Args { fpd_conv_t c[2]; C3Geo g[2]; };
 
 template <bool BWD, bool FOLD>
 __global__ __launch_bounds__(512, 2) void c3_kernel(const C3Args p) {
-    const int bid = blockIdx.x, n = gridDim.x, nb = p.g[1].nblk;
-    const int fb0 = fpd_cut(bid, nb, n), fb1 = fpd_cut(bid + 1, nb, n);
-    const int isb = fb1 > fb0 ? 1 : 0;
-    const int u = isb ? fb0 : bid - fb0;
+    int isb, u;
+    pair_block(blockIdx.x, gridDim.x, p.g[1].nblk, isb, u);
     c3_body<BWD, FOLD>(p.c[isb], p.g[isb], u);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // FPD_C3: 0 = never, 1 = launches of >= FPD_C3_MIN_PX pixels (default), 2 = whenever the shape is in the domain (tests:
-// fpd_set_option("conv_c3", v)); FPD_C3_BLOCKS: persistent blocks of a launch (default 160 of the 256 CUs, see c3_blocks()).
-int g_c3_mode = -1, g_c3_blocks = -1;
+// fpd_set_option("conv_c3", v)); FPD_C3_BLOCKS: persistent blocks of a launch, default 160 of the 256 CUs
+// (160, not 256: the block owns its CU's LDS (157 KB) and the frozen teacher's fused Bottlenecks on the other stream need compute
+//  units of their own; r06 sweep inside the step, one box: 128 / 160 / 192 / 224 / 256 blocks -> 9.02 / 9.07 / 9.08 / 9.21 / 9.25 ms)
+EnvOpt g_c3_mode{"FPD_C3", 1}, g_c3_blocks{"FPD_C3_BLOCKS", 160, 1}, g_c3_min_px{"FPD_C3_MIN_PX", 32768};
 std::atomic<int> g_c3_launches{0};
-int c3_mode() {
-    if (g_c3_mode < 0) { const char* e = getenv("FPD_C3"); g_c3_mode = e ? atoi(e) : 1; }
-    return g_c3_mode;
-}
-int c3_blocks() {
-    // (160, not 256: the block owns its CU's LDS (157 KB) and the frozen teacher's fused Bottlenecks on the other stream need compute
-    //  units of their own; r06 sweep inside the step, one box: 128 / 160 / 192 / 224 / 256 blocks -> 9.02 / 9.07 / 9.08 / 9.21 / 9.25 ms)
-    if (g_c3_blocks < 0) { const char* e = getenv("FPD_C3_BLOCKS"); g_c3_blocks = e ? atoi(e) : 160; }
-    return g_c3_blocks < 1 ? 1 : g_c3_blocks;
-}
-int c3_min_px() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FPD_C3_MIN_PX"); v = e ? atoi(e) : 32768; }
-    return v;
-}
 bool c3_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 bool c3_domain(const fpd_conv_t& a) {
@@ -480,14 +339,14 @@ bool c3_domain(const fpd_conv_t& a) {
     return true;
 }
 bool c3_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
-    const int mode = c3_mode();
+    const int mode = g_c3_mode.get();
     if (mode == 0 || !c3_domain(a)) return false;
     long long px = (long long)a.N * a.H * a.W;
     if (b != nullptr) {
         if (!c3_domain(*b) || a.epi != b->epi) return false;
         px += (long long)b->N * b->H * b->W;
     }
-    return mode != 1 || px >= c3_min_px();
+    return mode != 1 || px >= g_c3_min_px.get();
 }
 C3Geo c3_geo(const fpd_conv_t& a) {
     C3Geo g;
@@ -504,16 +363,8 @@ bool c3_plan(const fpd_conv_t& a, const fpd_conv_t* b, C3Plan& pl) {
     pl.ga = c3_geo(a);
     pl.gb = b ? c3_geo(*b) : pl.ga;
     pl.gb.nblk = 0;
-    const int sa = pl.ga.nstrip, sb = b ? pl.gb.nstrip : 0;
-    // blocks under the cap, balanced: every block walks the same number of strips (conv_c1.hip)
-    int total = std::max(1, std::min(c3_blocks(), sa + sb));
-    total = cdiv(sa + sb, cdiv(sa + sb, total));
-    if (b != nullptr) {
-        if (total < 2) return false;
-        pl.gb.nblk = std::max(1, std::min(total - 1, (int)((long long)total * sb / (sa + sb))));
-    }
-    pl.ga.nblk = total - pl.gb.nblk;
-    pl.grid = total;
+    if (!fpd_split_blocks(pl.ga.nstrip, b ? pl.gb.nstrip : 0, b != nullptr, g_c3_blocks.get(), pl.ga.nblk, pl.gb.nblk)) return false;
+    pl.grid = pl.ga.nblk + pl.gb.nblk;
     const int img = std::max(pl.ga.img_bytes, b ? pl.gb.img_bytes : 0);
     pl.ga.img_bytes = pl.gb.img_bytes = img;
     pl.lds = (size_t)C3_TABLES + C3_WBYTES + std::max(img + C3_NW * C3_TILE_O, C3_FLUSH);
@@ -542,10 +393,7 @@ bool c3_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& 
 
 int fpd_conv_c3_option(int which, int value) {      // which: 0 = mode, 1 = blocks (returns the previous value), 2 = launches served so far
     if (which == 2) return g_c3_launches.load(std::memory_order_relaxed);
-    int& g = which == 0 ? g_c3_mode : g_c3_blocks;
-    const int prev = which == 0 ? c3_mode() : c3_blocks();
-    g = value;
-    return prev;
+    return (which == 0 ? g_c3_mode : g_c3_blocks).set(value);
 }
 int fpd_conv_c3_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {
     C3Plan pl;

@@ -2,7 +2,34 @@
 //
 // Launch convention: 0 = launched, 1 = outside this kernel's domain (the caller tries the next one), < 0 error.
 #pragma once
+#include <algorithm>
+#include <climits>
+#include <cstdlib>
+
 #include "common.h"
+
+// An integer option of a kernel unit: its environment variable is read once, at the first use; fpd_set_option (the units'
+// *_option entry points) overrides it at run time and gets the previous value back.  A value below 0 means "not read yet".
+struct EnvOpt {
+    const char* env; int def, lo = INT_MIN, v = -1;       // variable, default, smallest value get() returns
+    int get() { if (v < 0) { const char* e = getenv(env); v = e ? atoi(e) : def; } return v < lo ? lo : v; }
+    int set(int value) { const int prev = get(); v = value; return prev; }
+};
+
+// Persistent blocks of a streaming launch under a cap, balanced: every block walks the same number of work units (rounds, strips) --
+// 512 rounds under a cap of 192 -> 171 blocks of 3, not 192 blocks of which two thirds run 3 and the rest 2.  A pair launch (ub > 0
+// units of a second convolution) shares the blocks in proportion, at least one each; false: a pair with a single block.
+inline bool fpd_split_blocks(int ua, int ub, bool pair, int cap, int& na, int& nb) {
+    int total = std::max(1, std::min(cap, ua + ub));
+    total = cdiv(ua + ub, cdiv(ua + ub, total));
+    nb = 0;
+    if (pair) {
+        if (total < 2) return false;
+        nb = std::max(1, std::min(total - 1, (int)((long long)total * ub / (ua + ub))));
+    }
+    na = total - nb;
+    return true;
+}
 
 // ---- convolutions: conv_c1 / conv_c3 / conv_pp / conv_tile decide in ONE route function each, which their launch and the
 //      queries of api.hip (fold, slab count) both go through ----

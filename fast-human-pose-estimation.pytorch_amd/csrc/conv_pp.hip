@@ -31,21 +31,18 @@
 
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
+#include "conv_stream.h"
 #include "mfma_frag.h"
 
 namespace {
-
-constexpr int pp_ilog2(int v) { return v <= 1 ? 0 : 1 + pp_ilog2(v / 2); }
 
 struct PPGeo {
     int nrows;                // image rows per tile
     int ntiles;               // pixel tiles of this convolution
     int nblk;                 // tile ranges (persistent blocks per channel slab) working on it
     int region;               // bytes of the LDS region holding the operand image / the epilogue staging tiles, multiple of 16
-    unsigned mW, mWV, mH;     // multiply-high reciprocals of W, W * (C / 8), H
+    unsigned mW, mWV, mH;     // multiply-high reciprocals of W, W * (C / 8), H (magic_of / qdiv, common.h)
 };
-__device__ __forceinline__ int pp_qdiv(int v, unsigned magic) { return (int)__umulhi((unsigned)v, magic); }
-static inline unsigned pp_magic(int d) { return (unsigned)((0x100000000ull / (unsigned long long)d) + 1ull); }
 
 // launder a value: everything derived from it is recomputed where it is used instead of being hoisted out of the tile loop
 // and kept in registers for the whole kernel (the register budget bounds this kernel, not a few VALU operations)
@@ -54,29 +51,8 @@ __device__ __forceinline__ int pp_fresh(int v) {
     return v;
 }
 
-// Two bf16 of a dword as two floats and back: the forward arithmetic below is written on PAIRS (v_pk_fma_f32 / v_pk_add_f32 /
-// v_pk_mul_f32, v_pk_max_i16 on the packed result) -- the same operation per element in the same order as the scalar form, so the
-// same bits, at fewer vector instructions (r04 ISA count of the 1x1 128->64 forward tile loop: 513 -> 406 per tile and wave,
-// against 8 MFMAs).  Measured (r04, interleaved A/B + per-shape trace A/B): 2-4 % on the 1x1 forward launches in isolation, nothing
-// on the step -- the tile loop is bound by its barriers and LDS round trips, not by VALU issue.  The BN-backward epilogue stays
-// scalar: its packed form was 2-7 % slower on the +wgrad +fold kernels (more registers, longer dependent chains).
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 bf2_unpack(unsigned w) {
-    f32x2 r = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-    return r;
-}
-__device__ __forceinline__ unsigned bf2_pack(f32x2 v) { return f2bf_pk(v[0], v[1]); }
-// max of the two signed 16-bit halves with `lo` in both: lo = 0 is ReLU on a packed bf16 pair (a negative bf16 is a negative
-// int16; rounding is monotonic and keeps the sign, so relu(round(t)) == round(relu(t))), lo = -32768 is the identity.
-// Not the bits of the scalar fmaxf path in two corners: -0.0 becomes +0.0 (equal as an MFMA operand and in
-// every sum), and a NaN survives with its sign bit clear / becomes 0 with it set, where fmaxf(NaN, 0) = 0 -- a NaN activation
-// means the step has diverged either way; the cross-kernel bit tests use finite inputs.
-__device__ __forceinline__ unsigned bf2_floor(unsigned w, short lo) {
-    s16x2 a = *reinterpret_cast<const s16x2*>(&w);
-    const s16x2 b = {lo, lo};
-    a = __builtin_elementwise_max(a, b);
-    return *reinterpret_cast<const unsigned*>(&a);
-}
+// (the forward arithmetic below is written on PAIRS of bf16 -- bf2_unpack / bf2_pack / bf2_floor, conv_stream.h; the BN-backward
+//  epilogue stays scalar)
 
 #ifdef FPD_PP_TIMING      // probe build only (tools/probes): cycle stamps of two blocks at the phase boundaries, printed by the kernel
 #define PP_STAMP() do { if (tid == 0 && s_ns < 100) s_stamp[s_ns++] = clock64(); } while (0)
@@ -90,7 +66,7 @@ __device__ __forceinline__ unsigned bf2_floor(unsigned w, short lo) {
 // the forward operand a(u) = relu?(bn(u)) the epilogue evaluates for its ReLU mask -- both through transposing LDS reads.
 template <int R, int C, int KH, bool BWD, bool WG>
 __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo geo, const int bi, const int n0) {
-    constexpr int RS = R * R, KP = 32 * KH, PXW = 8 / KH, CPR = C / 8, LOG_CPR = pp_ilog2(CPR), KS = C / 16;
+    constexpr int RS = R * R, KP = 32 * KH, PXW = 8 / KH, CPR = C / 8, LOG_CPR = ilog2(CPR), KS = C / 16;
     constexpr int LDA = C * 2 + 16;                       // operand-image pixel pitch in BYTES (16 B pad: conflict-free b128 reads)
     constexpr int LDST = 32 * 4 + 16;                     // pitch of a wave's [32 px][32 ch] fp32 staging tile
     constexpr int NVH = 4;                                // operand vectors per thread and tile (host guarantees the fit)
@@ -178,7 +154,7 @@ __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo ge
         for (int i = 0; i < NVH; ++i) {
             if (i < nvh) {
                 const int v = min(tl + i * 512, nvtot - 1);
-                const int hr = pp_qdiv(v, geo.mWV);
+                const int hr = qdiv(v, geo.mWV);
                 const int j = (v - hr * WV) >> LOG_CPR;
                 const int g = g0 + hr;
                 const int gc = min(max(g, 0), GR - 1);
@@ -229,7 +205,7 @@ __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo ge
                 const int vc = min(v, nvtot - 1);
                 int hr, j;
                 if constexpr (R == 1) { hr = 0; j = vc >> LOG_CPR; }        // (pixel of the tile: rows are contiguous without a halo)
-                else { hr = pp_qdiv(vc, geo.mWV); j = (vc - hr * WV) >> LOG_CPR; }
+                else { hr = qdiv(vc, geo.mWV); j = (vc - hr * WV) >> LOG_CPR; }
                 uint4 val = rh[i];
                 if (BWD && fold) {
                     float g[8], u[8];
@@ -316,20 +292,7 @@ __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo ge
             s_scale[tid] = sc;
             s_shift[tid] = sh;
         } else if (r_fold) {
-            // dy = gamma*is*(g - m1 - xhat*m2), xhat = (u - mu)*is  ==  A g + B u + D   (coefficients formed in fp64)
-            const double s1 = stat_resolve(braw.s1), s2 = stat_resolve(braw.s2), b1 = stat_resolve(fs1), b2 = stat_resolve(fs2);
-            const double cnt = (double)M, mu = s1 / cnt;
-            double var = s2 / cnt - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const double is = 1.0 / sqrt(var + (double)braw.eps), gi = (double)braw.g * is;
-            const double m1 = b1 / cnt, m2 = b2 / cnt;
-            s_fold[tid] = (float)gi;
-            s_fold[C + tid] = (float)(-gi * is * m2);
-            s_fold[2 * C + tid] = (float)(gi * (mu * is * m2 - m1));
-            if (bi == 0 && n0 == 0) {                     // the affine parameters' gradients fall out of the two sums
-                if (a.fold_dgamma != nullptr) a.fold_dgamma[tid] = (float)b2;
-                if (a.fold_dbeta != nullptr) a.fold_dbeta[tid] = (float)b1;
-            }
+            fold_coef(a, braw, fs1, fs2, (double)M, s_fold, C, tid, bi == 0 && n0 == 0);      // (conv_stream.h)
         } else if (r_epi) {
             float sc = 0.f, sh = 0.f, mu = 0.f, is = 0.f;
             if (n0 + te < K) bn_resolve(braw, (double)M, sc, sh, mu, is);
@@ -355,7 +318,7 @@ __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo ge
 
     // ---- per-lane MFMA addressing ----
     const int ml = wq * 32 + l31;                         // pixel of the tile this lane feeds (second MFMA operand)
-    const int ti = pp_qdiv(ml, geo.mW), tj = ml - ti * W;
+    const int ti = qdiv(ml, geo.mW), tj = ml - ti * W;
     int ab[3];
     auto tile_addr = [&](int tile) {
         if constexpr (R == 1) {                           // pixel ml of the tile sits at image pixel ml
@@ -364,7 +327,7 @@ __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo ge
             return;
         }
         const int g = tile * nrows + ti;
-        const int p = g - pp_qdiv(g, geo.mH) * H;
+        const int p = g - qdiv(g, geo.mH) * H;
         const bool live = g < GR && ml < TPX;
         const int zp = zero_px * LDA;
         if (R == 3) {
@@ -695,8 +658,7 @@ __device__ __forceinline__ void conv_pp_body(const fpd_conv_t& a, const PPGeo ge
 
 // One or two INDEPENDENT convolutions of the same template configuration (the up-/low-branch Bottleneck convolutions of an
 // hourglass level) in one launch.  A convolution owns nblk tile ranges x ks channel slabs = nblk * ks blocks ("units"); the
-// units of `b` are spread evenly over the grid (Bresenham), so that whatever subset of the grid is resident first serves both
-// in proportion.  gb.nblk == 0: single convolution.  Unit u -> (range, slab): the slabs of one range are 8 block ids apart,
+// units of `b` are spread evenly over the grid (pair_block, common.h).  gb.nblk == 0: single convolution.  Unit u -> (range, slab): the slabs of one range are 8 block ids apart,
 // i.e. on the same XCD.
 struct PPArgs { fpd_conv_t c[2]; PPGeo g[2]; int ks; };
 
@@ -704,9 +666,11 @@ struct PPArgs { fpd_conv_t c[2]; PPGeo g[2]; int ks; };
 // does not without spilling the operand prefetch to scratch, so those kernels take the 256-register budget and one block per CU.
 template <int R, int C, int KH, bool BWD, bool WG>
 __global__ __launch_bounds__(512, BWD ? 2 : 4) void conv_pp_kernel(const PPArgs p) {
+    // (pair_block of common.h, kept as this kernel's own text: through the shared function hipcc schedules the 3x3 data gradients' MFMA
+    //  loop with two more waits)
     const int bid = blockIdx.x, n = gridDim.x, ks = p.ks, nb = p.g[1].nblk * ks;
     const int fb0 = fpd_cut(bid, nb, n), fb1 = fpd_cut(bid + 1, nb, n);
-    const int isb = fb1 > fb0 ? 1 : 0;                    // (the descriptor is indexed, not branched on: ONE copy of the body)
+    const int isb = fb1 > fb0 ? 1 : 0;
     const int u = isb ? fb0 : bid - fb0;
     const int nr = p.g[isb].nblk;
     int range, slab;
@@ -723,22 +687,10 @@ constexpr size_t PP_LDS_MAX = 160 * 1024;
 // hold, at most 2 -- r03 sweep inside the pipelined step, one box: 64/96/128/256 x 2 -> 12.38/11.41/11.00/11.01 ms, 128/192/256 x 1
 // -> 11.35/11.12/11.03; threshold 512/256/128 tiles -> 11.00/10.79/10.78; conv_tile only: 11.50).  mode / blocks can be changed
 // at run time through fpd_set_option("conv_pp" / "conv_pp_blocks", v) (tests drive small shapes through the kernel that way).
-static int g_pp_mode = -1, g_pp_blocks = -1;
-static int pp_mode() {
-    if (g_pp_mode < 0) { const char* e = getenv("FPD_CONV_PP"); g_pp_mode = e ? atoi(e) : 1; }
-    return g_pp_mode;
-}
-static int pp_blocks() {
-    if (g_pp_blocks < 0) { const char* e = getenv("FPD_CONV_PP_BLOCKS"); g_pp_blocks = e ? atoi(e) : 256; }
-    return g_pp_blocks < 1 ? 1 : g_pp_blocks;
-}
-static int pp_min_tiles() {  // FPD_CONV_PP_MIN_TILES: smallest launch (pixel tiles) the kernel takes in mode 1
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FPD_CONV_PP_MIN_TILES"); v = e ? atoi(e) : 256; }
-    return v;
-}
+EnvOpt g_pp_mode{"FPD_CONV_PP", 1}, g_pp_blocks{"FPD_CONV_PP_BLOCKS", 256, 1};
+EnvOpt g_pp_min_tiles{"FPD_CONV_PP_MIN_TILES", 256};      // smallest launch (pixel tiles) the kernel takes in mode 1
 static int pp_occ_cap() { return 2; }        // resident blocks per CU the forward grids are sized for (FPD_CONV_PP_OCC of rounds 3-5)
-static int pp_blocks_bwd() { return pp_blocks(); }      // data-gradient kernels: one block per CU, same count (128 / 192 / 256 / 384 -> 10.33 / 10.22 / 10.08 / 10.42 ms, round 4)
+static int pp_blocks_bwd() { return g_pp_blocks.get(); }      // data-gradient kernels: one block per CU, same count (128 / 192 / 256 / 384 -> 10.33 / 10.22 / 10.08 / 10.42 ms, round 4)
 static int pp_fuse_wgrad() { return 1; }      // 1x1 data gradients also form their weight gradient
 
 static int pp_tile_px(const fpd_conv_t& a) { return a.K > 32 ? 128 : 256; }
@@ -770,9 +722,9 @@ static PPGeo pp_geo(const fpd_conv_t& a) {
     g.nblk = 0;
     const int hrows = g.nrows + a.R - 1, WP = a.W + a.R - 1;
     g.region = std::max((hrows * WP + 4) * LDA, 8 * 32 * LDST);
-    g.mW = pp_magic(a.W);
-    g.mWV = pp_magic(a.W * (a.C / 8));
-    g.mH = pp_magic(a.H);
+    g.mW = magic_of(a.W);
+    g.mWV = magic_of(a.W * (a.C / 8));
+    g.mH = magic_of(a.H);
     return g;
 }
 
@@ -806,7 +758,7 @@ static bool pp_plan(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, PPPla
     const int occ = bwd ? 1 : std::max(1, std::min(pp_occ_cap(), (int)(PP_LDS_MAX / pl.lds)));
     pl.ks = cdiv(a.K, 64);                                 // channel slabs of <= 64 (K = 128: two blocks per tile range)
     // tile ranges: ks blocks per range, every block should own at least two tiles
-    int ranges = std::max(1, std::min((bwd ? pp_blocks_bwd() : pp_blocks()) * occ / pl.ks, total / 2));
+    int ranges = std::max(1, std::min((bwd ? pp_blocks_bwd() : g_pp_blocks.get()) * occ / pl.ks, total / 2));
     if (b != nullptr) {
         if (ranges < 2) return false;
         pl.gb.nblk = std::max(1, std::min(ranges - 1, (int)((long long)ranges * pl.gb.ntiles / total)));
@@ -839,14 +791,14 @@ static int pp_launch_c(const fpd_conv_t& a, const fpd_conv_t* b, const PPPlan& p
 }
 
 static bool pp_takes(const fpd_conv_t& a, const fpd_conv_t* b) {
-    const int mode = pp_mode();
+    const int mode = g_pp_mode.get();
     if (mode == 0 || !pp_domain(a)) return false;
     int tiles = pp_tiles(a);
     if (b != nullptr) {
         if (!pp_domain(*b) || a.K != b->K || a.C != b->C || a.R != b->R || a.epi != b->epi) return false;
         tiles += pp_tiles(*b);
     }
-    return mode != 1 || tiles >= pp_min_tiles();
+    return mode != 1 || tiles >= g_pp_min_tiles.get();
 }
 
 // The ONE decision of this unit, for the launch and for the queries.  A BNRELU_BWD data gradient without a prologue BN evaluates
@@ -866,10 +818,7 @@ static bool pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, Conv
 }  // namespace
 
 int fpd_conv_pp_option(int which, int value) {     // which: 0 = mode, 1 = blocks; returns the previous value
-    int& g = which == 0 ? g_pp_mode : g_pp_blocks;
-    const int prev = which == 0 ? pp_mode() : pp_blocks();
-    g = value;
-    return prev;
+    return (which == 0 ? g_pp_mode : g_pp_blocks).set(value);
 }
 
 int fpd_conv_pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r) {

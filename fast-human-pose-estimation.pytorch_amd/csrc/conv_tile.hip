@@ -59,13 +59,8 @@ struct TapMma<float> {
     }
 };
 
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
-
-// tile geometry of one convolution: rows per tile and the multiply-high reciprocals of W and W*VPR (exact quotients for the
-// small indices divided here: v * d < 2^32)
+// tile geometry of one convolution: rows per tile and the multiply-high reciprocals of W and W*VPR (magic_of / qdiv, common.h)
 struct TileGeo { int nrows; unsigned mW, mWV; };
-__device__ __forceinline__ int qdiv(int v, unsigned magic) { return (int)__umulhi((unsigned)v, magic); }
-static inline unsigned magic_of(int d) { return (unsigned)((0x100000000ull / (unsigned long long)d) + 1ull); }
 
 // One 128-pixel x 32*TN-channel tile of convolution `a`; (bx, by) = tile coordinates.  Shared by the single-conv
 // kernel and the pair kernel (two independent convolutions in one launch).
@@ -297,8 +292,9 @@ __device__ __forceinline__ void conv_tile_body(const fpd_conv_t& a, const TileGe
     bn_fill(a.bn, C, (double)M, s_scale, s_shift);
     TILE_STAMP();                        // 3: BN tables
     if (FOLD && fold) {
-        // dy = gamma*is*(g - m1 - xhat*m2), xhat = (u - mu)*is  ==  A g + B u + D   (coefficients formed in fp64);
-        // the upper half of the block does it while the lower half fills the epilogue tables
+        // the coefficients A, B, D of fold_coef (conv_stream.h), as this kernel's own text: through the shared function hipcc allocates
+        // the FOLD variants differently (more scratch, other MFMA loops); the upper half of the block does it while the lower half
+        // fills the epilogue tables
         for (int c = tid - 128; c >= 0 && c < C; c += 128) {
             BnRaw r;
             bn_request(a.fold_bn, c, C, r);

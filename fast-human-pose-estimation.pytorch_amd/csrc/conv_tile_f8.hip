@@ -31,10 +31,7 @@ __device__ __forceinline__ uint2 pack_f8x8(const float* f) {
     return make_uint2((unsigned)lo, (unsigned)hi);
 }
 
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
-struct TileGeo8 { int nrows; unsigned mW, mWV; };
-__device__ __forceinline__ int qdiv(int v, unsigned magic) { return (int)__umulhi((unsigned)v, magic); }
-static inline unsigned magic_of(int d) { return (unsigned)((0x100000000ull / (unsigned long long)d) + 1ull); }
+struct TileGeo8 { int nrows; unsigned mW, mWV; };      // (reciprocals: magic_of / qdiv, common.h)
 
 // fp32 master weights [K][RSC] -> e4m3 [K][RSC] + scale[K]: one block per (convolution, output channel)
 __global__ __launch_bounds__(256) void wquant_kernel(const fpd_wquant_entry_t* table) {

@@ -19,14 +19,6 @@ namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
 // folded tables: sc[C], sh'[C] = sh + sc*b_fc | b_score[32] (zero padded) | b_out[C] = b_fc_ + b_score_
 template <int C>
 __device__ __forceinline__ void head_tables(const fpd_head_t& a, float* out, int tid, int nthreads) {
