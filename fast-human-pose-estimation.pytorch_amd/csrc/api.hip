@@ -93,6 +93,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t);
+    SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
 #undef SZ
     return -1;
 }
@@ -469,6 +470,34 @@ int fpd_warp_affine(const fpd_warp_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0, "warp_affine: bad dims");
     for (int c = 0; c < 3; ++c) FPD_REQUIRE(a->std[c] != 0.f, "warp_affine: std[%d] == 0", c);
     int rc = fpd_warp_affine_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_augment_params(const fpd_augment_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->idx && a->crop && a->trans && a->joints && a->vis && a->center && a->scale && a->rotation && a->flipped,
+                "augment_params: null pointer");
+    const fpd_aug_db_t& d = a->db;
+    FPD_REQUIRE(d.images && d.joints && d.vis && d.center && d.scale && d.flip_src && d.upper, "augment_params: null database pointer");
+    FPD_REQUIRE(d.N > 0 && d.J > 0 && d.J <= 64, "augment_params: bad database dims (N=%d, J=%d; J <= 64)", d.N, d.J);
+    FPD_REQUIRE(a->B > 0 && a->out_w > 0 && a->out_h > 0 && a->idx_stride > 0, "augment_params: bad dims");
+    FPD_REQUIRE(!a->is_train || (a->draws && a->draw_stride >= 6), "augment_params: training mode needs a draw table of >= 6 columns");
+    FPD_REQUIRE(d.aspect_ratio > 0 && d.pixel_std > 0 && a->sf >= 0 && a->rf >= 0, "augment_params: bad scalars");
+    int rc = fpd_augment_params_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_warp_affine_aug(const fpd_warp_aug_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->images && a->crop && a->out, "warp_affine_aug: null pointer");
+    FPD_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0 && a->N > 0, "warp_affine_aug: bad dims");
+    for (int c = 0; c < 3; ++c) FPD_REQUIRE(a->std[c] != 0.f, "warp_affine_aug: std[%d] == 0", c);
+    int rc = fpd_warp_affine_aug_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_render_targets_w(const fpd_targets_w_t* w, fpd_stream_t stream) {
+    FPD_REQUIRE(w, "render_targets_w: null pointer");
+    const fpd_targets_t* a = &w->t;
+    FPD_REQUIRE(a->joints && a->vis && a->g && a->target && a->weight, "render_targets_w: null pointer");
+    FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0 && a->patch > 0 && (a->patch & 1), "render_targets_w: bad dims");
+    FPD_REQUIRE(a->stride_x > 0 && a->stride_y > 0, "render_targets_w: bad stride");
+    int rc = fpd_render_targets_w_launch(*w, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 

@@ -77,7 +77,11 @@ def _defaults():
                   'EXTRA': {'NUM_FEATURES': 256, 'NUM_STACKS': 8, 'NUM_BLOCKS': 1}},
         'LOSS': {'USE_OHKM': False, 'TOPK': 8, 'USE_TARGET_WEIGHT': True, 'USE_DIFFERENT_JOINTS_WEIGHT': False},
         'DATASET': {'ROOT': '', 'DATASET': 'synthetic', 'TRAIN_SET': 'train', 'TEST_SET': 'valid', 'NUM_SAMPLES': 256,
-                    'NUM_VALID_SAMPLES': 64},
+                    'NUM_VALID_SAMPLES': 64,
+                    # training augmentation (default.py:66-71), read by DATASET.DATASET synthetic_aug; NUM_SCENES: size of its
+                    # device-resident database
+                    'FLIP': True, 'SCALE_FACTOR': 0.25, 'ROT_FACTOR': 30, 'PROB_HALF_BODY': 0.0, 'NUM_JOINTS_HALF_BODY': 8,
+                    'NUM_SCENES': 64},
         'TRAIN': {'LR_FACTOR': 0.1, 'LR_STEP': [90, 120], 'LR': 0.00025, 'OPTIMIZER': 'adam', 'MOMENTUM': 0.9, 'WD': 0.0001,
                   'NESTEROV': False, 'GAMMA1': 0.99, 'GAMMA2': 0.0, 'BEGIN_EPOCH': 0, 'END_EPOCH': 140, 'RESUME': False,
                   'CHECKPOINT': '', 'BATCH_SIZE_PER_GPU': 32, 'SHUFFLE': True},

@@ -133,6 +133,35 @@ class WarpT(C.Structure):
                 ('out', _vp)]
 
 
+class AugImgT(C.Structure):
+    _fields_ = [('img', _vp), ('h', _i32), ('w', _i32), ('row_bytes', _i64)]
+
+
+class AugDbT(C.Structure):
+    _fields_ = [('N', _i32), ('J', _i32), ('box_f32', _i32), ('_pad', _i32), ('images', _vp), ('joints', _vp), ('vis', _vp),
+                ('center', _vp), ('scale', _vp), ('flip_src', _vp), ('upper', _vp), ('aspect_ratio', _f64), ('pixel_std', _f64)]
+
+
+class AugCropT(C.Structure):
+    _fields_ = [('src', _i32), ('flip', _i32), ('minv', _f64 * 6)]
+
+
+class AugmentT(C.Structure):
+    _fields_ = [('db', AugDbT), ('B', _i32), ('is_train', _i32), ('flip', _i32), ('num_joints_half_body', _i32),
+                ('idx_stride', _i32), ('draw_stride', _i32), ('out_w', _i32), ('out_h', _i32), ('sf', _f64), ('rf', _f64),
+                ('prob_half_body', _f64), ('idx', _vp), ('draws', _vp), ('crop', _vp), ('trans', _vp), ('joints', _vp),
+                ('vis', _vp), ('center', _vp), ('scale', _vp), ('rotation', _vp), ('flipped', _vp)]
+
+
+class WarpAugT(C.Structure):
+    _fields_ = [('B', _i32), ('H', _i32), ('W', _i32), ('N', _i32), ('images', _vp), ('crop', _vp), ('mean', _f32 * 3),
+                ('std', _f32 * 3), ('out', _vp)]
+
+
+class TargetsWT(C.Structure):
+    _fields_ = [('t', TargetsT), ('joints_weight', _vp)]
+
+
 class LossT(C.Structure):
     _fields_ = [('B', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('S', _i32), ('dtype', _i32),
                 ('target_nchw', _i32), ('alpha', _f32), ('out', _vp * MAX_STACKS), ('dout', _vp * MAX_STACKS),
@@ -183,7 +212,9 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_bnupd_entry_t': BnupdEntryT, 'fpd_memset_t': MemsetT, 'fpd_table_t': TableT,
             'fpd_wreduce_entry_t': WreduceEntryT, 'fpd_bneck_t': BneckT, 'fpd_conv_pair_t': ConvPairT, 'fpd_bneck_pair_t': BneckPairT, 'fpd_ew_pair_t': EwPairT, 'fpd_pck_t': PckT, 'fpd_head_t': HeadT, 'fpd_affsum_t': AffsumT, 'fpd_layout_t': LayoutT,
             'fpd_conv_f8_t': ConvF8T, 'fpd_wquant_entry_t': WquantEntryT, 'fpd_flipmerge_t': FlipMergeT, 'fpd_finalpreds_t': FinalPredsT, 'fpd_targets_t': TargetsT,
-            'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT}
+            'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
+            'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
+            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -218,6 +249,9 @@ SYMBOLS = {
     'fpd_final_preds': (C.c_int, [C.POINTER(FinalPredsT), _vp]),
     'fpd_render_targets': (C.c_int, [C.POINTER(TargetsT), _vp]),
     'fpd_warp_affine': (C.c_int, [C.POINTER(WarpT), _vp]),
+    'fpd_augment_params': (C.c_int, [C.POINTER(AugmentT), _vp]),
+    'fpd_warp_affine_aug': (C.c_int, [C.POINTER(WarpAugT), _vp]),
+    'fpd_render_targets_w': (C.c_int, [C.POINTER(TargetsWT), _vp]),
     'fpd_head_forward': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_head_fold': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_loss': (C.c_int, [C.POINTER(LossT), _vp]),

@@ -544,6 +544,77 @@ typedef struct {
 } fpd_warp_t;
 int fpd_warp_affine(const fpd_warp_t* a, fpd_stream_t stream);
 
+/* ---- on-device training augmentation (JointsDataset.py:137-179, utils/transforms.py:32-110) ----
+ * Everything __getitem__ does after the image is decoded, as three launches per batch with no host work per sample:
+ * fpd_augment_params -> fpd_warp_affine_aug -> fpd_render_targets_w.  The dataset lives on the device (fpd_aug_db_t). */
+typedef struct {
+    const uint8_t* img;            /* [h][w][3] interleaved, anywhere in one packed device buffer */
+    int32_t h, w;
+    int64_t row_bytes;
+} fpd_aug_img_t;
+typedef struct {
+    int32_t N, J;                  /* images / joints per image (J <= 64) */
+    int32_t box_f32, _pad;         /* 1: center/scale hold float32 values (COCO's _box2cs); numpy then keeps the flipped
+                                      centre and the validation-mode scale*200 in float32 */
+    const fpd_aug_img_t* images;   /* [N] */
+    const double* joints;          /* [N,J,3] image pixels */
+    const float* vis;              /* [N,J] joints_3d_vis[:, 0] */
+    const double* center;          /* [N,2] */
+    const double* scale;           /* [N,2] */
+    const int32_t* flip_src;       /* [J]: joint that ends up at j after fliplr_joints' sequential pair swaps */
+    const int32_t* upper;          /* [J]: 1 = joint id in upper_body_ids */
+    double aspect_ratio;           /* image width / height (a Python float in the reference: enters float32 arithmetic) */
+    double pixel_std;              /* 200 */
+} fpd_aug_db_t;
+/* What fpd_augment_params hands to the crop, per sample. */
+typedef struct {
+    int32_t src;                   /* index into fpd_aug_db_t.images; -1 = index out of range (the crop reads nothing) */
+    int32_t flip;                  /* 1: tap column X reads source column w-1-X (the mirrored image, not a composed matrix) */
+    double minv[6];                /* DST->SRC map, invertAffineTransform of `trans` */
+} fpd_aug_crop_t;
+/* Draw table columns (what the reference pulls from np.random / random per sample, in its order of use):
+ *   0 u_half  rand()  < prob_half_body          1 n_half  randn() < 0.5: upper body
+ *   2 n_scale randn() scale jitter              3 n_rot   randn() rotation jitter
+ *   4 u_rot   random() <= 0.6: rotate           5 u_flip  random() <= 0.5: flip
+ * idx / draws are strided so that both can live in one [B,8]-double staging row (int32 index in the first word). */
+typedef struct {
+    fpd_aug_db_t db;
+    int32_t B, is_train;           /* is_train 0: draws ignored, r = 0, no flip, no half-body */
+    int32_t flip, num_joints_half_body;
+    int32_t idx_stride, draw_stride;    /* in int32 / in doubles */
+    int32_t out_w, out_h;          /* cfg.MODEL.IMAGE_SIZE */
+    double sf, rf, prob_half_body;
+    const int32_t* idx;            /* [B] sample -> image */
+    const double* draws;           /* [B][>=6] */
+    fpd_aug_crop_t* crop;          /* [B] */
+    double* trans;                 /* [B,2,3] SRC->DST, get_affine_transform(c, s, r, image_size) */
+    double* joints;                /* [B,J,3] transformed (visible joints), third column 0 */
+    float* vis;                    /* [B,J] after the flip's exchange */
+    double* center;                /* [B,2] */
+    double* scale;                 /* [B,2] */
+    double* rotation;              /* [B] degrees */
+    int32_t* flipped;              /* [B] */
+} fpd_augment_t;
+int fpd_augment_params(const fpd_augment_t* a, fpd_stream_t stream);
+
+/* fpd_warp_affine reading its per-sample source, matrix and flip flag from what fpd_augment_params wrote. */
+typedef struct {
+    int32_t B, H, W, N;            /* output [B,3,H,W] fp32; N images in the table */
+    const fpd_aug_img_t* images;   /* [N] */
+    const fpd_aug_crop_t* crop;    /* [B] */
+    float mean[3], std[3];
+    float* out;
+} fpd_warp_aug_t;
+int fpd_warp_affine_aug(const fpd_warp_aug_t* a, fpd_stream_t stream);
+
+/* fpd_render_targets with JointsDataset.py:286-287: the written weight is vis_or_zero * joints_weight[j] (float32); the
+ * paste decision uses the unmultiplied weight.  joints_weight NULL = fpd_render_targets. */
+typedef struct {
+    fpd_targets_t t;
+    const float* joints_weight;    /* [J] or NULL */
+} fpd_targets_w_t;
+int fpd_render_targets_w(const fpd_targets_w_t* a, fpd_stream_t stream);
+
 /* ---- execution plan: a recorded list of the ops above, replayed with one call ---- */
 enum {
     FPD_OP_CONV = 0, FPD_OP_WGRAD = 1, FPD_OP_STEM_FWD = 2, FPD_OP_STEM_WGRAD = 3, FPD_OP_EW = 4,

@@ -8,7 +8,9 @@ Same flow as the reference's main() (:96-294): config merge, student `models.<NA
 teacher from the cloned config merged with --tcfg, strict teacher-checkpoint load, two JointsMSELoss criteria,
 Adam + MultiStepLR, epoch loop -> core.function.fpd_train -> checkpoint.  What differs: one process per GPU with an
 RCCL gradient all-reduce instead of nn.DataParallel; the models run on the HIP path; DATASET.DATASET 'synthetic'
-(the default -- MPII/COCO are not available offline) feeds seeded synthetic crops, and KD.TEACHER 'synthetic' builds a
+(the default -- MPII/COCO are not available offline) feeds seeded synthetic crops, DATASET.DATASET 'synthetic_aug' seeded
+scenes that are augmented, cropped and labelled on the device per batch (DATASET.FLIP / SCALE_FACTOR / ROT_FACTOR /
+PROB_HALF_BODY / NUM_JOINTS_HALF_BODY, LOSS.USE_DIFFERENT_JOINTS_WEIGHT; lib/dataset/device_dataset.py), and KD.TEACHER 'synthetic' builds a
 random teacher with calibrated BN statistics instead of loading a checkpoint.  LOSS.USE_OHKM of the student config makes
 the pose criterion a JointsOHKMMSELoss(topk=LOSS.TOPK), LOSS.USE_OHKM of the teacher config the distillation criterion
 (make_criterion below); the reference declares both keys and its tools never read them (its class is never instantiated).
@@ -30,7 +32,7 @@ from fpd_amd import dist as fdist, executor as E, synth  # noqa: E402
 from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import fpd_train, train, validate  # noqa: E402
-from fpd_amd.lib.dataset import SyntheticPose  # noqa: E402
+from fpd_amd.lib.dataset import SyntheticPose, synthetic_aug  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
 from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
                                      save_checkpoint)
@@ -118,16 +120,21 @@ def run(args, normal=False):
         logger.info('=> hard keypoint mining: pose criterion %s, distillation criterion %s',
                     'topk %d' % cfg.LOSS.TOPK if cfg.LOSS.USE_OHKM else 'MSE', 'topk %d' % tcfg.LOSS.TOPK if tcfg.LOSS.USE_OHKM else 'MSE')
 
-    if cfg.DATASET.DATASET != 'synthetic':
+    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug'):
         sys.exit('dataset %r is not available here (CPU-side MPII/COCO pipeline is out of scope); use DATASET.DATASET synthetic'
                  % cfg.DATASET.DATASET)
     bs = cfg.TRAIN.BATCH_SIZE_PER_GPU
-    train_set = SyntheticPose(cfg, cfg.DATASET.NUM_SAMPLES, seed=rank)
-    loader = torch.utils.data.DataLoader(train_set, batch_size=bs, shuffle=cfg.TRAIN.SHUFFLE, num_workers=0,
-                                         pin_memory=cfg.PIN_MEMORY, drop_last=True, collate_fn=train_set.collate)
-    valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
-    valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, shuffle=False, num_workers=0,
-                                               pin_memory=cfg.PIN_MEMORY, collate_fn=valid_set.collate)
+    if cfg.DATASET.DATASET == 'synthetic_aug':
+        # seeded scenes resident on the device; every batch is augmented there (half-body, scale / rotation jitter, flip),
+        # cropped and given its targets by three kernels (lib/dataset/device_dataset.py)
+        loader, valid_loader, valid_set = synthetic_aug(cfg, dev, rank)
+    else:
+        train_set = SyntheticPose(cfg, cfg.DATASET.NUM_SAMPLES, seed=rank)
+        loader = torch.utils.data.DataLoader(train_set, batch_size=bs, shuffle=cfg.TRAIN.SHUFFLE, num_workers=0,
+                                             pin_memory=cfg.PIN_MEMORY, drop_last=True, collate_fn=train_set.collate)
+        valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
+        valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, shuffle=False, num_workers=0,
+                                                   pin_memory=cfg.PIN_MEMORY, collate_fn=valid_set.collate)
     if args.max_iters:
         import itertools
         full = loader

@@ -7,7 +7,7 @@ Same flow as the reference's main(): config merge, `models.<NAME>.get_pose_net(c
 TEST.MODEL_FILE (strict=False like the reference, :88-90) or <output dir>/final_state.pth (:91-96), JointsMSELoss,
 validation loader, `core.function.validate` (flip test / heat-map shift / post-processing per cfg.TEST).  What differs: the
 model runs on the HIP path of one GPU; DATASET.DATASET 'synthetic' (MPII / COCO archives are not available offline) feeds
-the seeded synthetic validation set of tools/fpd_train.py."""
+the seeded synthetic validation set of tools/fpd_train.py ('synthetic_aug': its validation scenes, cropped on the device)."""
 import argparse
 import logging
 import os
@@ -25,7 +25,7 @@ from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import validate  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss  # noqa: E402
-from fpd_amd.lib.dataset import SyntheticPose  # noqa: E402
+from fpd_amd.lib.dataset import SyntheticPose, synthetic_aug  # noqa: E402
 from fpd_amd.lib.utils.utils import load_checkpoint  # noqa: E402
 
 
@@ -57,12 +57,15 @@ def main():
     model = fdist.DataParallelReplica(model.to(dev))
     criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)          # :101-103
 
-    if cfg.DATASET.DATASET != 'synthetic':
+    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug'):
         sys.exit('dataset %r is not available here (CPU-side MPII/COCO pipeline is out of scope); use DATASET.DATASET synthetic'
                  % cfg.DATASET.DATASET)
-    valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
-    valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, shuffle=False, num_workers=0,
-                                               pin_memory=cfg.PIN_MEMORY, collate_fn=valid_set.collate)
+    if cfg.DATASET.DATASET == 'synthetic_aug':          # the validation scenes of tools/fpd_train.py, cropped on the device
+        _, valid_loader, valid_set = synthetic_aug(cfg, dev, train=False)
+    else:
+        valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
+        valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, shuffle=False, num_workers=0,
+                                                   pin_memory=cfg.PIN_MEMORY, collate_fn=valid_set.collate)
     perf = validate(cfg, valid_loader, valid_set, model, criterion, out_dir, cfg.LOG_DIR)    # :130-132
     logger.info('=> validation done: perf indicator %.4f, loss %.5f, accuracy %.4f', perf, validate.last['loss'], validate.last['acc'])
 
