@@ -78,6 +78,8 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c1_launches")) return fpd_conv_c1_option(2, value);      // (read-only: launches served so far)
     if (!strcmp(name, "conv_skip")) return fpd_conv_c1_option(3, value);             // second 1x1 source (fpd_conv_t.x2) offered at all
     if (!strcmp(name, "stem_act")) return fpd_stem_s2d_option(0, value);             // eval-mode BN + ReLU in the stem's epilogue (fpd_stem_t.act)
+    if (!strcmp(name, "ew_merge")) return fpd_ew_merge_option(value < 0 ? 0 : value);      // BN-backward applies inside the pool backward (fpd_ew_merge_t) offered at all
+    if (!strcmp(name, "ew_merge_blocks")) return fpd_ew_merge_blocks_option(value);      // their grid cap (tests: several windows per thread on small tensors)
     if (!strcmp(name, "conv_c3")) return fpd_conv_c3_option(0, value);
     if (!strcmp(name, "conv_c3_blocks")) return fpd_conv_c3_option(1, value);
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);
@@ -92,7 +94,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_bn_t); SZ(fpd_conv_t); SZ(fpd_wgrad_t); SZ(fpd_stem_t); SZ(fpd_ew_t); SZ(fpd_loss_t); SZ(fpd_adam_t);
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
-    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t);
+    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
 #undef SZ
     return -1;
@@ -406,6 +408,13 @@ int fpd_elementwise(const fpd_ew_t* a, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+int fpd_ew_merge_supported(const fpd_ew_merge_t* a) { return (a && fpd_ew_merge_why_not(*a) == nullptr) ? 1 : 0; }
+int fpd_ew_merge(const fpd_ew_merge_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a, "ew_merge: null pointer");
+    int rc = fpd_ew_merge_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
 static int validate_head(const fpd_head_t* a) {
     FPD_REQUIRE(a && a->y0 && a->score && a->w_fc && a->w_score, "head: null pointer");
     FPD_REQUIRE(a->next == nullptr || (a->x && a->w_fc2 && a->w_score2 && a->next != a->x && a->next != a->y0),
@@ -593,7 +602,7 @@ int fpd_nhwc_to_nchw(const void* src, float* dst, int32_t N, int32_t C, int32_t 
 struct fpd_op {
     int32_t type;
     union {
-        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_adam_t adam; fpd_sgd_t sgd;
+        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_adam_t adam; fpd_sgd_t sgd; fpd_ew_merge_t ewm;
         fpd_memset_t mset; fpd_table_t table;
     } u;
 };
@@ -646,6 +655,7 @@ int fpd_plan_add(fpd_plan* p, int32_t op, const void* args, int64_t bytes) {
         case FPD_OP_BNECK: case FPD_OP_BNECK_FOLD: want = sizeof(fpd_bneck_t); break;
         case FPD_OP_STEM_FWD: case FPD_OP_STEM_WGRAD: want = sizeof(fpd_stem_t); break;
         case FPD_OP_EW: want = sizeof(fpd_ew_t); break;
+        case FPD_OP_EW_MERGE: want = sizeof(fpd_ew_merge_t); break;
         case FPD_OP_LOSS: want = sizeof(fpd_loss_t); break;
         case FPD_OP_LOSS_OHKM: want = sizeof(fpd_loss_ohkm_t); break;
         case FPD_OP_ADAM: want = sizeof(fpd_adam_t); break;
@@ -715,6 +725,12 @@ static void set_op_tag(int idx, const fpd_op& o) {
         case FPD_OP_HEAD: snprintf(t, sizeof(t), "head N=%d H=%d W=%d C=%d J=%d", o.u.head.N, o.u.head.H, o.u.head.W, o.u.head.C, o.u.head.J); break;
         case FPD_OP_EW: snprintf(t, sizeof(t), "ew %s N=%d H=%d W=%d C=%d", ewn(o.u.ew.op), o.u.ew.N, o.u.ew.H, o.u.ew.W, o.u.ew.C); break;
         case FPD_OP_EW_PAIR: snprintf(t, sizeof(t), "ew2 %s N=%d H=%d W=%d C=%d | H=%d W=%d", ewn(o.u.epair.a.op), o.u.epair.a.N, o.u.epair.a.H, o.u.epair.a.W, o.u.epair.a.C, o.u.epair.b.H, o.u.epair.b.W); break;
+        case FPD_OP_EW_MERGE: {
+            const fpd_ew_merge_t& m = o.u.ewm;
+            const bool pb = m.kind == FPD_EWM_MAXPOOL_BWD;
+            snprintf(t, sizeof(t), "ewm %s N=%d H=%d W=%d C=%d", pb ? (m.has_full ? "apply2+maxpool_bwd" : "apply+maxpool_bwd") : "apply+sumpool", m.pool.N, m.pool.H, m.pool.W, m.pool.C);
+            break;
+        }
         case FPD_OP_STEM_FWD: case FPD_OP_STEM_WGRAD: snprintf(t, sizeof(t), "%s N=%d H=%d W=%d K=%d%s", o.type == FPD_OP_STEM_FWD ? "stem_fwd" : "stem_wgrad", o.u.stem.N, o.u.stem.H, o.u.stem.W, o.u.stem.K,
                                                               (o.type == FPD_OP_STEM_FWD && o.u.stem.act.mode != FPD_BN_NONE) ? " +act" : ""); break;
         case FPD_OP_AFFSUM: snprintf(t, sizeof(t), "affsum N=%d H=%d W=%d C=%d terms=%d", o.u.affsum.N, o.u.affsum.H, o.u.affsum.W, o.u.affsum.C, o.u.affsum.nterms); break;
@@ -747,6 +763,7 @@ static int run_op(const fpd_op& o, fpd_stream_t s) {
         case FPD_OP_STEM_FWD: return fpd_stem_forward(&o.u.stem, s);
         case FPD_OP_STEM_WGRAD: return fpd_stem_wgrad(&o.u.stem, s);
         case FPD_OP_EW: return fpd_elementwise(&o.u.ew, s);
+        case FPD_OP_EW_MERGE: return fpd_ew_merge(&o.u.ewm, s);
         case FPD_OP_LOSS: return fpd_loss(&o.u.loss, s);
         case FPD_OP_LOSS_OHKM: return fpd_loss_ohkm(&o.u.lossk, s);
         case FPD_OP_ADAM: return fpd_adam(&o.u.adam, s);

@@ -114,6 +114,11 @@ int fpd_augment_params_launch(const fpd_augment_t& a, hipStream_t st);
 int fpd_elementwise_launch(const fpd_ew_t& a, hipStream_t st);
 int fpd_elementwise_pair_launch(const fpd_ew_t& a, const fpd_ew_t& b, hipStream_t st);
 int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st);
+// merged BN-backward apply + pool backward (elementwise.hip): nullptr = served, else the reason; the launch walks the same decision
+const char* fpd_ew_merge_why_not(const fpd_ew_merge_t& m);
+int fpd_ew_merge_launch(const fpd_ew_merge_t& m, hipStream_t st);
+int fpd_ew_merge_option(int value);      // >= 0: set; returns the previous value
+int fpd_ew_merge_blocks_option(int value);      // >= 1: set the grid cap of the merged launches; returns the previous value
 int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
 int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& a, hipStream_t st);      // csrc/loss_ohkm.hip: two launches
 int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a);

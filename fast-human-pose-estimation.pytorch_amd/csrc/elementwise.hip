@@ -326,6 +326,167 @@ __global__ __launch_bounds__(256) void affsum_kernel(const fpd_affsum_t a) {
     }
 }
 
+// ---- BN-backward apply(s) evaluated inside the pool backward that reads them (fpd_ew_merge_t) ----
+// Per-channel tables of one FPD_EW_BN_BWD_APPLY, the ones ew_body builds for it (same expressions, same roundings).
+struct ApplyTab { float t0[FPD_MAXC], t1[FPD_MAXC], t2[FPD_MAXC], mu[FPD_MAXC], is[FPD_MAXC]; };
+
+// channels c0, c0 + stride, ...
+__device__ __forceinline__ void apply_tab_fill(const fpd_ew_t& a, ApplyTab& t, const int c0, const int stride, const bool grads) {
+    const int C = a.C;
+    const double cnt = (double)a.N * a.H * a.W;
+    for (int c = c0; c < C; c += stride) {
+        float sc, sh, mu, is;
+        bn_coef(a.bn, c, C, cnt, sc, sh, mu, is);
+        t.t0[c] = a.bn.gamma[c] * is;                 // gamma * invstd
+        const double b1 = stats_sum(a.bstats, C, 0, c), b2 = stats_sum(a.bstats, C, 1, c);
+        t.t1[c] = (float)(b1 / cnt);                  // mean(dz)
+        t.t2[c] = (float)(b2 / cnt);                  // mean(dz * xhat)
+        t.mu[c] = mu;
+        t.is[c] = is;
+        if (grads) {
+            if (a.dgamma) a.dgamma[c] = (float)b2;
+            if (a.dbeta) a.dbeta[c] = (float)b1;
+        }
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ uint4 ldraw(const T* p) { return *reinterpret_cast<const uint4*>(p); }
+
+// o = round_T(apply(g, v) + add): the value the stand-alone apply stores, as a float
+template <typename T, bool ADD>
+__device__ __forceinline__ void apply_vec(const uint4& rg, const uint4& rv, const uint4& rad, const ApplyTab& t, const int cv, float* o) {
+    constexpr int VEC = DT<T>::VEC;
+    float g[VEC], v[VEC], ad[VEC];
+    DT<T>::unpack(rg, g);
+    DT<T>::unpack(rv, v);
+    if (ADD) DT<T>::unpack(rad, ad);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        const int c = cv + j;
+        const float xhat = (v[j] - t.mu[c]) * t.is[c];
+        o[j] = DT<T>::rnd(t.t0[c] * (g[j] - t.t1[c] - xhat * t.t2[c]) + (ADD ? ad[j] : 0.f));
+    }
+}
+
+// A thread owns whole 2x2 windows of one channel vector (layout and grid-stride of ew_body's pooled ops): every load of a window
+// is issued before its first use, and all its reads precede its writes.  No output is an input (checked on the host), hence __restrict__.
+// KIND FPD_EWM_MAXPOOL_BWD: FULL = the full-resolution apply is present; ADDF = its `add` (FULL) / the pool op's `add` (!FULL); ADDH = the
+// half-resolution apply's `add`.  KIND FPD_EWM_SUMPOOL: ADDF = the apply's `add`, ADDH = the pool op's `add` (FULL is not looked at).
+template <typename T, int KIND, bool FULL, bool ADDF, bool ADDH>
+__global__ __launch_bounds__(256) void ew_merge_kernel(const fpd_ew_merge_t m) {
+    constexpr int VEC = DT<T>::VEC;
+    constexpr bool POOLB = KIND == FPD_EWM_MAXPOOL_BWD;
+    constexpr bool APF = !POOLB || FULL;                 // the full-resolution apply is evaluated
+    __shared__ ApplyTab s_f, s_h;
+    const int tid = threadIdx.x;
+    const int C = m.pool.C, H = m.pool.H, W = m.pool.W, N = m.pool.N;
+    if (APF && POOLB) {      // two tables: even waves fill one, odd waves the other, so that both sets of statistics loads are in flight together
+        const int w = tid >> 6, c0 = (w >> 1) * 64 + (tid & 63);
+        if (w & 1) apply_tab_fill(m.half, s_h, c0, 128, blockIdx.x == 0);
+        else apply_tab_fill(m.full, s_f, c0, 128, blockIdx.x == 0);
+    } else if (APF) {
+        apply_tab_fill(m.full, s_f, tid, 256, blockIdx.x == 0);
+    } else {
+        apply_tab_fill(m.half, s_h, tid, 256, blockIdx.x == 0);
+    }
+    __syncthreads();
+    const int VP = C / VEC, PB = 256 / VP;
+    const int cv = (tid % VP) * VEC, pl = tid / VP;
+    if (pl >= PB) return;
+    const int OH = H / 2, OW = W / 2, npix = N * OH * OW;
+    typedef const T* __restrict__ in_t;
+    in_t xf = reinterpret_cast<const T*>(POOLB ? m.pool.x : m.full.x);      // BN input of the full-resolution apply = the pooled tensor
+    in_t gf = reinterpret_cast<const T*>(m.full.dy);
+    in_t af = reinterpret_cast<const T*>(APF ? m.full.add : m.pool.add);
+    in_t xh = reinterpret_cast<const T*>(m.half.x);
+    in_t gh = reinterpret_cast<const T*>(m.half.dy);
+    in_t ah = reinterpret_cast<const T*>(POOLB ? m.half.add : m.pool.add);
+    T* __restrict__ const yf = reinterpret_cast<T*>(POOLB ? m.pool.y : m.full.y);      // full resolution
+    T* __restrict__ const yh = reinterpret_cast<T*>(m.pool.y);                          // SUMPOOL: half resolution
+    for (int pix = blockIdx.x * PB + pl; pix < npix; pix += gridDim.x * PB) {
+        const int n = pix / (OH * OW), rem = pix - n * (OH * OW);
+        const int oy = rem / OW, ox = rem - oy * OW;
+        const size_t ih = (size_t)pix * C + cv;
+        const size_t i00 = ((size_t)(n * H + 2 * oy) * W + 2 * ox) * C + cv;
+        const size_t i01 = i00 + C, i10 = i00 + (size_t)W * C, i11 = i10 + C;
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+        uint4 rx0 = z, rx1 = z, rx2 = z, rx3 = z, rg0 = z, rg1 = z, rg2 = z, rg3 = z, ra0 = z, ra1 = z, ra2 = z, ra3 = z, rxh = z, rgh = z, rah = z;
+        if (POOLB || APF) { rx0 = ldraw<T>(xf + i00); rx1 = ldraw<T>(xf + i01); rx2 = ldraw<T>(xf + i10); rx3 = ldraw<T>(xf + i11); }
+        if (APF) { rg0 = ldraw<T>(gf + i00); rg1 = ldraw<T>(gf + i01); rg2 = ldraw<T>(gf + i10); rg3 = ldraw<T>(gf + i11); }
+        if (ADDF) { ra0 = ldraw<T>(af + i00); ra1 = ldraw<T>(af + i01); ra2 = ldraw<T>(af + i10); ra3 = ldraw<T>(af + i11); }
+        if (POOLB) { rxh = ldraw<T>(xh + ih); rgh = ldraw<T>(gh + ih); }
+        if (ADDH) rah = ldraw<T>(ah + ih);
+        float a0[VEC], a1[VEC], a2[VEC], a3[VEC];
+        if (APF) {
+            apply_vec<T, ADDF>(rg0, rx0, ra0, s_f, cv, a0);
+            apply_vec<T, ADDF>(rg1, rx1, ra1, s_f, cv, a1);
+            apply_vec<T, ADDF>(rg2, rx2, ra2, s_f, cv, a2);
+            apply_vec<T, ADDF>(rg3, rx3, ra3, s_f, cv, a3);
+        } else if (ADDF) {
+            DT<T>::unpack(ra0, a0); DT<T>::unpack(ra1, a1); DT<T>::unpack(ra2, a2); DT<T>::unpack(ra3, a3);
+        } else {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) a0[j] = a1[j] = a2[j] = a3[j] = 0.f;
+        }
+        if (POOLB) {      // route b to the first maximum in scan order (FPD_EW_MAXPOOL_BWD), on top of a_i
+            float b[VEC], v0[VEC], v1[VEC], v2[VEC], v3[VEC], o0[VEC], o1[VEC], o2[VEC], o3[VEC];
+            apply_vec<T, ADDH>(rgh, rxh, rah, s_h, cv, b);
+            DT<T>::unpack(rx0, v0); DT<T>::unpack(rx1, v1); DT<T>::unpack(rx2, v2); DT<T>::unpack(rx3, v3);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                int arg = 0; float best = v0[j];
+                if (v1[j] > best) { best = v1[j]; arg = 1; }
+                if (v2[j] > best) { best = v2[j]; arg = 2; }
+                if (v3[j] > best) { best = v3[j]; arg = 3; }
+                o0[j] = (arg == 0 ? b[j] : 0.f) + a0[j];
+                o1[j] = (arg == 1 ? b[j] : 0.f) + a1[j];
+                o2[j] = (arg == 2 ? b[j] : 0.f) + a2[j];
+                o3[j] = (arg == 3 ? b[j] : 0.f) + a3[j];
+            }
+            stv<T>(yf + i00, o0); stv<T>(yf + i01, o1); stv<T>(yf + i10, o2); stv<T>(yf + i11, o3);
+        } else {          // dx out, and its 2x2 sum in the order of FPD_EW_SUMPOOL
+            float ad[VEC], o[VEC];
+            if (ADDH) DT<T>::unpack(rah, ad);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) o[j] = (a0[j] + a1[j]) + (a2[j] + a3[j]) + (ADDH ? ad[j] : 0.f);
+            stv<T>(yf + i00, a0); stv<T>(yf + i01, a1); stv<T>(yf + i10, a2); stv<T>(yf + i11, a3);
+            stv<T>(yh + ih, o);
+        }
+    }
+}
+
+int g_ew_merge_blocks = 2048;      // grid cap (option "ew_merge_blocks"; 2048 = the cap of ew_grid)
+
+template <typename T, int KIND, bool FULL, bool ADDF, bool ADDH>
+int launch_ew_merge(const fpd_ew_merge_t& m, hipStream_t st) {
+    const int grid = std::min(ew_grid<T, FPD_EW_SUMPOOL>(m.pool), g_ew_merge_blocks);      // the grid rule of the pooled ops: one window per thread and trip
+    FPD_LAUNCH((ew_merge_kernel<T, KIND, FULL, ADDF, ADDH>), dim3(grid), dim3(256), 0, st, m);
+    return 0;
+}
+
+template <typename T>
+int dispatch_ew_merge(const fpd_ew_merge_t& m, hipStream_t st) {
+    const bool pb = m.kind == FPD_EWM_MAXPOOL_BWD;
+    const bool full = !pb || m.has_full;
+    const int v = (pb ? 8 : 0) | (full ? 4 : 0) | ((full ? m.full.add : m.pool.add) ? 2 : 0) | ((pb ? m.half.add : m.pool.add) ? 1 : 0);
+    switch (v) {
+        case 4: return launch_ew_merge<T, FPD_EWM_SUMPOOL, true, false, false>(m, st);
+        case 5: return launch_ew_merge<T, FPD_EWM_SUMPOOL, true, false, true>(m, st);
+        case 6: return launch_ew_merge<T, FPD_EWM_SUMPOOL, true, true, false>(m, st);
+        case 7: return launch_ew_merge<T, FPD_EWM_SUMPOOL, true, true, true>(m, st);
+        case 8: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, false, false, false>(m, st);
+        case 9: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, false, false, true>(m, st);
+        case 10: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, false, true, false>(m, st);
+        case 11: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, false, true, true>(m, st);
+        case 12: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, true, false, false>(m, st);
+        case 13: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, true, false, true>(m, st);
+        case 14: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, true, true, false>(m, st);
+        case 15: return launch_ew_merge<T, FPD_EWM_MAXPOOL_BWD, true, true, true>(m, st);
+    }
+    return fpd_fail(-2, "ew_merge: no variant %d", v);
+}
+
 template <typename T>
 int dispatch_ew(const fpd_ew_t& a, hipStream_t st) {
     switch (a.op) {
@@ -370,6 +531,77 @@ int fpd_elementwise_launch(const fpd_ew_t& a, hipStream_t st) {
                          a.op == FPD_EW_UPADD_FWD || a.op == FPD_EW_DILATE2);
     if (pooled && ((a.H & 1) || (a.W & 1))) return fpd_fail(-3, "elementwise: 2x2 ops need even H,W (got %dx%d)", a.H, a.W);
     return a.dtype == FPD_BF16 ? dispatch_ew<bf16_t>(a, st) : dispatch_ew<float>(a, st);
+}
+
+// ---- fpd_ew_merge_t: the ONE decision both the query and the launch walk (pure host code, nothing dereferenced) ----
+static int ew_merge_default() {      // FPD_EW_MERGE as it stands when the library is loaded (default 1)
+    const char* e = getenv("FPD_EW_MERGE");
+    return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+}
+static int g_ew_merge = ew_merge_default();
+int fpd_ew_merge_option(int value) {
+    const int prev = g_ew_merge;
+    if (value >= 0) g_ew_merge = value ? 1 : 0;
+    return prev;
+}
+
+int fpd_ew_merge_blocks_option(int value) {
+    const int prev = g_ew_merge_blocks;
+    if (value >= 1) g_ew_merge_blocks = value;
+    return prev;
+}
+
+static bool ew_apply_ok(const fpd_ew_t& a, const fpd_ew_t& pool, const int div) {
+    return a.op == FPD_EW_BN_BWD_APPLY && a.dtype == pool.dtype && a.N == pool.N && a.H == pool.H / div && a.W == pool.W / div && a.C == pool.C &&
+           a.x && a.dy && a.y && a.bstats && a.bn.gamma && a.bn.beta &&
+           ((a.bn.mode == FPD_BN_TRAIN && a.bn.stats) || (a.bn.mode == FPD_BN_EVAL && a.bn.running_mean && a.bn.running_var));
+}
+
+// nullptr: served; else why not
+const char* fpd_ew_merge_why_not(const fpd_ew_merge_t& m) {
+    if (fpd_ew_merge_option(-1) == 0) return "switched off (FPD_EW_MERGE=0 / option ew_merge)";
+    const fpd_ew_t& p = m.pool;
+    if (m.kind != FPD_EWM_MAXPOOL_BWD && m.kind != FPD_EWM_SUMPOOL) return "unknown kind";
+    if (p.dtype != FPD_BF16 && p.dtype != FPD_F32) return "bad dtype";
+    const int vec = (p.dtype == FPD_BF16) ? 8 : 4;
+    if (p.N <= 0 || p.H <= 0 || p.W <= 0 || p.C <= 0 || (p.H & 1) || (p.W & 1)) return "dims must be positive, H and W even";
+    if (p.C % vec != 0 || p.C > FPD_MAXC || p.C / vec > 128) return "C must be a multiple of the 16-byte vector and <= FPD_MAXC";
+    if ((int64_t)p.N * p.H * p.W * p.C >= ((int64_t)1 << 31)) return "tensor too large for 32-bit pixel indexing";
+    const bool pb = m.kind == FPD_EWM_MAXPOOL_BWD;
+    if (p.op != (pb ? FPD_EW_MAXPOOL_BWD : FPD_EW_SUMPOOL) || !p.x || !p.y) return "pool member: wrong op or null pointer";
+    const void* in[10];
+    int n = 0;
+    const void* out2 = nullptr;
+    if (pb) {
+        if (!ew_apply_ok(m.half, p, 2)) return "half-resolution member is not a complete FPD_EW_BN_BWD_APPLY on [N,H/2,W/2,C]";
+        if (p.dy != m.half.y) return "the pool backward's dy is not the half-resolution apply's result";
+        in[n++] = p.x; in[n++] = m.half.x; in[n++] = m.half.dy; in[n++] = m.half.add;
+        if (m.has_full) {
+            if (!ew_apply_ok(m.full, p, 1)) return "full-resolution member is not a complete FPD_EW_BN_BWD_APPLY on [N,H,W,C]";
+            if (p.add != m.full.y || p.x != m.full.x) return "the pool backward's add / x are not the full-resolution apply's result / input";
+            in[n++] = m.full.dy; in[n++] = m.full.add;
+        } else {
+            in[n++] = p.add;
+        }
+    } else {
+        if (!ew_apply_ok(m.full, p, 1)) return "full-resolution member is not a complete FPD_EW_BN_BWD_APPLY on [N,H,W,C]";
+        if (p.x != m.full.y) return "the sum-pool's x is not the apply's result";
+        out2 = m.full.y;
+        if (out2 == p.y) return "the two outputs are one tensor";
+        in[n++] = m.full.x; in[n++] = m.full.dy; in[n++] = m.full.add; in[n++] = p.add;
+    }
+    for (int i = 0; i < n; ++i)
+        if (in[i] != nullptr && (in[i] == p.y || in[i] == out2)) return "an output is one of the inputs";
+    for (int i = 0; i < n; ++i)
+        if (((uintptr_t)in[i] & 15) != 0) return "pointers must be 16-byte aligned";
+    if (((uintptr_t)p.y & 15) != 0 || ((uintptr_t)out2 & 15) != 0) return "pointers must be 16-byte aligned";
+    return nullptr;
+}
+
+int fpd_ew_merge_launch(const fpd_ew_merge_t& m, hipStream_t st) {
+    const char* why = fpd_ew_merge_why_not(m);      // refused here, before any HIP call
+    if (why) return fpd_fail(-3, "ew_merge: %s; fpd_ew_merge_supported() reports 0 for it", why);
+    return m.pool.dtype == FPD_BF16 ? dispatch_ew_merge<bf16_t>(m, st) : dispatch_ew_merge<float>(m, st);
 }
 
 int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st) {

@@ -224,6 +224,104 @@ class Lowering:
                     m.fold_active = True
                     m.fold_apply.folded = True
 
+    def plan_ew_merge(self, ops):
+        """Decide, AFTER memory planning and before the backward list is lowered, which BN-backward applies that carry a residual
+        `add` are evaluated inside the pool-backward op that reads them first (include/fpd_amd.h: fpd_ew_merge_t):
+          pattern 1  an apply pair (or a lone half-resolution apply) directly in front of a 'maxpool_bwd' on lane 0 whose dy / add
+                     / x are the pair's b.y / a.y / a.x, and nothing else reads a.y or b.y;
+          pattern 2  an apply directly in front of the 'sumpool' whose x is its result.
+        The absorbed ops are marked `ewm_absorbed` (lowered as no-ops); the pool op gets `ewm_kind` / `ewm_full` / `ewm_half`
+        and is lowered, at its own position, as one FPD_OP_EW_MERGE.  The launch reads the applies' inputs (and, pattern 2, writes
+        the apply's result) later than the memory plan assumed, so a group is taken only if, on PHYSICAL arena intervals, no
+        output of the launch overlaps one of its inputs and no op between the absorbed op and the launch touches what moved."""
+        if os.environ.get('FPD_EW_MERGE', '1') == '0':
+            return
+        l = R.lib()
+        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
+        iv = lambda b: (b.arena, b.off, b.off + b.numel)
+        hit = lambda p, q: p[0] == q[0] and p[1] < q[2] and q[1] < p[2]
+        is_apply = lambda m: (m is not None and m.kind == 'ew' and m.op == 'bn_bwd_apply' and not getattr(m, 'folded', False)
+                              and not getattr(m, 'ewm_absorbed', False))
+        lane0 = [i for i, op in enumerate(ops) if op is not None and (op.lane or 0) == 0]
+        for k in range(1, len(lane0)):
+            i, j = lane0[k - 1], lane0[k]
+            prev, op = ops[i], ops[j]
+            if op.kind != 'ew' or op.op not in ('maxpool_bwd', 'sumpool') or getattr(op, 'ewm_kind', None) is not None:
+                continue
+            full = half = None
+            if op.op == 'maxpool_bwd':
+                cands = [m for m in members_of(prev) if is_apply(m)] if prev.kind in ('ew', 'ew2') else []
+                if len(cands) != len(members_of(prev)):
+                    continue
+                half = next((m for m in cands if _abuf(m.y) is _abuf(op.dy)), None)
+                full = next((m for m in cands if m is not half), None)
+                n, h, w, c = op.dims
+                if half is None or tuple(half.dims) != (n, h // 2, w // 2, c):
+                    continue
+                if full is not None and not (_abuf(op.add) is _abuf(full.y) and _abuf(op.x) is _abuf(full.x) and tuple(full.dims) == tuple(op.dims)):
+                    continue
+                hidden = [m.y for m in (full, half) if m is not None]      # never written: nobody else may read them
+                if any(o is not op and any(_abuf(t) is _abuf(y) for t in o.acts_in() for y in hidden)
+                       for top in ops if top is not None for o in members_of(top)):
+                    continue
+            else:
+                if prev.kind != 'ew' or not is_apply(prev) or _abuf(prev.y) is not _abuf(op.x) or tuple(prev.dims) != tuple(op.dims):
+                    continue
+                full = prev
+                # its result is written at the pool op's position now: a reader in between would see it too early
+                if any(any(_abuf(t) is _abuf(full.y) for t in o.acts_in()) for top in ops[i + 1:j] if top is not None for o in members_of(top)):
+                    continue
+            group = [m for m in (full, half) if m is not None]
+            if not self._ew_merge_intervals_ok(op, full, half, ops[i + 1:j], iv, hit):
+                continue
+            op.ewm_kind, op.ewm_full, op.ewm_half = op.op, full, half
+            if l.fpd_ew_merge_supported(C.byref(self.ew_merge(op)[1])) == 1:
+                for m in group:
+                    m.ewm_absorbed = True
+            else:
+                op.ewm_kind = op.ewm_full = op.ewm_half = None
+
+    @staticmethod
+    def _ew_merge_intervals_ok(op, full, half, between, iv, hit):
+        """The aliasing rule of plan_ew_merge on physical intervals (arena, first element, end): the fused launch's outputs overlap
+        none of its inputs (nor each other), and no op issued between the absorbed op(s) and the launch writes what the applies
+        read or touches what they write -- those accesses now happen at the launch."""
+        group = [m for m in (full, half) if m is not None]
+        pool_bwd = op.op == 'maxpool_bwd'
+        moved_rd, moved_wr = [], []
+        for m in group:
+            r, w = m.accesses()
+            moved_rd += r + [m.bstats]                                        # (listed under the writes: produced OR consumed)
+            moved_wr += [b for b in w if b is not m.bstats and not (pool_bwd and b is _abuf(m.y))]     # pattern 1: the result is never written
+        ins = moved_rd + [_abuf(t) for t in ((op.x, op.add if full is None else None) if pool_bwd else (op.add,)) if t is not None]
+        outs = moved_wr + [_abuf(op.y)]
+        if any(hit(iv(o), iv(b)) for o in outs for b in ins):
+            return False
+        if any(hit(iv(a), iv(b)) for x, a in enumerate(outs) for b in outs[x + 1:]):
+            return False
+        for top in between:
+            if top is None:
+                continue
+            acc = top.accesses()
+            if acc is None:
+                return False
+            r, w = acc
+            if any(hit(iv(a), iv(b)) for a in w for b in moved_rd + moved_wr) or any(hit(iv(a), iv(b)) for a in r for b in moved_wr):
+                return False
+        return True
+
+    def ew_merge(self, op):
+        """fpd_ew_merge_t of a pool-backward op that evaluates its apply(s) itself (plan_ew_merge decided)."""
+        s = R.EwMergeT()
+        s.kind = R.EWM_MAXPOOL_BWD if op.ewm_kind == 'maxpool_bwd' else R.EWM_SUMPOOL
+        s.has_full = 1 if op.ewm_full is not None else 0
+        if op.ewm_full is not None:
+            s.full = self.ew(op.ewm_full, plain=True)[1]
+        if op.ewm_half is not None:
+            s.half = self.ew(op.ewm_half, plain=True)[1]
+        s.pool = self.ew(op, plain=True)[1]
+        return R.OP_EW_MERGE, s
+
     def _fill_skip(self, op, s):
         """Second 1x1 source of a conv3 that forms its Bottleneck's downsample convolution itself (fpd_conv_t.x2)."""
         sc, p = op.skip_conv, self.A.ptr
@@ -426,7 +524,11 @@ class Lowering:
                 self.partial_elems += n * stride
         return R.OP_STEM_WGRAD, s
 
-    def ew(self, op):
+    def ew(self, op, plain=False):
+        if not plain and getattr(op, 'ewm_absorbed', False):   # evaluated inside the pool-backward op that reads it (plan_ew_merge)
+            return R.OP_NOP, R.MemsetT()
+        if not plain and getattr(op, 'ewm_kind', None) is not None:
+            return self.ew_merge(op)
         if getattr(op, 'folded', False):                   # evaluated by the data gradient that consumes it (plan_folds)
             return R.OP_NOP, R.MemsetT()
         if getattr(op, 'stem_fused', False):               # applied in the epilogue of the stem that produces its input (plan_stem_act)
@@ -494,6 +596,8 @@ class Lowering:
             self._fill_fold(op.b, s.b)
             return R.OP_CONV_PAIR, s
         if op.kind == 'ew2':
+            if getattr(op.a, 'ewm_absorbed', False) and getattr(op.b, 'ewm_absorbed', False):      # both inside the pool backward behind them
+                return R.OP_NOP, R.MemsetT()
             fa, fb = getattr(op.a, 'folded', False), getattr(op.b, 'folded', False)
             if fa or fb:                                   # folded members leave the pair
                 return (R.OP_NOP, R.MemsetT()) if (fa and fb) else self.ew(op.b if fa else op.a)
@@ -659,6 +763,8 @@ class GraphInstance:
             self.low.use_partials = True
             bwd_ir = [op for op in g.bwd if op.kind != 'seed']
             self.low.plan_folds(bwd_ir)
+            if not isinstance(g, G.HRNetGraph):       # (hourglass only: the HRNet backward has no such groups worth a launch)
+                self.low.plan_ew_merge(bwd_ir)
             lowered = [self.low.op(op) for op in bwd_ir]
             self.low.finish_partials()                # patches the wgrad structs / fills the per-bucket reduce tables
             self.bucket_ops = {}                      # gradient bucket -> plan op after which its grad slice is final

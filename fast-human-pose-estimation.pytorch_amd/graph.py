@@ -165,6 +165,11 @@ class Op:
         elif k == 'ew':
             rd = [b(self.x), b(self.x2), b(self.dy), b(self.add)] + bn_bufs(self.bn)
             wr = [b(self.y), self.out_stats, self.bstats, self.dgamma, self.dbeta]    # bstats: produced or consumed
+            if getattr(self, 'ewm_kind', None) is not None:      # a pool backward that evaluates its BN-backward apply(s) itself
+                for m in (self.ewm_full, self.ewm_half):         # (executor.plan_ew_merge): it reads their inputs and writes their outputs
+                    if m is not None:
+                        rd += [b(m.x), b(m.dy), b(m.add)] + bn_bufs(m.bn)
+                        wr += [b(m.y), m.bstats, m.dgamma, m.dbeta]
         else:
             return None
         return [x for x in rd if x is not None], [x for x in wr if x is not None]

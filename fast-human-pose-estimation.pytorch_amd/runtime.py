@@ -17,7 +17,8 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
  EW_ADD, EW_RELU_MASK, EW_DILATE2) = range(10)
 (OP_CONV, OP_WGRAD, OP_STEM_FWD, OP_STEM_WGRAD, OP_EW, OP_LOSS, OP_ADAM, OP_MEMSET, OP_WPREP, OP_BNUPD,
  OP_WREDUCE, OP_BNECK, OP_BNECK_FOLD, OP_CONV_PAIR, OP_BNECK_PAIR, OP_EW_PAIR, OP_PCK, OP_HEAD, OP_HEAD_FOLD,
- OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD) = range(26)
+ OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE) = range(27)
+EWM_MAXPOOL_BWD, EWM_SUMPOOL = 0, 1
 AFFSUM_MAX = 4
 MAX_STACKS = 8
 MAXC = 512
@@ -82,6 +83,10 @@ class EwT(C.Structure):
 
 class EwPairT(C.Structure):
     _fields_ = [('a', EwT), ('b', EwT)]
+
+
+class EwMergeT(C.Structure):
+    _fields_ = [('kind', _i32), ('has_full', _i32), ('full', EwT), ('half', EwT), ('pool', EwT)]
 
 
 class HeadT(C.Structure):
@@ -214,7 +219,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_conv_f8_t': ConvF8T, 'fpd_wquant_entry_t': WquantEntryT, 'fpd_flipmerge_t': FlipMergeT, 'fpd_finalpreds_t': FinalPredsT, 'fpd_targets_t': TargetsT,
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
-            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT}
+            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -242,6 +247,8 @@ SYMBOLS = {
     'fpd_stem_wgrad_num_partials': (C.c_int, [C.POINTER(StemT)]),
     'fpd_elementwise': (C.c_int, [C.POINTER(EwT), _vp]),
     'fpd_elementwise_pair': (C.c_int, [C.POINTER(EwPairT), _vp]),
+    'fpd_ew_merge': (C.c_int, [C.POINTER(EwMergeT), _vp]),
+    'fpd_ew_merge_supported': (C.c_int, [_vp]),
     'fpd_pck': (C.c_int, [C.POINTER(PckT), _vp]),
     'fpd_affsum': (C.c_int, [C.POINTER(AffsumT), _vp]),
     'fpd_flip_w': (C.c_int, [_vp, _vp, _i64, _i32, _vp]),

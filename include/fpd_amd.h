@@ -264,6 +264,36 @@ typedef struct {
     fpd_bn_t bn;
 } fpd_ew_t;
 
+/* MERGED BN-BACKWARD APPLY + 2x2 POOL BACKWARD: a FPD_EW_BN_BWD_APPLY that carries a residual `add`, evaluated inside the
+ * pool-backward op that reads its result first -- one launch where the plan had two, and the tensor between them is not
+ * re-read (kind 0: not even written).  The members are the descriptors of the launches replaced, as they would have been
+ * issued; the result holds their bits: an apply is rounded to the storage type exactly where its own launch rounded it, and
+ * the rounded value enters the pool op's arithmetic unchanged.
+ *  FPD_EWM_MAXPOOL_BWD  the apply pair in front of a max-pool backward (the up / low branch of an hourglass level):
+ *      a_i = round(apply_full(full.dy[i], full.x[i]) + full.add[i])     the four pixels of a window   (has_full)
+ *      b   = round(apply_half(half.dy, half.x) + half.add)              the pooled pixel
+ *      pool.y[i] = round((i is the first maximum of pool.x's window in scan order ? b : 0) + a_i)
+ *    has_full: pool.add == full.y, pool.x == full.x, same dims; a_i is not stored.  !has_full: `full` is ignored and a_i =
+ *    pool.add[i] (or 0).  Always pool.dy == half.y, half dims = (N, H/2, W/2, C); b is not stored.
+ *  FPD_EWM_SUMPOOL      an apply in front of the nearest-up-sampling backward (`half` and has_full are ignored):
+ *      dx_i = round(apply_full(full.dy[i], full.x[i]) + full.add[i])  -> full.y (stored: later ops read it)
+ *      pool.y = round(pool.add + ((dx_0 + dx_1) + (dx_2 + dx_3)))     pool.x == full.y, same dims
+ * dgamma / dbeta of every apply present are written as its own launch writes them.  No output may be one of the inputs
+ * (pointer equality; the members' "may alias y" does not carry over).  fpd_ew_merge_supported() tells whether a launch is
+ * served (0: issue the member launches). */
+enum { FPD_EWM_MAXPOOL_BWD = 0, FPD_EWM_SUMPOOL = 1 };
+typedef struct {
+    int32_t kind;          /* FPD_EWM_* */
+    int32_t has_full;      /* MAXPOOL_BWD: the full-resolution apply is present */
+    fpd_ew_t full;         /* FPD_EW_BN_BWD_APPLY on [N,H,W,C], the pool op's dims */
+    fpd_ew_t half;         /* MAXPOOL_BWD: FPD_EW_BN_BWD_APPLY on [N,H/2,W/2,C] */
+    fpd_ew_t pool;         /* FPD_EW_MAXPOOL_BWD / FPD_EW_SUMPOOL */
+} fpd_ew_merge_t;
+int fpd_ew_merge(const fpd_ew_merge_t* a, fpd_stream_t stream);
+/* 1 if fpd_ew_merge() would serve this launch (pure host code: the members' ops, dims, dtype, wiring and aliasing are looked
+ * at, nothing is dereferenced); 0 otherwise.  Process-wide switch: FPD_EW_MERGE=0 / fpd_set_option("ew_merge", 0). */
+int fpd_ew_merge_supported(const fpd_ew_merge_t* a);
+
 /* y = relu?( sum_j a_j(up_j(x_j)) ): the tail of an HRNet block (pose_hrnet.py:52-57,93-98: relu(bn(conv) + skip)), a fuse
  * layer (:252-265: relu(sum of identity / 1x1-conv+BN+nearest-up / strided-conv+BN terms)) or a transition output (:349-372)
  * in ONE pass.  Term j is x_j[n, h/up_j, w/up_j, :] (nearest up-sampling by up_j in {1,2,4,8}), normalised by bn_j (mode
@@ -623,7 +653,8 @@ enum {
     FPD_OP_HEAD_FOLD = 18, FPD_OP_NOP = 19, FPD_OP_AFFSUM = 20, FPD_OP_NCHW2NHWC = 21, FPD_OP_CONV_F8 = 22,
     FPD_OP_WQUANT = 23,         /* args: fpd_table_t over fpd_wquant_entry_t */
     FPD_OP_LOSS_OHKM = 24,      /* args: fpd_loss_ohkm_t */
-    FPD_OP_SGD = 25             /* args: fpd_sgd_t */
+    FPD_OP_SGD = 25,            /* args: fpd_sgd_t */
+    FPD_OP_EW_MERGE = 26        /* args: fpd_ew_merge_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;
@@ -664,7 +695,9 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * "conv_pp_blocks" = its persistent blocks per occupancy slot (default 256); "bneck_blocks" / "head_blocks" = grid caps of the
  * persistent fpd_bottleneck_forward / fpd_head_forward kernels (defaults 128 / 160, any n >= 1); "wgrad_tile_only" = 1: fpd_conv_wgrad() fails
  * instead of falling through to the generic kernels when the halo-tile kernel declines a shape (tests); "conv_skip" / "stem_act" =
- * 0: fpd_conv_skip_supported() / fpd_stem_act_supported() answer 0 and such launches are refused (default 1).  Returns the
+ * 0: fpd_conv_skip_supported() / fpd_stem_act_supported() answer 0 and such launches are refused (default 1); "ew_merge" = 0:
+ * the same for fpd_ew_merge_supported() / fpd_ew_merge() (default 1, or what FPD_EW_MERGE says); "ew_merge_blocks" = grid cap of those launches (default 2048, any
+ * n >= 1).  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */
 int fpd_set_option(const char* name, int32_t value);
 int fpd_abi_sizeof(const char* struct_name);  /* sizeof of a struct above, -1 if unknown */
