@@ -81,7 +81,9 @@ def _defaults():
                     # training augmentation (default.py:66-71), read by DATASET.DATASET synthetic_aug; NUM_SCENES: size of its
                     # device-resident database
                     'FLIP': True, 'SCALE_FACTOR': 0.25, 'ROT_FACTOR': 30, 'PROB_HALF_BODY': 0.0, 'NUM_JOINTS_HALF_BODY': 8,
-                    'NUM_SCENES': 64},
+                    'NUM_SCENES': 64,
+                    # read by DATASET.DATASET mpii (default.py:62-75); CACHE_ROOT and HYBRID_JOINTS_TYPE are accepted and unused
+                    'DATA_FORMAT': 'jpg', 'COLOR_RGB': False, 'SELECT_DATA': False, 'CACHE_ROOT': '', 'HYBRID_JOINTS_TYPE': ''},
         'TRAIN': {'LR_FACTOR': 0.1, 'LR_STEP': [90, 120], 'LR': 0.00025, 'OPTIMIZER': 'adam', 'MOMENTUM': 0.9, 'WD': 0.0001,
                   'NESTEROV': False, 'GAMMA1': 0.99, 'GAMMA2': 0.0, 'BEGIN_EPOCH': 0, 'END_EPOCH': 140, 'RESUME': False,
                   'CHECKPOINT': '', 'BATCH_SIZE_PER_GPU': 32, 'SHUFFLE': True},

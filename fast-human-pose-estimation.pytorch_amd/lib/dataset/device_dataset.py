@@ -3,11 +3,13 @@ device and per batch: half-body crop, scale / rotation jitter, horizontal flip w
 get_affine_transform, the crop (cv2.warpAffine + ToTensor + Normalize), the joint transform and generate_target.
 
   DeviceJointsDB        the dataset, resident on the device: decoded 8-bit images of any size packed into one buffer with
-                        a table of {pointer, h, w, row_bytes}, the annotations, and the per-dataset tables
+                        a table of {pointer, h, w, row_bytes}, the annotations, and the per-dataset tables.  Samples may
+                        share an image (image_index), and the images may be streamed in from a loader (load)
   DeviceAugmentLoader   an iterable over batches.  Per batch the host draws the random numbers of the whole batch in one
                         vectorised call into a pinned staging buffer, copies it to the device and enqueues three kernels
                         (csrc/data.hip: augment_params, warp_affine_aug, render_targets_w).  There is no loop over samples
-                        and nothing waits for the device.
+                        and nothing waits for the device.  With world_size > 1 it yields this rank's share of
+                        the epoch (epoch_order)
 
 The draw table has one row per sample: the six numbers the reference pulls from np.random / random in its order of use
 (include/fpd_amd.h fpd_augment_t): u_half, n_half, n_scale, n_rot, u_rot, u_flip.  u_* are uniform [0,1), n_* standard
@@ -23,19 +25,37 @@ from ..utils.transforms import channel_sources
 from .device_pipeline import gaussian_patch
 
 DRAW_COLUMNS = ('u_half', 'n_half', 'n_scale', 'n_rot', 'u_rot', 'u_flip')
+DEFAULT_CHUNK_BYTES = 256 << 20          # the pinned staging block of a streamed upload
 
 
 class DeviceJointsDB:
     def __init__(self, images, joints, joints_vis, center, scale, flip_pairs, upper_body_ids, aspect_ratio,
-                 joints_weight=None, device='cuda', pixel_std=200):
-        """images: list of N uint8 [h,w,3] arrays (decoded, channel order is the caller's); joints [N,J,3] and
+                 joints_weight=None, device='cuda', pixel_std=200, image_index=None, load=None,
+                 chunk_bytes=DEFAULT_CHUNK_BYTES):
+        """images: list of uint8 [h,w,3] arrays (decoded, channel order is the caller's); joints [N,J,3] and
         joints_vis [N,J,3] or [N,J] as in db_rec['joints_3d'] / ['joints_3d_vis']; center, scale [N,2] in the dtype the
         dataset computes them in (MPII float64, COCO float32: the dtype decides numpy's arithmetic on them, the values
-        are stored as float64, which holds both exactly); joints_weight [J] or None."""
+        are stored as float64, which holds both exactly); joints_weight [J] or None.
+
+        image_index [N] (None: sample i owns image i): the image of every sample, for datasets with several people per
+        image -- each image is stored once and the table rows of its samples point at the same pixels.
+
+        load (None: `images` holds the arrays): a callable i -> uint8 [h,w,3] array; `images` then holds the (h, w) of
+        every image and the pixels are streamed to the device in image order through one pinned staging block of at most
+        chunk_bytes, without a host copy of the dataset (an image may span blocks).
+
+        Either way the pixels must fit into the device memory that is free now: FpdError otherwise, there is no
+        host-resident mode."""
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise R.FpdError('DeviceJointsDB lives on a CUDA (ROCm) device; there is no CPU path')
-        n = len(images)
+        n_images = len(images)
+        if image_index is None:
+            image_index = np.arange(n_images)
+        image_index = np.ascontiguousarray(image_index, np.int64).reshape(-1)
+        if image_index.size and not (0 <= image_index.min() and image_index.max() < n_images):
+            raise R.FpdError('DeviceJointsDB: image_index must lie in [0, %d)' % n_images)
+        n = len(image_index)
         joints = np.asarray(joints, np.float64)
         vis = np.asarray(joints_vis)
         vis = np.ascontiguousarray(vis[..., 0] if vis.ndim == 3 else vis, np.float32)
@@ -53,24 +73,68 @@ class DeviceJointsDB:
         self.h_center, self.h_scale = np.ascontiguousarray(center, np.float64), np.ascontiguousarray(scale, np.float64)
         self.names = ['scene/%d' % i for i in range(n)]
         # one packed image buffer + its table
-        sizes = np.array([im.shape[0] * im.shape[1] * 3 for im in images], np.int64)
-        offs = np.concatenate([[0], np.cumsum(sizes)])
-        packed = np.empty(int(offs[-1]), np.uint8)
-        for i, im in enumerate(images):
-            if not (im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-                raise R.FpdError('DeviceJointsDB: image %d must be a uint8 [h,w,3] array' % i)
-            packed[offs[i]:offs[i + 1]] = im.reshape(-1)
-        self.pixels = torch.from_numpy(packed).to(self.device)
+        if load is None:
+            for i, im in enumerate(images):
+                if not (im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+                    raise R.FpdError('DeviceJointsDB: image %d must be a uint8 [h,w,3] array' % i)
+            shapes = [(im.shape[0], im.shape[1]) for im in images]
+        else:
+            shapes = [(int(h), int(w)) for h, w in images]
+        sizes = np.array([h * w * 3 for h, w in shapes], np.int64)
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        need = int(offs[-1])
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free:
+            raise R.FpdError('DeviceJointsDB: the %d images need %d bytes of device memory and %d bytes are free; the '
+                             'database is device-resident, there is no host-resident mode' % (n_images, need, free))
+        if load is None:
+            packed = np.empty(need, np.uint8)
+            for i, im in enumerate(images):
+                packed[offs[i]:offs[i + 1]] = im.reshape(-1)
+            self.pixels = torch.from_numpy(packed).to(self.device)
+        else:
+            self.pixels = self._stream(shapes, offs, load, int(chunk_bytes))
+        self.image_index, self.image_offsets = image_index, offs
         table = (R.AugImgT * n)()
         base = self.pixels.data_ptr()
-        for i, im in enumerate(images):
-            table[i].img, table[i].h, table[i].w, table[i].row_bytes = base + int(offs[i]), im.shape[0], im.shape[1], im.shape[1] * 3
+        for i, k in enumerate(image_index):
+            h, w = shapes[k]
+            table[i].img, table[i].h, table[i].w, table[i].row_bytes = base + int(offs[k]), h, w, w * 3
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
         self.table = dev(np.frombuffer(bytes(table), np.uint8).copy())
         self.joints, self.vis, self.center, self.scale = dev(joints), dev(vis), dev(self.h_center), dev(self.h_scale)
         self.flip_src = dev(np.array(channel_sources(j, self.flip_pairs), np.int32))
         self.upper = dev(np.array([1 if k in self.upper_body_ids else 0 for k in range(j)], np.int32))
         self.joints_weight = None if joints_weight is None else dev(np.asarray(joints_weight, np.float32).reshape(j))
+
+    def _stream(self, shapes, offs, load, chunk_bytes):
+        """The packed pixel buffer, filled in image order through one pinned block: bytes [done, done + fill) of the
+        buffer sit in stage[0:fill) until the block is full or the last image is in."""
+        need = int(offs[-1])
+        if chunk_bytes < 1:
+            raise R.FpdError('DeviceJointsDB: chunk_bytes must be positive')
+        pixels = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stage = torch.empty(max(min(chunk_bytes, need), 1), dtype=torch.uint8, pin_memory=True)
+        host, cap = stage.numpy(), stage.numel()
+        done = fill = 0
+        for i, (h, w) in enumerate(shapes):
+            im = load(i)
+            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.shape == (h, w, 3)):
+                raise R.FpdError('DeviceJointsDB: image %d must be a uint8 [%d,%d,3] array, load() gave %s %s'
+                                 % (i, h, w, getattr(im, 'dtype', type(im)), getattr(im, 'shape', '')))
+            flat, pos = np.ascontiguousarray(im).reshape(-1), 0
+            assert done + fill == offs[i]
+            while pos < flat.size:
+                k = min(cap - fill, flat.size - pos)
+                host[fill:fill + k] = flat[pos:pos + k]
+                fill, pos = fill + k, pos + k
+                if fill == cap:
+                    pixels[done:done + fill].copy_(stage[:fill])       # blocking: the block is free again on return
+                    done, fill = done + fill, 0
+        if fill:
+            pixels[done:done + fill].copy_(stage[:fill])
+        assert done + fill == need
+        return pixels
 
     def __len__(self):
         return self.n
@@ -95,10 +159,33 @@ class DeviceJointsDB:
         return {'PCK@0.5': pck}, pck
 
 
+def epoch_order(n, seed, epoch, shuffle, rank=0, world_size=1):
+    """(database rows of this rank in this epoch as int32, the generator its augmentation draws come from).
+
+    One process: the permutation of (seed, epoch), and the draws continue on the generator that made it.  world_size > 1,
+    every rank holding the whole database: all ranks draw that same permutation, pad it by wrap-around to a multiple of
+    world_size and take rank::world_size (torch.utils.data.DistributedSampler's rule), and each draws its augmentation
+    numbers from a generator of its own, seeded by (seed, epoch, rank)."""
+    rank, world_size = int(rank), int(world_size)
+    if not 0 <= rank < world_size:
+        raise R.FpdError('epoch_order: rank %d is not in [0, %d)' % (rank, world_size))
+    rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([seed, epoch])))
+    order = rng.permutation(n).astype(np.int32) if shuffle else np.arange(n, dtype=np.int32)
+    if world_size == 1:
+        return order, rng
+    total = (n + world_size - 1) // world_size * world_size
+    order = np.resize(order, total) if n else order
+    rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([seed, epoch, rank])))
+    return np.ascontiguousarray(order[rank::world_size]), rng
+
+
 class DeviceAugmentLoader:
     def __init__(self, db, cfg, batch_size, is_train, shuffle=None, drop_last=None, seed=0,
-                 mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+                 mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), rank=0, world_size=1):
         self.db, self.batch_size, self.is_train = db, int(batch_size), bool(is_train)
+        self.rank, self.world_size = int(rank), int(world_size)
+        if not 0 <= self.rank < self.world_size:
+            raise R.FpdError('DeviceAugmentLoader: rank %d is not in [0, %d)' % (self.rank, self.world_size))
         self.shuffle = self.is_train if shuffle is None else bool(shuffle)
         self.drop_last = self.is_train if drop_last is None else bool(drop_last)
         self.seed, self.epoch = int(seed), 0
@@ -116,14 +203,12 @@ class DeviceAugmentLoader:
         self.epoch = int(epoch)
 
     def __len__(self):
-        n, b = len(self.db), self.batch_size
+        n, b = (len(self.db) + self.world_size - 1) // self.world_size, self.batch_size      # samples of this rank
         return n // b if self.drop_last else (n + b - 1) // b
 
     def __iter__(self):
-        rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([self.seed, self.epoch])))
+        order, rng = epoch_order(len(self.db), self.seed, self.epoch, self.shuffle, self.rank, self.world_size)
         self.epoch += 1
-        n = len(self.db)
-        order = rng.permutation(n).astype(np.int32) if self.shuffle else np.arange(n, dtype=np.int32)
         for k in range(len(self)):
             yield self.batch(order[k * self.batch_size:(k + 1) * self.batch_size], rng)
 

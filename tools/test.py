@@ -6,8 +6,9 @@
 Same flow as the reference's main(): config merge, `models.<NAME>.get_pose_net(cfg, is_train=False)`, weights from
 TEST.MODEL_FILE (strict=False like the reference, :88-90) or <output dir>/final_state.pth (:91-96), JointsMSELoss,
 validation loader, `core.function.validate` (flip test / heat-map shift / post-processing per cfg.TEST).  What differs: the
-model runs on the HIP path of one GPU; DATASET.DATASET 'synthetic' (MPII / COCO archives are not available offline) feeds
-the seeded synthetic validation set of tools/fpd_train.py ('synthetic_aug': its validation scenes, cropped on the device)."""
+model runs on the HIP path of one GPU; DATASET.DATASET 'synthetic' feeds the seeded synthetic validation set of
+tools/fpd_train.py ('synthetic_aug': its validation scenes, cropped on the device), 'mpii' DATASET.ROOT / TEST_SET with the
+PCKh table; COCO is not available."""
 import argparse
 import logging
 import os
@@ -25,7 +26,7 @@ from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import validate  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss  # noqa: E402
-from fpd_amd.lib.dataset import SyntheticPose, synthetic_aug  # noqa: E402
+from fpd_amd.lib.dataset import SyntheticPose, mpii, synthetic_aug  # noqa: E402
 from fpd_amd.lib.utils.utils import load_checkpoint  # noqa: E402
 
 
@@ -57,10 +58,12 @@ def main():
     model = fdist.DataParallelReplica(model.to(dev))
     criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)          # :101-103
 
-    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug'):
+    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii'):
         sys.exit('dataset %r is not available here (CPU-side MPII/COCO pipeline is out of scope); use DATASET.DATASET synthetic'
                  % cfg.DATASET.DATASET)
-    if cfg.DATASET.DATASET == 'synthetic_aug':          # the validation scenes of tools/fpd_train.py, cropped on the device
+    if cfg.DATASET.DATASET == 'mpii':                    # DATASET.ROOT / TEST_SET, resident on the device; PCKh
+        _, valid_loader, valid_set = mpii(cfg, dev, train=False)
+    elif cfg.DATASET.DATASET == 'synthetic_aug':          # the validation scenes of tools/fpd_train.py, cropped on the device
         _, valid_loader, valid_set = synthetic_aug(cfg, dev, train=False)
     else:
         valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
