@@ -96,6 +96,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
+    SZ(fpd_oks_nms_t);
 #undef SZ
     return -1;
 }
@@ -500,6 +501,20 @@ int fpd_warp_affine_aug(const fpd_warp_aug_t* a, fpd_stream_t stream) {
     int rc = fpd_warp_affine_aug_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
+int fpd_oks_nms(const fpd_oks_nms_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->offsets && a->n_keep, "oks_nms: null pointer");
+    FPD_REQUIRE(a->P_total >= 0 && a->n_img >= 0 && a->grid >= 0, "oks_nms: negative size (P_total=%d, n_img=%d, grid=%d)", a->P_total, a->n_img, a->grid);
+    FPD_REQUIRE(a->J >= 1 && a->J <= 64, "oks_nms: J=%d outside 1..64", a->J);
+    FPD_REQUIRE((a->soft == 0 || a->soft == 1) && (a->rescore == 0 || a->rescore == 1), "oks_nms: soft / rescore must be 0 or 1");
+    FPD_REQUIRE(a->oks_thre == a->oks_thre && a->in_vis_thre == a->in_vis_thre && (!a->soft || a->oks_thre != 0.0), "oks_nms: bad threshold");
+    FPD_REQUIRE(a->sigmas, "oks_nms: null pointer (sigmas)");
+    FPD_REQUIRE(a->P_total == 0 || (a->kpts && a->area && a->box_score && a->score && a->work && a->keep), "oks_nms: null pointer (per-person array)");
+    FPD_REQUIRE((int64_t)a->P_total * a->J * 3 < (1ll << 40), "oks_nms: too many people");
+    if (a->n_img == 0) return 0;
+    int rc = fpd_oks_nms_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
 int fpd_render_targets_w(const fpd_targets_w_t* w, fpd_stream_t stream) {
     FPD_REQUIRE(w, "render_targets_w: null pointer");
     const fpd_targets_t* a = &w->t;

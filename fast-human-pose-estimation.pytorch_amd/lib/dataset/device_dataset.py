@@ -31,7 +31,7 @@ DEFAULT_CHUNK_BYTES = 256 << 20          # the pinned staging block of a streame
 class DeviceJointsDB:
     def __init__(self, images, joints, joints_vis, center, scale, flip_pairs, upper_body_ids, aspect_ratio,
                  joints_weight=None, device='cuda', pixel_std=200, image_index=None, load=None,
-                 chunk_bytes=DEFAULT_CHUNK_BYTES):
+                 chunk_bytes=DEFAULT_CHUNK_BYTES, scores=None):
         """images: list of uint8 [h,w,3] arrays (decoded, channel order is the caller's); joints [N,J,3] and
         joints_vis [N,J,3] or [N,J] as in db_rec['joints_3d'] / ['joints_3d_vis']; center, scale [N,2] in the dtype the
         dataset computes them in (MPII float64, COCO float32: the dtype decides numpy's arithmetic on them, the values
@@ -43,6 +43,9 @@ class DeviceJointsDB:
         load (None: `images` holds the arrays): a callable i -> uint8 [h,w,3] array; `images` then holds the (h, w) of
         every image and the pixels are streamed to the device in image order through one pinned staging block of at most
         chunk_bytes, without a host copy of the dataset (an image may span blocks).
+
+        scores [N] (None: every sample scores 1): the detector's score of every sample's box (COCO validation from detection
+        boxes); validation batches carry it as meta['score'].
 
         Either way the pixels must fit into the device memory that is free now: FpdError otherwise, there is no
         host-resident mode."""
@@ -72,6 +75,9 @@ class DeviceJointsDB:
         self.h_joints, self.h_vis = joints, vis
         self.h_center, self.h_scale = np.ascontiguousarray(center, np.float64), np.ascontiguousarray(scale, np.float64)
         self.names = ['scene/%d' % i for i in range(n)]
+        self.h_scores = None if scores is None else np.ascontiguousarray(scores, np.float64).reshape(-1)
+        if self.h_scores is not None and self.h_scores.size != n:
+            raise R.FpdError('DeviceJointsDB: %d scores for %d samples' % (self.h_scores.size, n))
         # one packed image buffer + its table
         if load is None:
             for i, im in enumerate(images):
@@ -243,7 +249,8 @@ class DeviceAugmentLoader:
         else:
             contiguous = b > 0 and int(idx[-1]) - int(idx[0]) == b - 1
             meta = {'center': torch.from_numpy(db.h_center[idx]), 'scale': torch.from_numpy(db.h_scale[idx]),
-                    'score': torch.ones(b, dtype=torch.float64), 'index': torch.from_numpy(np.asarray(idx)),
+                    'score': torch.ones(b, dtype=torch.float64) if db.h_scores is None else torch.from_numpy(db.h_scores[idx]),
+                    'index': torch.from_numpy(np.asarray(idx)),
                     'image': db.names[int(idx[0]):int(idx[0]) + b] if contiguous else [db.names[i] for i in idx],
                     'joints': p['joints'], 'joints_vis': p['vis']}
         meta['trans'] = p['trans']

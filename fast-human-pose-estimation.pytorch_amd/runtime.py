@@ -167,6 +167,12 @@ class TargetsWT(C.Structure):
     _fields_ = [('t', TargetsT), ('joints_weight', _vp)]
 
 
+class OksNmsT(C.Structure):
+    _fields_ = [('P_total', _i32), ('n_img', _i32), ('J', _i32), ('soft', _i32), ('rescore', _i32), ('grid', _i32),
+                ('in_vis_thre', _f64), ('oks_thre', _f64), ('kpts', _vp), ('area', _vp), ('box_score', _vp), ('offsets', _vp),
+                ('sigmas', _vp), ('score', _vp), ('work', _vp), ('keep', _vp), ('n_keep', _vp), ('oks_first', _vp)]
+
+
 class LossT(C.Structure):
     _fields_ = [('B', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('S', _i32), ('dtype', _i32),
                 ('target_nchw', _i32), ('alpha', _f32), ('out', _vp * MAX_STACKS), ('dout', _vp * MAX_STACKS),
@@ -219,7 +225,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_conv_f8_t': ConvF8T, 'fpd_wquant_entry_t': WquantEntryT, 'fpd_flipmerge_t': FlipMergeT, 'fpd_finalpreds_t': FinalPredsT, 'fpd_targets_t': TargetsT,
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
-            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT}
+            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -259,6 +265,7 @@ SYMBOLS = {
     'fpd_augment_params': (C.c_int, [C.POINTER(AugmentT), _vp]),
     'fpd_warp_affine_aug': (C.c_int, [C.POINTER(WarpAugT), _vp]),
     'fpd_render_targets_w': (C.c_int, [C.POINTER(TargetsWT), _vp]),
+    'fpd_oks_nms': (C.c_int, [C.POINTER(OksNmsT), _vp]),
     'fpd_head_forward': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_head_fold': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_loss': (C.c_int, [C.POINTER(LossT), _vp]),

@@ -645,6 +645,36 @@ typedef struct {
 } fpd_targets_w_t;
 int fpd_render_targets_w(const fpd_targets_w_t* a, fpd_stream_t stream);
 
+/* ---- rescoring + OKS NMS of COCO's evaluate (coco.py:334-369, nms/nms.py:75-177): every picture in one launch ----
+ * One workgroup owns a picture (grid-stride over pictures when `grid` caps the launch) and runs the greedy loop itself; any
+ * number of people per picture.  The people of picture i are rows offsets[i] .. offsets[i+1] of the per-person arrays.
+ *   score[p] = mean of the maxvals > (float)in_vis_thre (float32, summed in joint order; 0 without any) * box_score[p]
+ *              (float64); rescore 0: score[p] = box_score[p] as it is (nms.oks_nms gets rescored people)
+ *   oks(g,d) = mean_j exp(-((xd-xg)^2 + (yd-yg)^2 [float32] / (2 sigma_j)^2 / ((area_g + area_d)/2 + 2^-52) / 2)) [float64]
+ *   hard (soft 0): pick the highest score, drop everyone left with oks > oks_thre, repeat
+ *   soft (soft 1): at most 20 picks; after each the working scores of the rest become s * exp(-oks^2 / oks_thre)
+ * Equal (working) scores: the lower index is picked first.  keep holds, per picture, the picked people as indices local to
+ * the picture in pick order, -1 in the remaining slots; n_keep[i] their number, or -1 if offsets[i..i+1] do not describe a
+ * range inside [0, P_total] (nothing of that picture is then read or written). */
+typedef struct {
+    int32_t P_total, n_img;        /* people over all pictures / pictures */
+    int32_t J;                     /* joints per person, 1..64 */
+    int32_t soft, rescore;         /* 0 / 1 each */
+    int32_t grid;                  /* workgroups launched; 0 = min(n_img, 4096) */
+    double in_vis_thre, oks_thre;
+    const float* kpts;             /* [P_total,J,3] x, y, maxval */
+    const double* area;            /* [P_total] */
+    const double* box_score;       /* [P_total] */
+    const int32_t* offsets;        /* [n_img+1] */
+    const double* sigmas;          /* [J] */
+    double* score;                 /* [P_total] out */
+    double* work;                  /* [P_total] scratch: the working scores */
+    int32_t* keep;                 /* [P_total] out */
+    int32_t* n_keep;               /* [n_img] out */
+    double* oks_first;             /* [P_total] or NULL: oks of every person (the pick itself included) with the first pick of its picture */
+} fpd_oks_nms_t;
+int fpd_oks_nms(const fpd_oks_nms_t* a, fpd_stream_t stream);
+
 /* ---- execution plan: a recorded list of the ops above, replayed with one call ---- */
 enum {
     FPD_OP_CONV = 0, FPD_OP_WGRAD = 1, FPD_OP_STEM_FWD = 2, FPD_OP_STEM_WGRAD = 3, FPD_OP_EW = 4,

@@ -9,7 +9,8 @@ teacher from the cloned config merged with --tcfg, strict teacher-checkpoint loa
 Adam + MultiStepLR, epoch loop -> core.function.fpd_train -> checkpoint.  What differs: one process per GPU with an
 RCCL gradient all-reduce instead of nn.DataParallel; the models run on the HIP path; DATASET.DATASET 'synthetic'
 (the default) feeds seeded synthetic crops, DATASET.DATASET 'mpii' an MPII directory at DATASET.ROOT, decoded once and
-resident on the device (lib/dataset/mpii.py; COCO is not available), DATASET.DATASET 'synthetic_aug' seeded
+resident on the device (lib/dataset/mpii.py), DATASET.DATASET 'coco' a COCO directory the same way, validated from
+ground-truth or detection boxes with OKS NMS on the device and the keypoint AP table (lib/dataset/coco.py), DATASET.DATASET 'synthetic_aug' seeded
 scenes that are augmented, cropped and labelled on the device per batch (DATASET.FLIP / SCALE_FACTOR / ROT_FACTOR /
 PROB_HALF_BODY / NUM_JOINTS_HALF_BODY, LOSS.USE_DIFFERENT_JOINTS_WEIGHT; lib/dataset/device_dataset.py), and KD.TEACHER 'synthetic' builds a
 random teacher with calibrated BN statistics instead of loading a checkpoint.  LOSS.USE_OHKM of the student config makes
@@ -33,7 +34,7 @@ from fpd_amd import dist as fdist, executor as E, synth  # noqa: E402
 from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import fpd_train, train, validate  # noqa: E402
-from fpd_amd.lib.dataset import SyntheticPose, mpii, synthetic_aug  # noqa: E402
+from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
 from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
                                      save_checkpoint)
@@ -121,14 +122,15 @@ def run(args, normal=False):
         logger.info('=> hard keypoint mining: pose criterion %s, distillation criterion %s',
                     'topk %d' % cfg.LOSS.TOPK if cfg.LOSS.USE_OHKM else 'MSE', 'topk %d' % tcfg.LOSS.TOPK if tcfg.LOSS.USE_OHKM else 'MSE')
 
-    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii'):
-        sys.exit('dataset %r is not available here (CPU-side MPII/COCO pipeline is out of scope); use DATASET.DATASET synthetic'
-                 % cfg.DATASET.DATASET)
+    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii', 'coco'):
+        sys.exit('dataset %r is not available here; use DATASET.DATASET synthetic, synthetic_aug, mpii or coco' % cfg.DATASET.DATASET)
     bs = cfg.TRAIN.BATCH_SIZE_PER_GPU
     if cfg.DATASET.DATASET == 'mpii':
         # DATASET.ROOT decoded once and resident on every rank's device; each rank augments its rank::world share of the
         # epoch's permutation (lib/dataset/mpii.py); the validation set lives on rank 0
         loader, valid_loader, valid_set = mpii(cfg, dev, rank, world)
+    elif cfg.DATASET.DATASET == 'coco':                  # the same for a COCO directory (lib/dataset/coco.py)
+        loader, valid_loader, valid_set = coco(cfg, dev, rank, world)
     elif cfg.DATASET.DATASET == 'synthetic_aug':
         # seeded scenes resident on the device; every batch is augmented there (half-body, scale / rotation jitter, flip),
         # cropped and given its targets by three kernels (lib/dataset/device_dataset.py)

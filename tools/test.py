@@ -8,7 +8,8 @@ TEST.MODEL_FILE (strict=False like the reference, :88-90) or <output dir>/final_
 validation loader, `core.function.validate` (flip test / heat-map shift / post-processing per cfg.TEST).  What differs: the
 model runs on the HIP path of one GPU; DATASET.DATASET 'synthetic' feeds the seeded synthetic validation set of
 tools/fpd_train.py ('synthetic_aug': its validation scenes, cropped on the device), 'mpii' DATASET.ROOT / TEST_SET with the
-PCKh table; COCO is not available."""
+PCKh table, 'coco' DATASET.ROOT / TEST_SET from ground-truth or detection boxes (TEST.USE_GT_BBOX, TEST.COCO_BBOX_FILE) with the
+keypoint AP table."""
 import argparse
 import logging
 import os
@@ -26,7 +27,7 @@ from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import validate  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss  # noqa: E402
-from fpd_amd.lib.dataset import SyntheticPose, mpii, synthetic_aug  # noqa: E402
+from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa: E402
 from fpd_amd.lib.utils.utils import load_checkpoint  # noqa: E402
 
 
@@ -58,11 +59,12 @@ def main():
     model = fdist.DataParallelReplica(model.to(dev))
     criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)          # :101-103
 
-    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii'):
-        sys.exit('dataset %r is not available here (CPU-side MPII/COCO pipeline is out of scope); use DATASET.DATASET synthetic'
-                 % cfg.DATASET.DATASET)
+    if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii', 'coco'):
+        sys.exit('dataset %r is not available here; use DATASET.DATASET synthetic, synthetic_aug, mpii or coco' % cfg.DATASET.DATASET)
     if cfg.DATASET.DATASET == 'mpii':                    # DATASET.ROOT / TEST_SET, resident on the device; PCKh
         _, valid_loader, valid_set = mpii(cfg, dev, train=False)
+    elif cfg.DATASET.DATASET == 'coco':                  # DATASET.ROOT / TEST_SET; OKS NMS on the device, keypoint AP
+        _, valid_loader, valid_set = coco(cfg, dev, train=False)
     elif cfg.DATASET.DATASET == 'synthetic_aug':          # the validation scenes of tools/fpd_train.py, cropped on the device
         _, valid_loader, valid_set = synthetic_aug(cfg, dev, train=False)
     else:
