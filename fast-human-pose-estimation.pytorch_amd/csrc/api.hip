@@ -96,7 +96,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
-    SZ(fpd_oks_nms_t);
+    SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t);
 #undef SZ
     return -1;
 }
@@ -512,6 +512,33 @@ int fpd_oks_nms(const fpd_oks_nms_t* a, fpd_stream_t stream) {
     FPD_REQUIRE((int64_t)a->P_total * a->J * 3 < (1ll << 40), "oks_nms: too many people");
     if (a->n_img == 0) return 0;
     int rc = fpd_oks_nms_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
+int fpd_coco_match(const fpd_coco_match_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->gt_offsets && a->dt_offsets && a->oks_offsets && a->status, "coco_match: null pointer");
+    FPD_REQUIRE(a->n_img >= 0 && a->G_total >= 0 && a->D_total >= 0 && a->grid >= 0 && a->oks_total >= 0,
+                "coco_match: negative size (n_img=%d, G_total=%d, D_total=%d, grid=%d)", a->n_img, a->G_total, a->D_total, a->grid);
+    FPD_REQUIRE(a->J >= 1 && a->J <= 64, "coco_match: J=%d outside 1..64", a->J);
+    FPD_REQUIRE(a->sigmas && a->gt_counted, "coco_match: null pointer (sigmas / gt_counted)");
+    FPD_REQUIRE(a->G_total == 0 || (a->gt_kpts && a->gt_area && a->gt_bbox && a->gt_flags && a->scratch), "coco_match: null pointer (per-gt array)");
+    FPD_REQUIRE(a->D_total == 0 || (a->dt_kpts && a->matched && a->dt_ignored && a->dt_area), "coco_match: null pointer (per-detection array)");
+    FPD_REQUIRE(a->oks_total == 0 || a->oks, "coco_match: null pointer (oks)");
+    FPD_REQUIRE(a->oks_total <= (int64_t)a->G_total * a->D_total, "coco_match: oks_total exceeds G_total * D_total");
+    for (int r = 0; r < FPD_COCO_AREAS; ++r)
+        FPD_REQUIRE(a->area_lo[r] < a->area_hi[r], "coco_match: bad area range %d", r);       // (false for a NaN, and for a struct left at zero)
+    for (int k = 0; k < FPD_COCO_THRS; ++k)
+        FPD_REQUIRE(a->oks_thrs[k] == a->oks_thrs[k], "coco_match: bad threshold %d", k);
+    if (a->n_img == 0) return 0;
+    int rc = fpd_coco_match_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_coco_accumulate(const fpd_coco_accum_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->npig && a->rec_thrs && a->precision && a->recall && a->status, "coco_accumulate: null pointer");
+    FPD_REQUIRE(a->D_total >= 0, "coco_accumulate: negative size (D_total=%d)", a->D_total);
+    FPD_REQUIRE(a->n_rec >= 1 && a->n_rec <= 1024, "coco_accumulate: n_rec=%d outside 1..1024", a->n_rec);
+    FPD_REQUIRE(a->D_total == 0 || (a->matched && a->dt_ignored && a->order && a->tp && a->env), "coco_accumulate: null pointer (per-detection array)");
+    int rc = fpd_coco_accumulate_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 

@@ -112,6 +112,8 @@ int fpd_render_targets_w_launch(const fpd_targets_w_t& a, hipStream_t st);
 int fpd_warp_affine_aug_launch(const fpd_warp_aug_t& a, hipStream_t st);
 int fpd_augment_params_launch(const fpd_augment_t& a, hipStream_t st);
 int fpd_oks_nms_launch(const fpd_oks_nms_t& a, hipStream_t st);
+int fpd_coco_match_launch(const fpd_coco_match_t& a, hipStream_t st);            // csrc/coco_eval.hip
+int fpd_coco_accumulate_launch(const fpd_coco_accum_t& a, hipStream_t st);
 int fpd_elementwise_launch(const fpd_ew_t& a, hipStream_t st);
 int fpd_elementwise_pair_launch(const fpd_ew_t& a, const fpd_ew_t& b, hipStream_t st);
 int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st);

@@ -1,7 +1,7 @@
 """The COCO keypoint dataset (/root/reference/lib/dataset/coco.py): the records of `_get_db` from ground-truth or detection
 boxes, the decoded images resident on the device behind the augmenting loaders (device_dataset.py), and `evaluate`:
 rescoring + OKS NMS of every picture in one launch (csrc/oks_nms.hip through lib/nms/nms.py), the results file, and
-the keypoint AP / AR table (coco_eval.py).
+the keypoint AP / AR table (coco_eval.py: matched and accumulated on the device, csrc/coco_eval.hip).
 
     root/annotations/person_keypoints_<set>.json      (image_info_<set>.json for a test set)
     root/images/<set>/<%012d>.jpg                     ('COCO_<set>_' in front of the number for the 2014 sets; every test
@@ -97,6 +97,7 @@ class COCODataset:
         self.lower_body_ids = (11, 12, 13, 14, 15, 16)
         self.joints_weight = np.array([1., 1., 1., 1., 1., 1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1., 1.2, 1.2, 1.5, 1.5],
                                       dtype=np.float32).reshape((self.num_joints, 1))
+        self._packed_gt = None
         self.db = self._get_db()
         logger.info('=> load {} samples'.format(len(self.db)))
 
@@ -240,9 +241,20 @@ class COCODataset:
         kept = [order[offsets[k] + keep[offsets[k]:offsets[k] + n_keep[k]]] for k in range(len(first))]
         return list(first), kept, rescored
 
+    def packed_ground_truth(self):
+        """The annotations as coco_eval.pack_ground_truth's arrays: made on first use, they do not change between validations."""
+        if self._packed_gt is None:
+            cats = self.coco.category_ids()
+            if len(cats) != 1:
+                raise R.FpdError('COCODataset: the device AP table evaluates exactly one category, the annotations have %d '
+                                 '(evaluate(..., host_eval=True) takes any number)' % len(cats))
+            self._packed_gt = coco_eval.pack_ground_truth(self.coco.annotations, self.coco.image_ids(), cats[0])
+        return self._packed_gt
+
     def evaluate(self, cfg, preds, output_dir, all_boxes, img_path, *args, **kwargs):
         """coco.py:302-379 -> (OrderedDict of the ten statistics, AP); ({'Null': 0}, 0) for a test set.  Writes
-        <output_dir>/results/keypoints_<set>_results_<RANK>.json: picture order, then pick order."""
+        <output_dir>/results/keypoints_<set>_results_<RANK>.json: picture order, then pick order.  The AP table comes from the
+        device (coco_eval.evaluate_arrays_device over the kept people as arrays); host_eval=True: from the numpy functions."""
         res_folder = os.path.join(output_dir, 'results')
         os.makedirs(res_folder, exist_ok=True)
         res_file = os.path.join(res_folder, 'keypoints_{}_results_{}.json'.format(self.image_set, cfg.RANK))
@@ -258,7 +270,12 @@ class COCODataset:
             json.dump(results, f, sort_keys=True, indent=4)
         if 'test' in self.image_set:
             return {'Null': 0}, 0
-        stats = coco_eval.evaluate_keypoints(self.coco.annotations, results, self.coco.image_ids(), self.coco.category_ids())
+        if kwargs.get('host_eval', False):
+            stats = coco_eval.evaluate_keypoints(self.coco.annotations, results, self.coco.image_ids(), self.coco.category_ids())
+        else:
+            rows = np.concatenate(kept).astype(np.int64) if kept else np.zeros(0, np.int64)
+            stats = coco_eval.evaluate_arrays_device(self.packed_ground_truth(), np.repeat(np.asarray(pictures, np.int64), [len(k) for k in kept]),
+                                                     flat[rows], rescored[rows], device=kwargs.get('device', 'cuda'))
         name_value = OrderedDict(zip(coco_eval.STAT_NAMES, [float(v) for v in stats]))
         return name_value, name_value['AP']
 

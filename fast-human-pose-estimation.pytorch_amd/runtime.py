@@ -173,6 +173,19 @@ class OksNmsT(C.Structure):
                 ('sigmas', _vp), ('score', _vp), ('work', _vp), ('keep', _vp), ('n_keep', _vp), ('oks_first', _vp)]
 
 
+class CocoMatchT(C.Structure):
+    _fields_ = [('n_img', _i32), ('J', _i32), ('G_total', _i32), ('D_total', _i32), ('grid', _i32), ('_pad', _i32),
+                ('oks_total', _i64), ('area_lo', _f64 * 3), ('area_hi', _f64 * 3), ('oks_thrs', _f64 * 10), ('gt_kpts', _vp),
+                ('gt_area', _vp), ('gt_bbox', _vp), ('gt_flags', _vp), ('dt_kpts', _vp), ('gt_offsets', _vp), ('dt_offsets', _vp),
+                ('oks_offsets', _vp), ('sigmas', _vp), ('oks', _vp), ('scratch', _vp), ('matched', _vp), ('dt_ignored', _vp),
+                ('gt_counted', _vp), ('dt_area', _vp), ('status', _vp)]
+
+
+class CocoAccumT(C.Structure):
+    _fields_ = [('D_total', _i32), ('n_rec', _i32), ('matched', _vp), ('dt_ignored', _vp), ('order', _vp), ('npig', _vp),
+                ('rec_thrs', _vp), ('tp', _vp), ('env', _vp), ('precision', _vp), ('recall', _vp), ('status', _vp)]
+
+
 class LossT(C.Structure):
     _fields_ = [('B', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('S', _i32), ('dtype', _i32),
                 ('target_nchw', _i32), ('alpha', _f32), ('out', _vp * MAX_STACKS), ('dout', _vp * MAX_STACKS),
@@ -225,7 +238,8 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_conv_f8_t': ConvF8T, 'fpd_wquant_entry_t': WquantEntryT, 'fpd_flipmerge_t': FlipMergeT, 'fpd_finalpreds_t': FinalPredsT, 'fpd_targets_t': TargetsT,
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
-            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT}
+            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
+            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -266,6 +280,8 @@ SYMBOLS = {
     'fpd_warp_affine_aug': (C.c_int, [C.POINTER(WarpAugT), _vp]),
     'fpd_render_targets_w': (C.c_int, [C.POINTER(TargetsWT), _vp]),
     'fpd_oks_nms': (C.c_int, [C.POINTER(OksNmsT), _vp]),
+    'fpd_coco_match': (C.c_int, [C.POINTER(CocoMatchT), _vp]),
+    'fpd_coco_accumulate': (C.c_int, [C.POINTER(CocoAccumT), _vp]),
     'fpd_head_forward': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_head_fold': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_loss': (C.c_int, [C.POINTER(LossT), _vp]),

@@ -675,6 +675,74 @@ typedef struct {
 } fpd_oks_nms_t;
 int fpd_oks_nms(const fpd_oks_nms_t* a, fpd_stream_t stream);
 
+/* ---- COCO keypoint AP (lib/dataset/coco_eval.py): OKS matrix + greedy matching of every picture in one launch ----
+ * One workgroup owns a picture (grid-stride over pictures when `grid` caps the launch).  The gts of picture i are rows
+ * gt_offsets[i] .. gt_offsets[i+1] of the gt arrays, its detections (best score first, the host cuts them to the 20 best) rows
+ * dt_offsets[i] .. dt_offsets[i+1]; its OKS matrix [D_i, G_i] starts at oks[oks_offsets[i]].  Any number of either.
+ *   oks[d,g]  = mean over the gt's annotated joints (v > 0) of exp(-e_j) -- float64, no contraction, summed in joint order --
+ *                 e_j = ((xd-xg)^2 + (yd-yg)^2) / (2 sigma_j)^2 / (area_g + 2^-52) / 2
+ *               a gt without an annotated joint: over every joint, with dx = max(0, x0 - xd) + max(0, xd - x1) (dy alike),
+ *                 [x0, x1] = [bx - bw, bx + 2 bw] the gt box doubled about itself
+ *   dt_area[d] = (max x - min x) * (max y - min y) over the detection's joints
+ *   for each area range r (area_lo[r] .. area_hi[r], both ends inside) and threshold t = oks_thrs[k], independently:
+ *     a gt is ignored when bit 0 of its flags is set or its area lies outside the range; gt_counted[r] counts the others
+ *     the detections in order: best = min(t, 1 - 1e-10); first over the counting gts in their order, then -- only if none
+ *     matched -- over the ignored ones: skip a gt already taken unless bit 1 of its flags (crowd) is set; skip oks < best;
+ *     otherwise best = oks and the gt is the candidate (a tie goes to the later gt).  A candidate: matched = 1, dt_ignored = the
+ *     gt is ignored, the gt is taken.  None: matched = 0, dt_ignored = dt_area[d] outside the range.
+ * status[i] = 0, or -1 if an offset of picture i does not describe a range inside its array (nothing of that picture is then
+ * read or written).  scratch: 31 bytes per gt (the ignore bits and, per (range, threshold), the taken flags of pictures with more
+ * than 64 gts; smaller pictures keep both in registers / LDS). */
+#define FPD_COCO_AREAS 3
+#define FPD_COCO_THRS 10
+typedef struct {
+    int32_t n_img, J;              /* pictures / joints per person, 1..64 */
+    int32_t G_total, D_total;      /* gts / detections over all pictures */
+    int32_t grid, _pad;            /* workgroups launched; 0 = min(n_img, 8192) */
+    int64_t oks_total;             /* elements of oks: the sum of D_i * G_i */
+    double area_lo[FPD_COCO_AREAS], area_hi[FPD_COCO_AREAS];
+    double oks_thrs[FPD_COCO_THRS];
+    const double* gt_kpts;         /* [G_total,J,3] x, y, v */
+    const double* gt_area;         /* [G_total] */
+    const double* gt_bbox;         /* [G_total,4] x, y, w, h */
+    const uint8_t* gt_flags;       /* [G_total] bit 0: ignore (crowd or no annotated joint), bit 1: crowd */
+    const double* dt_kpts;         /* [D_total,J,3] */
+    const int32_t* gt_offsets;     /* [n_img+1] */
+    const int32_t* dt_offsets;     /* [n_img+1] */
+    const int64_t* oks_offsets;    /* [n_img+1] */
+    const double* sigmas;          /* [J] */
+    double* oks;                   /* [oks_total] out */
+    uint8_t* scratch;              /* [31,G_total] */
+    uint8_t* matched;              /* [3,10,D_total] out */
+    uint8_t* dt_ignored;           /* [3,10,D_total] out */
+    int32_t* gt_counted;           /* [3,n_img] out */
+    double* dt_area;               /* [D_total] out */
+    int32_t* status;               /* [n_img] out */
+} fpd_coco_match_t;
+int fpd_coco_match(const fpd_coco_match_t* a, fpd_stream_t stream);
+
+/* The precision / recall tables of those flags: one workgroup per (area range, threshold).  order[i] = the detection at rank i
+ * of the stable descending sort of the scores; per rank tp = the running count of matched & ~ignored, fp of ~matched & ~ignored;
+ *   rc = tp / npig[r], pr = tp / (fp + tp + 2^-52) made non-increasing from the right (suffix maximum);
+ *   precision[k][q][r] = pr at the leftmost rank with rc >= rec_thrs[q], 0 past the end; recall[k][r] = the last rc, 0 without
+ *   detections; both -1 where npig[r] == 0.
+ * Counts are integers and a maximum is exact: equal flags give tables bit-equal to coco_eval.accumulate's.
+ * status[r*10+k] = 0, or -1 if `order` held an index outside [0, D_total) (such a rank counts as ignored). */
+typedef struct {
+    int32_t D_total, n_rec;        /* detections / recall thresholds, 1..1024 */
+    const uint8_t* matched;        /* [3,10,D_total] */
+    const uint8_t* dt_ignored;     /* [3,10,D_total] */
+    const int32_t* order;          /* [D_total] */
+    const int32_t* npig;           /* [3] */
+    const double* rec_thrs;        /* [n_rec] rising */
+    int32_t* tp;                   /* [3,10,D_total] scratch: tp per rank */
+    double* env;                   /* [3,10,D_total] scratch: pr, then its envelope */
+    double* precision;             /* [10,n_rec,3] out */
+    double* recall;                /* [10,3] out */
+    int32_t* status;               /* [30] out */
+} fpd_coco_accum_t;
+int fpd_coco_accumulate(const fpd_coco_accum_t* a, fpd_stream_t stream);
+
 /* ---- execution plan: a recorded list of the ops above, replayed with one call ---- */
 enum {
     FPD_OP_CONV = 0, FPD_OP_WGRAD = 1, FPD_OP_STEM_FWD = 2, FPD_OP_STEM_WGRAD = 3, FPD_OP_EW = 4,
