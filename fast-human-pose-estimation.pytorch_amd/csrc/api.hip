@@ -84,6 +84,7 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c3_blocks")) return fpd_conv_c3_option(1, value);
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);
     if (!strcmp(name, "bneck_blocks")) return fpd_bneck_blocks_option(value);
+    if (!strcmp(name, "bneck_upadd")) return fpd_bneck_upadd_option(value);          // up-add formed on load (fpd_bneck_t.x2) offered at all
     if (!strcmp(name, "head_blocks")) return fpd_head_blocks_option(value);
     if (!strcmp(name, "wgrad_tile_only")) { g_wgrad_tile_only = value; return 0; }
     return fpd_fail(-2, "set_option: unknown option '%s'", name);
@@ -266,6 +267,7 @@ int fpd_bottleneck_forward_pair(const fpd_bneck_pair_t* p, fpd_stream_t stream) 
     const fpd_bneck_t* ab[2] = {&p->a, &p->b};
     for (const fpd_bneck_t* a : ab) {
         FPD_REQUIRE(a->x && a->y && a->w1 && a->w2 && a->w3 && a->x != a->y, "bottleneck_pair: null pointer or y aliases x");
+        FPD_REQUIRE(a->x2 == nullptr, "bottleneck_pair: a pair launch takes no low-branch source (x2)");
         FPD_REQUIRE((int64_t)a->N * a->H * a->W * a->C < ((int64_t)1 << 31), "bottleneck_pair: tensor too large for 32-bit indexing");
         int rc = validate_bneck_bns(a);
         if (rc) return rc;
@@ -285,12 +287,20 @@ int fpd_bottleneck_forward(const fpd_bneck_t* a, fpd_stream_t stream) {
     FPD_REQUIRE((int64_t)a->N * a->H * a->W * a->C < ((int64_t)1 << 31), "bottleneck: tensor too large for 32-bit indexing");
     int rc = validate_bneck_bns(a);
     if (rc) return rc;
+    if (a->x2 != nullptr) {              // up-add on load: refused here, before any HIP call
+        const char* why = fpd_bneck_upadd_why_not(*a);
+        if (why) return fpd_fail(-3, "bottleneck: low-branch source (x2) with N=%d H=%d W=%d C=%d P=%d: %s; fpd_bneck_upadd_supported() reports 0 for it",
+                                 a->N, a->H, a->W, a->C, a->P, why);
+        FPD_REQUIRE(a->x2 != a->y, "bottleneck: y must not alias x2");
+    }
     rc = fpd_bneck_fused_launch(*a, (hipStream_t)stream);
     if (rc == 1)
         return fpd_fail(-3, "bottleneck: shape N=%d H=%d W=%d C=%d P=%d dtype=%d is outside the fused kernel's domain",
                         a->N, a->H, a->W, a->C, a->P, a->dtype);
     return rc ? rc : check_launch();
 }
+
+int fpd_bneck_upadd_supported(const fpd_bneck_t* a) { return (a && fpd_bneck_upadd_why_not(*a) == nullptr) ? 1 : 0; }
 
 // ---- weight-gradient backends, in dispatch order; partials: slabs the launch writes (0: it declines) ----
 struct WgradBackend {
@@ -762,7 +772,7 @@ static void set_op_tag(int idx, const fpd_op& o) {
             break;
         }
         case FPD_OP_WGRAD: snprintf(t, sizeof(t), "wgrad N=%d H=%d W=%d C=%d K=%d R=%d s=%d", o.u.wgrad.N, o.u.wgrad.H, o.u.wgrad.W, o.u.wgrad.C, o.u.wgrad.K, o.u.wgrad.R, o.u.wgrad.stride); break;
-        case FPD_OP_BNECK: snprintf(t, sizeof(t), "bneck N=%d H=%d W=%d C=%d P=%d", o.u.bneck.N, o.u.bneck.H, o.u.bneck.W, o.u.bneck.C, o.u.bneck.P); break;
+        case FPD_OP_BNECK: snprintf(t, sizeof(t), "bneck N=%d H=%d W=%d C=%d P=%d%s", o.u.bneck.N, o.u.bneck.H, o.u.bneck.W, o.u.bneck.C, o.u.bneck.P, o.u.bneck.x2 ? "+upadd" : ""); break;
         case FPD_OP_BNECK_PAIR: snprintf(t, sizeof(t), "bneck2 N=%d H=%d W=%d C=%d P=%d | H=%d W=%d", o.u.bpair.a.N, o.u.bpair.a.H, o.u.bpair.a.W, o.u.bpair.a.C, o.u.bpair.a.P, o.u.bpair.b.H, o.u.bpair.b.W); break;
         case FPD_OP_HEAD: snprintf(t, sizeof(t), "head N=%d H=%d W=%d C=%d J=%d", o.u.head.N, o.u.head.H, o.u.head.W, o.u.head.C, o.u.head.J); break;
         case FPD_OP_EW: snprintf(t, sizeof(t), "ew %s N=%d H=%d W=%d C=%d", ewn(o.u.ew.op), o.u.ew.N, o.u.ew.H, o.u.ew.W, o.u.ew.C); break;

@@ -22,7 +22,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -69,7 +69,12 @@ __global__ void bneck_fold_kernel(const fpd_bneck_t a, float* out) { bneck_fold_
 // ds_write pass): ring rows are unpadded (the DMA destination is lane-linear, 1 KiB per wave instruction) and bank
 // conflicts are avoided by an XOR swizzle of the 16-byte chunks applied on the per-lane SOURCE address and again on
 // the fragment reads (chunk c of row r sits at position c ^ sw(r)).
-template <int P, bool DMA>
+// UPADD: x is not a tensor but the sum the hourglass forms in front of this Bottleneck, x[p] = round_bf16(up1[p] + low[p / 2])
+// (hourglass.py:80-92) with up1 = a.x and low = a.x2 at half resolution.  Both places that read x -- the phase-A staging and the
+// residual rows of the epilogue -- load the two sources and round their fp32 sum to bf16 once, which is bit for bit what the
+// stand-alone FPD_EW_UPADD_FWD launch stored: the 2 x [N,H,W,C] round trip of that tensor through HBM is gone.  The low pixel of
+// global image row g (= n*H + row; H and n*H are even), column j is row g >> 1, column j >> 1 of the [N*H/2][W/2] grid.
+template <int P, bool DMA, bool UPADD>
 __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int logW, const int swz, const int bid_in,
                                                 const int nblk, const int ntiles) {
     constexpr int C = 2 * P;
@@ -123,6 +128,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     bf16_t* sA2 = reinterpret_cast<bf16_t*>(s_b3 + C);
     bf16_t* sR2 = sA2 + (zero_px + 3) * LD2;     // 3 zero pixels: the column tap offset is added to a redirected address too
     const bf16_t* __restrict__ x = reinterpret_cast<const bf16_t*>(a.x);
+    const bf16_t* __restrict__ x2 = reinterpret_cast<const bf16_t*>(UPADD ? a.x2 : nullptr);
     const bf16_t* __restrict__ w1 = reinterpret_cast<const bf16_t*>(a.w1);
     const bf16_t* __restrict__ w2 = reinterpret_cast<const bf16_t*>(a.w2);
     const bf16_t* __restrict__ w3 = reinterpret_cast<const bf16_t*>(a.w3);
@@ -134,6 +140,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     int npass = whole ? 1 : ((hrows * W + 127) >> 7);
     const int xpx = tid >> 3, xcv = (tid & 7) * 8;       // this thread stages pixels xpx, xpx+64, channels xcv..+7
     int xo[2];                                           // element offsets of the two pixels in the pass being loaded
+    int xo2[UPADD ? 2 : 1];                              // UPADD: the same for their low-branch pixels
     bool xok[2];
     auto pass_addr = [&](int p) __attribute__((always_inline)) {
 #pragma unroll
@@ -143,6 +150,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
             const int g = g0 - 1 + hr;
             xok[i] = hr < hrows && (unsigned)g < (unsigned)GR;
             xo[i] = xok[i] ? (g * W + j) * C + xcv : 0;
+            if constexpr (UPADD) xo2[i] = xok[i] ? ((((g >> 1) << logW) >> 1) + (j >> 1)) * C + xcv : 0;
         }
     };
     int w1o[W1V], w1l[W1V];
@@ -155,6 +163,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     const int xl = xpx * LDX + xcv;
 
     u32x4 rx[NCH][2], rw[NCH][W1V];
+    u32x4 rx2[UPADD ? NCH : 1][2];
     auto a_load = [&](auto kcc) __attribute__((always_inline)) {
         constexpr int kc = decltype(kcc)::value;
         static_for<2>([&](auto ic) {
@@ -162,11 +171,31 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
             const u32x4 z = {0u, 0u, 0u, 0u};
             rx[kc][i] = z;
             if (xok[i]) rx[kc][i] = *reinterpret_cast<const u32x4*>(x + (xo[i] + kc * 64));
+            if constexpr (UPADD) {
+                rx2[kc][i] = z;
+                if (xok[i]) rx2[kc][i] = *reinterpret_cast<const u32x4*>(x2 + (xo2[i] + kc * 64));
+            }
         });
         static_for<W1V>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             rw[kc][i] = *reinterpret_cast<const u32x4*>(w1 + (w1o[i] + kc * 64));
         });
+    };
+    // UPADD: vector i of slot kc becomes x = round(up1 + low), as the up-add launch stored it; a_store_slice then stages rx as
+    // it always did.  The sums are VALU work like the staging and ride behind the MFMAs of the chunk steps in the same way (below).
+    auto a_sum = [&](auto kcc, auto ic) __attribute__((always_inline)) {
+        constexpr int kc = decltype(kcc)::value, i = decltype(ic)::value;
+        if constexpr (UPADD) {
+            float v[8], u[8];
+            const u32x4 r = rx[kc][i], r2 = rx2[kc][i];
+            DT<bf16_t>::unpack(make_uint4(r[0], r[1], r[2], r[3]), v);
+            DT<bf16_t>::unpack(make_uint4(r2[0], r2[1], r2[2], r2[3]), u);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = v[e] + u[e];
+            const uint4 o = DT<bf16_t>::pack(v);
+            const u32x4 ov = {o.x, o.y, o.z, o.w};
+            rx[kc][i] = ov;
+        }
     };
     // staging of chunk kc in NSL = 2 + W1V slices (x vector 0, x vector 1, then the w1 vectors): the chunk loop places one
     // slice behind the MFMAs of each k-step, so that the VALU / LDS-store work of the next chunk runs while the matrix
@@ -304,6 +333,9 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
             *reinterpret_cast<uint4*>(sA2 + px * LD2 + cv) = z;
         }
     }
+    // (UPADD) chunk 0 of the tile's first loads is staged right below: summed here.  Chunks 1.. follow in the chunk steps.
+    a_sum(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    a_sum(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
     STAMP(1);
 
     // =========================== phase A: conv1 over the halo rows ===========================
@@ -332,15 +364,15 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
         static_for<NCH>([&](auto kcc) {
             constexpr int kc = decltype(kcc)::value;
             // slice sl of the staging of the NEXT chunk (next pass's chunk 0 behind the last chunk) + the refill of its slot
-            auto stage_slice = [&](auto slc) __attribute__((always_inline)) {
-                constexpr int sl = decltype(slc)::value;
+            auto stage_slice = [&](auto slc, auto lastc) __attribute__((always_inline)) {
+                constexpr bool last = decltype(lastc)::value;
                 if constexpr (kc + 1 < NCH) {
                     a_store_slice(std::integral_constant<int, (kc + 1) % NCH>{}, slc);
-                    if constexpr (sl == NSL - 1) refill(std::integral_constant<int, (kc + 1) % NCH>{}, p);
+                    if constexpr (last) refill(std::integral_constant<int, (kc + 1) % NCH>{}, p);
                 } else {
                     if (p + 1 < npass) {
                         a_store_slice(std::integral_constant<int, 0>{}, slc);
-                        if constexpr (sl == NSL - 1) {
+                        if constexpr (last) {
                             if (p + 2 < npass) pass_addr(p + 2);               // (never taken: npass <= 2)
                             refill(std::integral_constant<int, 0>{}, p + 1);
                         }
@@ -357,7 +389,23 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
                     const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wrow + tn * 32 * LDX + kk * 16);
                     acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, px, acc[tn], 0, 0, 0);
                 }
-                stage_slice(kkc);                                              // NSL <= 4 slices, one per k-step
+                if constexpr (!UPADD) {
+                    stage_slice(kkc, std::integral_constant<bool, kk == NSL - 1>{});      // NSL <= 4 slices, one per k-step
+                } else {
+                    // the x vectors of the next chunk are summed behind k-steps 0 and 1 and staged behind 2 and 3, the w1 vectors
+                    // go first.  Slots of the tile's first loads are summed here, just before their staging (pass 0, chunks 1..);
+                    // a slot refilled for the next pass is summed one step after its request (the barrier has drained it): slot
+                    // kc behind k-steps 2 and 3 of this step.
+                    if constexpr (kk < 2) {
+                        if constexpr (kc + 1 < NCH) {
+                            if (p == 0) a_sum(std::integral_constant<int, (kc + 1) % NCH>{}, kkc);
+                        }
+                        stage_slice(std::integral_constant<int, (kk + 2 < NSL ? kk + 2 : NSL)>{}, std::false_type{});
+                    } else {
+                        stage_slice(std::integral_constant<int, kk - 2>{}, std::integral_constant<bool, kk == 3>{});
+                        if (p + 1 < npass) a_sum(kcc, std::integral_constant<int, kk - 2>{});
+                    }
+                }
             });
             __syncthreads();
             ASTAMP();
@@ -435,6 +483,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     constexpr int VW = CW / 8;                   // output vectors per pixel row of this wave's channel slice
     constexpr int NIT = 32 * VW / 64;
     u32x4 rres[2][NIT];
+    u32x4 rres2[UPADD ? NIT : 1];                // UPADD: the low-branch vectors of the rows requested last, until res_sum folds them in
     auto res_load = [&](auto stc) __attribute__((always_inline)) {
         constexpr int st = decltype(stc)::value;
         static_for<NIT>([&](auto itc) {
@@ -445,6 +494,43 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
             const u32x4 z = {0u, 0u, 0u, 0u};
             rres[st][it] = z;
             if (m < M) rres[st][it] = *reinterpret_cast<const u32x4*>(x + ((size_t)m * C + st * P + hC * CW + cv));
+            if constexpr (UPADD) {
+                const int g = m >> logW, j = m & (W - 1);
+                const int m2 = (((g >> 1) << logW) >> 1) + (j >> 1);
+                rres2[it] = z;
+                if (m < M) rres2[it] = *reinterpret_cast<const u32x4*>(x2 + ((size_t)m2 * C + st * P + hC * CW + cv));
+            }
+        });
+    };
+    // UPADD: the residual is the same rounded sum that phase A staged.  Formed one pipeline step after the request (the barrier
+    // in between has drained the loads), behind the MFMAs of that step; the epilogue then reads rres as it always did.
+    auto res_sum = [&](auto stc, auto itc) __attribute__((always_inline)) {
+        constexpr int st = decltype(stc)::value, it = decltype(itc)::value;
+        if constexpr (UPADD && it < NIT) {
+            float v[8], u[8];
+            const u32x4 r = rres[st][it], r2 = rres2[it];
+            DT<bf16_t>::unpack(make_uint4(r[0], r[1], r[2], r[3]), v);
+            DT<bf16_t>::unpack(make_uint4(r2[0], r2[1], r2[2], r2[3]), u);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = v[e] + u[e];
+            const uint4 o = DT<bf16_t>::pack(v);
+            const u32x4 ov = {o.x, o.y, o.z, o.w};
+            rres[st][it] = ov;
+        }
+    };
+    // UPADD, steps 9 and 10: the same MFMA sequence with one residual vector summed behind each of the first NIT k-steps
+    auto mma_sum = [&](const bf16_t* arow, int buf, f32x16* acc, auto stc) __attribute__((always_inline)) {
+        const bf16_t* wbase = sR2 + buf * P * LDW + (hC * CW + (lane & 31)) * LDW;
+        static_for<P / 16>([&](auto kkc) {
+            constexpr int kk = decltype(kkc)::value;
+            const bf16x8 px = *reinterpret_cast<const bf16x8*>(arow + kk * 16);
+            const int wo = DMA ? (((2 * kk + (lane >> 5)) ^ wsw) * 8) : (kk * 16 + koff);
+#pragma unroll
+            for (int tn = 0; tn < TNH; ++tn) {
+                const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wbase + tn * 32 * LDW + wo);
+                acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, px, acc[tn], 0, 0, 0);
+            }
+            res_sum(stc, kkc);
         });
     };
 
@@ -460,7 +546,8 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
             for (int tn = 0; tn < TNH; ++tn)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) accC[s - 9][tn][i] = 0.f;
-            mma(sA2 + (a3px + ml) * LD2 + koff, s & 1, accC[s - 9]);          // a3 aliases the dead half of a2: [128 px][LD2]
+            if constexpr (UPADD) mma_sum(sA2 + (a3px + ml) * LD2 + koff, s & 1, accC[s - 9], std::integral_constant<int, s - 9>{});
+            else mma(sA2 + (a3px + ml) * LD2 + koff, s & 1, accC[s - 9]);     // a3 aliases the dead half of a2: [128 px][LD2]
         }
         if constexpr (s + 1 < NSTEP) {
             t_store(std::integral_constant<int, s + 1>{});
@@ -544,9 +631,9 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
 #endif
 }
 
-template <int P, bool DMA>
+template <int P, bool DMA, bool UPADD>
 __global__ __launch_bounds__(512, 1) void bneck_eval_kernel(const fpd_bneck_t a, const int logW, const int ntiles) {
-    bneck_eval_body<P, DMA>(a, logW, (ntiles & 7) == 0, blockIdx.x, gridDim.x, ntiles);
+    bneck_eval_body<P, DMA, UPADD>(a, logW, (ntiles & 7) == 0, blockIdx.x, gridDim.x, ntiles);
 }
 
 // Two independent fused Bottlenecks (the up-branch and the low-branch one of an hourglass level) in one launch.
@@ -554,8 +641,8 @@ template <int P, bool DMA>
 __global__ __launch_bounds__(512, 1) void bneck_eval_pair_kernel(const fpd_bneck_t a, const fpd_bneck_t b, const int logWa,
                                                                  const int logWb, const int nblk_a, const int ntiles_a,
                                                                  const int ntiles_b) {
-    if ((int)blockIdx.x < nblk_a) bneck_eval_body<P, DMA>(a, logWa, (ntiles_a & 7) == 0, blockIdx.x, nblk_a, ntiles_a);
-    else bneck_eval_body<P, DMA>(b, logWb, (ntiles_b & 7) == 0, (int)blockIdx.x - nblk_a, (int)gridDim.x - nblk_a, ntiles_b);
+    if ((int)blockIdx.x < nblk_a) bneck_eval_body<P, DMA, false>(a, logWa, (ntiles_a & 7) == 0, blockIdx.x, nblk_a, ntiles_a);
+    else bneck_eval_body<P, DMA, false>(b, logWb, (ntiles_b & 7) == 0, (int)blockIdx.x - nblk_a, (int)gridDim.x - nblk_a, ntiles_b);
 }
 
 // (The register path of the weight tiles -- DMA = false, round 1, selectable through FPD_BNECK_DMA until round 5 -- is no longer
@@ -615,13 +702,13 @@ int launch_bneck_pair(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st
     return 0;
 }
 
-template <int P, bool DMA>
+template <int P, bool DMA, bool UPADD>
 int launch_bneck(const fpd_bneck_t& a, int logW, hipStream_t st) {
     const size_t lds = bneck_lds_bytes<P>(a.H, a.W);
     static LdsAttr configured;        // per device, set once (thread-safe: common.h)
-    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&bneck_eval_kernel<P, DMA>), lds)) return rc_;
+    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&bneck_eval_kernel<P, DMA, UPADD>), lds)) return rc_;
     const int ntiles = cdiv(a.N * a.H * a.W, 128);
-    FPD_LAUNCH((bneck_eval_kernel<P, DMA>), dim3(bneck_blocks(ntiles, bneck_block_cap())), dim3(512), lds, st, a, logW, ntiles);
+    FPD_LAUNCH((bneck_eval_kernel<P, DMA, UPADD>), dim3(bneck_blocks(ntiles, bneck_block_cap())), dim3(512), lds, st, a, logW, ntiles);
     return 0;
 }
 
@@ -641,17 +728,35 @@ static bool bneck_in_domain(const fpd_bneck_t& a) {
     return hw % 128 == 0 || 128 % hw == 0;                    // a tile is whole rows of one image, or whole images
 }
 
+// ---- up-add on load (fpd_bneck_t.x2) ----
+static EnvOpt g_bneck_upadd{"FPD_BNECK_UPADD", 1};
+int fpd_bneck_upadd_option(int value) { return g_bneck_upadd.set(value < 0 ? 0 : value); }
+
+// nullptr = a launch of these dimensions with a low-branch source is served, else the reason.  Dimensions, dtype and the option
+// only: the lowering asks before memory is planned.  (Up-add results are never 4 wide: their low branch is at least 4 x 4.)
+const char* fpd_bneck_upadd_why_not(const fpd_bneck_t& a) {
+    if (g_bneck_upadd.get() == 0) return "switched off (FPD_BNECK_UPADD=0 / option bneck_upadd)";
+    if (!bneck_in_domain(a)) return "the shape is outside the fused kernel's domain";
+    if (a.W < 8) return "W must be one of 8, 16, 32, 64";
+    if (a.H & 1) return "H must be even";
+    return nullptr;
+}
+
 // 0 = launched, 1 = shape outside this kernel's domain, <0 = error
 int fpd_bneck_fused_launch(const fpd_bneck_t& a, hipStream_t st) {
     if (!bneck_in_domain(a)) return 1;
     int logW = 0;
     while ((1 << logW) < a.W) ++logW;
-    return a.P == 128 ? launch_bneck<128, true>(a, logW, st) : launch_bneck<64, true>(a, logW, st);
+    if (a.x2 != nullptr) {
+        if (fpd_bneck_upadd_why_not(a) != nullptr) return 1;      // (api.hip refused it with the reason already)
+        return a.P == 128 ? launch_bneck<128, true, true>(a, logW, st) : launch_bneck<64, true, true>(a, logW, st);
+    }
+    return a.P == 128 ? launch_bneck<128, true, false>(a, logW, st) : launch_bneck<64, true, false>(a, logW, st);
 }
 
 // 0 = both launched as one kernel, 1 = not pairable (caller launches them one by one)
 int fpd_bneck_fused_pair_launch(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st) {
-    if (!bneck_in_domain(a) || !bneck_in_domain(b) || a.P != b.P) return 1;
+    if (!bneck_in_domain(a) || !bneck_in_domain(b) || a.P != b.P || a.x2 != nullptr || b.x2 != nullptr) return 1;
     return a.P == 128 ? launch_bneck_pair<128, true>(a, b, st) : launch_bneck_pair<64, true>(a, b, st);
 }
 

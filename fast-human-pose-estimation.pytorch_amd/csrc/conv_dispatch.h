@@ -100,6 +100,9 @@ int fpd_stem_wgrad_launch(const fpd_stem_t& a, hipStream_t st);
 int fpd_bneck_fused_launch(const fpd_bneck_t& a, hipStream_t st);
 int fpd_bneck_fused_pair_launch(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st);
 int fpd_bneck_fold_launch(const fpd_bneck_t& a, float* out, hipStream_t st);
+// up-add formed on load (fpd_bneck_t.x2): nullptr = dimensions served, else the reason; the launch walks the same decision
+const char* fpd_bneck_upadd_why_not(const fpd_bneck_t& a);
+int fpd_bneck_upadd_option(int value);      // >= 0: set; returns the previous value
 int fpd_head_fused_launch(const fpd_head_t& a, hipStream_t st);
 int fpd_head_fold_launch(const fpd_head_t& a, float* out, hipStream_t st);
 int fpd_pck_launch(const fpd_pck_t& a, hipStream_t st);

@@ -380,6 +380,40 @@ class Lowering:
             op.act_active = ok
             ae.stem_fused = ok
 
+    @staticmethod
+    def plan_upadd(ops, readers=None, dtype=R.BF16):
+        """Decide, BEFORE memory is planned, which up-adds of a frozen graph are formed on load by the fused Bottleneck that reads
+        them (include/fpd_amd.h: fpd_bneck_t.x2): the up-add produces no statistics, its result has exactly one reader (among
+        `readers`, default `ops`) and that reader is a single fused Bottleneck on the same lane (not a member of a 'bneck2'), the
+        knob FPD_BNECK_UPADD is on and the library serves the dimensions.  The Bottleneck then names both sources as its inputs
+        (`x`, `x2`; `upadd_op` keeps the relation), the up-add is `upadd_absorbed`: it accesses nothing, is lowered as a no-op and
+        its result is never allocated.  A train-mode graph has no fused Bottlenecks (and its up-adds feed statistics): none
+        qualifies.  Returns the number absorbed."""
+        if os.environ.get('FPD_BNECK_UPADD', '1') == '0':
+            return 0
+        readers = ops if readers is None else readers
+        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
+        n = 0
+        for op in ops:
+            if op is None or op.kind != 'bneck' or getattr(op, 'x2', None) is not None:
+                continue
+            ua = getattr(op.x, 'producer', None)
+            if ua is None or ua.kind != 'ew' or ua.op != 'upadd_fwd' or ua.out_stats is not None or op.x.stats is not None:
+                continue
+            if ua.y is not op.x or op.x.persistent or not any(o is ua for o in ops) or (op.lane or 0) != (ua.lane or 0):
+                continue
+            rd = [o for top in readers if top is not None for o in members_of(top) if any(t is op.x for t in o.acts_in())]
+            if len(rd) != 1 or rd[0] is not op:
+                continue
+            s = R.BneckT()
+            (s.N, s.H, s.W, s.C, s.P), s.dtype = op.dims, dtype
+            if R.lib().fpd_bneck_upadd_supported(C.byref(s)) != 1:
+                continue
+            op.upadd_op, op.x, op.x2 = ua, ua.x, ua.x2
+            ua.upadd_absorbed = True
+            n += 1
+        return n
+
     def _fill_fold(self, op, s):
         """Fold fields of a data gradient that evaluates its BN-backward apply itself (plan_folds decided)."""
         if not getattr(op, 'fold_active', False):
@@ -429,6 +463,12 @@ class Lowering:
         s.w1, s.b1, s.w2, s.b2, s.w3, s.b3 = p(op.w1), p(op.b1), p(op.w2), p(op.b2), p(op.w3), p(op.b3)
         s.bn1, s.bn2, s.bn3 = self.bn(op.bn1), self.bn(op.bn2), self.bn(op.bn3)
         s.folded = p(getattr(op, 'folded', None))
+        x2 = getattr(op, 'x2', None)
+        if x2 is not None:                                 # up-add on load (plan_upadd): y overlaps neither source in the arena
+            yb = _abuf(op.y)
+            for t in (_abuf(op.x), _abuf(x2)):
+                assert t.arena != yb.arena or t.off + t.numel <= yb.off or yb.off + yb.numel <= t.off, 'bneck: y overlaps a source of its up-add'
+            s.x2 = p(_abuf(x2))
         return R.OP_BNECK, s
 
     def head(self, op):
@@ -526,6 +566,8 @@ class Lowering:
 
     def ew(self, op, plain=False):
         if not plain and getattr(op, 'ewm_absorbed', False):   # evaluated inside the pool-backward op that reads it (plan_ew_merge)
+            return R.OP_NOP, R.MemsetT()
+        if getattr(op, 'upadd_absorbed', False):           # formed on load by the fused Bottleneck that reads it (plan_upadd)
             return R.OP_NOP, R.MemsetT()
         if not plain and getattr(op, 'ewm_kind', None) is not None:
             return self.ew_merge(op)
@@ -705,6 +747,8 @@ class GraphInstance:
         delay = int(os.environ.get('FPD_REUSE_DELAY', '400')) if self.lanes_enabled else 0
         if not self.train:
             delay = 0
+        if not self.train and self.dtype == R.BF16:
+            self.low.plan_upadd(g.fwd, readers=ops, dtype=self.dtype)      # before planning: lifetimes are right by construction
         act = G.plan_memory(ops, reuse_delay=delay)
         self.act_elems = act
         self.A.alloc('act', act)

@@ -136,8 +136,8 @@ class Op:
             rd = [b(self.y0), b(self.x), self.w_fc, self.b_fc, self.w_score, self.b_score, self.w_fc2, self.b_fc2,
                   self.w_score2, self.b_score2] + bn_bufs(self.bn)
             wr = [b(self.score), b(self.next)]
-        elif k == 'bneck':
-            rd = [b(self.x), self.w1, self.b1, self.w2, self.b2, self.w3, self.b3] + bn_bufs(self.bn1) + \
+        elif k == 'bneck':                     # (x2: the low branch of an up-add it forms on load, executor.plan_upadd)
+            rd = [b(self.x), b(getattr(self, 'x2', None)), self.w1, self.b1, self.w2, self.b2, self.w3, self.b3] + bn_bufs(self.bn1) + \
                 bn_bufs(self.bn2) + bn_bufs(self.bn3)
             wr = [b(self.y)]
         elif k == 'wgrad':
@@ -163,6 +163,8 @@ class Op:
         elif k == 'stem_wgrad':
             rd, wr = [self.image, b(self.dy)], [self.dw, self.dbias]
         elif k == 'ew':
+            if getattr(self, 'upadd_absorbed', False):           # formed on load by the fused Bottleneck that reads it: accesses nothing
+                return [], []
             rd = [b(self.x), b(self.x2), b(self.dy), b(self.add)] + bn_bufs(self.bn)
             wr = [b(self.y), self.out_stats, self.bstats, self.dgamma, self.dbeta]    # bstats: produced or consumed
             if getattr(self, 'ewm_kind', None) is not None:      # a pool backward that evaluates its BN-backward apply(s) itself
@@ -179,6 +181,8 @@ class Op:
             return self.a.acts_in() + self.b.acts_in()
         if self.kind == 'head':
             return [t for t in (self.y0, self.x) if t is not None]
+        if getattr(self, 'upadd_absorbed', False):         # its sources are inputs of the Bottleneck, its result does not exist
+            return []
         fa = getattr(self, 'fold_apply', None)
         folded = [t for t in (fa.x, fa.dy) if isinstance(t, Act)] if fa is not None else []
         sc = getattr(self, 'skip_conv', None)              # (conservatively, whatever the lowering decides: x stays alive up to conv3)
@@ -192,6 +196,8 @@ class Op:
             return self.a.acts_out() + self.b.acts_out()
         if self.kind == 'head':
             return [t for t in (self.score, self.next) if t is not None]
+        if getattr(self, 'upadd_absorbed', False):
+            return []
         ae = getattr(self, 'act_ew', None)                 # (conservatively: the activation's buffer exists when the stem runs)
         return [getattr(self, f) for f in ('y',) if isinstance(getattr(self, f, None), Act)] + \
                [a for a in getattr(self, 'extra_out', []) if a is not None] + ([ae.y] if ae is not None else [])

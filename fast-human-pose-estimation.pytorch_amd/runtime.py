@@ -56,7 +56,7 @@ class ConvPairT(C.Structure):
 class BneckT(C.Structure):
     _fields_ = [('N', _i32), ('H', _i32), ('W', _i32), ('C', _i32), ('P', _i32), ('dtype', _i32), ('_pad', _i32 * 2),
                 ('x', _vp), ('y', _vp), ('w1', _vp), ('b1', _vp), ('w2', _vp), ('b2', _vp), ('w3', _vp), ('b3', _vp),
-                ('bn1', BnT), ('bn2', BnT), ('bn3', BnT), ('folded', _vp)]
+                ('bn1', BnT), ('bn2', BnT), ('bn3', BnT), ('folded', _vp), ('x2', _vp)]
 
 
 class BneckPairT(C.Structure):
@@ -253,6 +253,7 @@ SYMBOLS = {
     'fpd_bottleneck_forward': (C.c_int, [C.POINTER(BneckT), _vp]),
     'fpd_bottleneck_fold': (C.c_int, [C.POINTER(BneckT), _vp]),
     'fpd_bottleneck_forward_pair': (C.c_int, [C.POINTER(BneckPairT), _vp]),
+    'fpd_bneck_upadd_supported': (C.c_int, [C.POINTER(BneckT)]),
     'fpd_conv_fused_wgrad_partials': (C.c_int, [C.POINTER(ConvT)]),
     'fpd_conv_fold_supported': (C.c_int, [_vp]),
     'fpd_conv_pair_fold_supported': (C.c_int, [_vp]),

@@ -138,7 +138,13 @@ typedef struct {
  * conv2 3x3 P->P pad 1, conv3 1x1 P->C.  Both P-channel intermediates stay in LDS (rounded to bf16 once, after
  * bias+BN+ReLU).  Domain: dtype BF16, C == 2P, P in {64,128}, W a power of two in [4,64], H*W a multiple or a divisor
  * of 128, every BN in EVAL mode; fpd_bottleneck_forward() returns an error outside it (callers then issue the three
- * fpd_conv_forward() calls). */
+ * fpd_conv_forward() calls).
+ * UP-ADD ON LOAD (optional, x2 != NULL): the Bottleneck that follows an hourglass level's `up1 + up(low)` (hourglass.py:80-92)
+ * forms that sum where it reads its input instead of reading a tensor a FPD_EW_UPADD_FWD launch materialised:
+ *     x'[n,i,j,:] = round(x[n,i,j,:] + x2[n,i/2,j/2,:]),   y = x' + conv3(...(bn1(x')))
+ * exactly the two launches it replaces, the rounding of the sum included.  Domain: the one above with W in {8,16,32,64} and H
+ * even; y aliases neither source; no pair launch.  fpd_bneck_upadd_supported() tells whether such a launch is served (0: leave
+ * x2 NULL and issue the two launches). */
 typedef struct {
     int32_t N, H, W, C, P, dtype;
     int32_t _pad[2];
@@ -154,6 +160,7 @@ typedef struct {
     /* optional [3C + 4P] floats written by fpd_bottleneck_fold(): the three BNs folded to scale/shift with the conv1/conv2
      * biases folded into the following shift, + b3.  A frozen model folds once; NULL = every block folds for itself. */
     const float* folded;
+    const void* x2;        /* [N,H/2,W/2,C] low branch added to x on load, or NULL */
 } fpd_bneck_t;
 
 /* The inter-stack head of a FROZEN hourglass stack in one launch (hourglass.py:134-137,184-190 with eval-mode BN):
@@ -412,6 +419,9 @@ int fpd_bottleneck_forward(const fpd_bneck_t* a, fpd_stream_t stream);
 /* writes a->folded (must be non-NULL) from a's BN / bias pointers; rerun whenever those parameters change */
 int fpd_bottleneck_fold(const fpd_bneck_t* a, fpd_stream_t stream);
 int fpd_bottleneck_forward_pair(const fpd_bneck_pair_t* p, fpd_stream_t stream);
+/* 1 if fpd_bottleneck_forward() serves a launch of these dimensions with a low-branch source (fpd_bneck_t.x2), else 0.  Pure host
+ * code; reads N, H, W, C, P, dtype and the option "bneck_upadd" only, so it can be asked before the tensors have addresses. */
+int fpd_bneck_upadd_supported(const fpd_bneck_t* a);
 /* slabs the fused weight gradient of data-gradient launch `a` writes (see fpd_conv_t.wg_partial); 0 = not available.  For the
  * two convolutions of a pair launch: fpd_conv_pair_fused_wgrad_partials (counts for p->a and p->b; returns 0 / error code). */
 int fpd_conv_fused_wgrad_partials(const fpd_conv_t* a);
@@ -793,7 +803,8 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * "conv_pp_blocks" = its persistent blocks per occupancy slot (default 256); "bneck_blocks" / "head_blocks" = grid caps of the
  * persistent fpd_bottleneck_forward / fpd_head_forward kernels (defaults 128 / 160, any n >= 1); "wgrad_tile_only" = 1: fpd_conv_wgrad() fails
  * instead of falling through to the generic kernels when the halo-tile kernel declines a shape (tests); "conv_skip" / "stem_act" =
- * 0: fpd_conv_skip_supported() / fpd_stem_act_supported() answer 0 and such launches are refused (default 1); "ew_merge" = 0:
+ * 0: fpd_conv_skip_supported() / fpd_stem_act_supported() answer 0 and such launches are refused (default 1); "bneck_upadd" = 0: fpd_bneck_upadd_supported() answers 0 and a Bottleneck
+ * launch with x2 is refused (default 1, or what FPD_BNECK_UPADD says); "ew_merge" = 0:
  * the same for fpd_ew_merge_supported() / fpd_ew_merge() (default 1, or what FPD_EW_MERGE says); "ew_merge_blocks" = grid cap of those launches (default 2048, any
  * n >= 1).  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */

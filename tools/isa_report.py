@@ -9,6 +9,9 @@ the compiler's assembly on the build machine.  Two views:
     tools/isa_report.py branchy <unit> [<unit> ...]          kernels ranked by branch density (per-element control flow the compiler
                                                              made out of selects: how `bnrelu_bwd_r`'s 56-block loop body was found)
 
+    tools/isa_report.py regs <unit> [kernel-substring]      per kernel, from the code object's metadata: VGPRs, AGPRs, SGPRs, static LDS,
+                                                             scratch bytes per lane and the register spill counts
+
 <unit> = a translation unit of csrc/ without the extension (conv_pp, wgrad3, elementwise, ...) or a path to an existing .s file.
 """
 import os
@@ -104,6 +107,34 @@ def cmd_blocks(unit, pattern=''):
                                                          ' '.join('%s:%d' % kv for kv in c.most_common(6))))
 
 
+_META = ('.vgpr_count', '.agpr_count', '.sgpr_count', '.group_segment_fixed_size', '.private_segment_fixed_size', '.vgpr_spill_count',
+         '.sgpr_spill_count')
+
+
+def cmd_regs(unit, pattern=''):
+    """The amdhsa.kernels metadata at the end of the listing: one record per kernel ("  - .key: value" opens it, keys are sorted)."""
+    recs, cur, on = [], None, False
+    for line in open(assembly(unit)).read().split('\n'):
+        if line.startswith('amdhsa.kernels:'):
+            on = True
+        elif on and line.startswith('amdhsa.'):
+            on = False
+        elif on:
+            m = re.match(r'^  (- | {2})(\.\w+):\s*(.*)$', line)
+            if m:
+                if m.group(1) == '- ':
+                    cur = {}
+                    recs.append(cur)
+                cur[m.group(2)] = m.group(3).strip()
+    names = demangle([r.get('.name', '?') for r in recs])
+    print('%-72s %5s %5s %5s %7s %8s %12s' % ('kernel', 'VGPR', 'AGPR', 'SGPR', 'LDS', 'scratch', 'spills v/s'))
+    for r, name in zip(recs, names):
+        if pattern and pattern not in name:
+            continue
+        v = [r.get(k, '0') for k in _META]
+        print('%-72s %5s %5s %5s %7s %8s %12s' % (name[:72], v[0], v[1], v[2], v[3], v[4], v[5] + '/' + v[6]))
+
+
 def cmd_branchy(units):
     rows = []
     for u in units:
@@ -120,9 +151,11 @@ def cmd_branchy(units):
 
 
 if __name__ == '__main__':
-    if len(sys.argv) < 3 or sys.argv[1] not in ('blocks', 'branchy'):
+    if len(sys.argv) < 3 or sys.argv[1] not in ('blocks', 'branchy', 'regs'):
         raise SystemExit(__doc__)
-    if sys.argv[1] == 'blocks':
+    if sys.argv[1] == 'regs':
+        cmd_regs(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else '')
+    elif sys.argv[1] == 'blocks':
         cmd_blocks(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else '')
     else:
         cmd_branchy(sys.argv[2:])
