@@ -97,7 +97,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
-    SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t);
+    SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t);
 #undef SZ
     return -1;
 }
@@ -476,6 +476,20 @@ int fpd_final_preds(const fpd_finalpreds_t* a, fpd_stream_t stream) {
     FPD_REQUIRE((a->trans == nullptr) == (a->preds == nullptr), "final_preds: trans and preds go together");
     FPD_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->J > 0, "final_preds: bad dims");
     int rc = fpd_final_preds_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_val_post(const fpd_val_post_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->a && a->center && a->scale && a->score && a->merged && a->all_preds && a->all_boxes, "val_post: null pointer");
+    FPD_REQUIRE((const void*)a->merged != a->a && (const void*)a->merged != a->b, "val_post: merged aliases an input map");
+    FPD_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->J > 0 && a->J <= FPD_MAX_JOINTS, "val_post: bad dims (J <= %d)", FPD_MAX_JOINTS);
+    FPD_REQUIRE((int64_t)a->N * a->H * a->W * a->J < ((int64_t)1 << 31), "val_post: map too large");
+    FPD_REQUIRE(a->row0 >= 0, "val_post: row0 = %lld is negative", (long long)a->row0);
+    FPD_REQUIRE(a->row0 + a->N <= a->rows, "val_post: rows %lld..%lld outside the %lld result rows", (long long)a->row0,
+                (long long)(a->row0 + a->N - 1), (long long)a->rows);
+    FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "val_post: bad dtype %d", a->dtype);
+    if (a->b != nullptr)
+        for (int j = 0; j < a->J; ++j) FPD_REQUIRE(a->src[j] >= 0 && a->src[j] < a->J, "val_post: src[%d] = %d out of range", j, a->src[j]);
+    int rc = fpd_val_post_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 int fpd_render_targets(const fpd_targets_t* a, fpd_stream_t stream) {

@@ -109,6 +109,7 @@ int fpd_pck_launch(const fpd_pck_t& a, hipStream_t st);
 int fpd_flip_w_launch(const float* x, float* y, int64_t rows, int W, hipStream_t st);
 int fpd_flip_merge_launch(const fpd_flipmerge_t& p, hipStream_t st);
 int fpd_final_preds_launch(const fpd_finalpreds_t& p, hipStream_t st);
+int fpd_val_post_launch(const fpd_val_post_t& p, hipStream_t st);
 int fpd_render_targets_launch(const fpd_targets_t& a, hipStream_t st);
 int fpd_warp_affine_launch(const fpd_warp_t& a, hipStream_t st);
 int fpd_render_targets_w_launch(const fpd_targets_w_t& a, hipStream_t st);

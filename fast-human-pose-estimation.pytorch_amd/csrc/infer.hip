@@ -8,12 +8,44 @@
 //                       zeroed where the maximum is not positive), the quarter-pixel shift towards the higher neighbour
 //                       (TEST.POST_PROCESS) and the affine map back to image coordinates (transform_preds,
 //                       utils/transforms.py:50-55: float64 [x, y, 1] . trans^T, result stored as float32)
-// All three are index / byte work or exact fp32 arithmetic in the reference's own operation order: results are
+//   val_post_kernel    one validation batch in one launch (fpd_val_post_t): the NHWC maps of the arena in, the merged NHWC
+//                       fp32 map, the batch's rows of all_preds and all_boxes out; the per-sample inverse affine map is
+//                       computed on the device (val_post_math.h, the text a host build checks against numpy)
+// All of them are index / byte work or exact fp32 arithmetic in the reference's own operation order: results are
 // bit-identical to the reference functions (tests/golden/infer_ref.npz).
 #include "argmax.h"
 #include "common.h"
+#include "val_post_math.h"
 
 namespace {
+
+// get_max_preds' zeroing + get_final_preds' quarter-pixel shift (inference.py:18-46,57-70) for the arg-max m of one map;
+// at(y, x) reads the map
+template <typename At>
+__device__ __forceinline__ void peak_coords(ArgMax m, int H, int W, int post_process, At at, float& cx, float& cy) {
+    cx = m.v > 0.f ? (float)(m.i % W) : 0.f;
+    cy = m.v > 0.f ? (float)(m.i / W) : 0.f;
+    if (post_process) {
+        const int px = (int)floorf(cx + 0.5f), py = (int)floorf(cy + 0.5f);
+        if (1 < px && px < W - 1 && 1 < py && py < H - 1) {
+            const float dx = at(py, px + 1) - at(py, px - 1);
+            const float dy = at(py + 1, px) - at(py - 1, px);
+            cx += (dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f));
+            cy += (dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f));
+        }
+    }
+}
+
+// transform_preds (transforms.py:50-55,99-102) in float64, stored as float32: trans[n] . [x, y, 1].  The two rows are written
+// out with the fused multiply-adds final_preds_kernel has always been compiled to (x: t0*X first, y: t4*Y first), with
+// contraction off, so that every kernel that maps coordinates rounds alike whatever the compiler would choose per call site:
+// for float32 boxes the float64 sums sit on float32 rounding ties often enough for the order to show.
+__device__ __forceinline__ void map_coords(const double* t, float cx, float cy, float& ox, float& oy) {
+#pragma clang fp contract(off)
+    const double X = (double)cx, Y = (double)cy;
+    ox = (float)(t[2] + fma(t[1], Y, t[0] * X));
+    oy = (float)(t[5] + fma(t[3], X, t[4] * Y));
+}
 
 __global__ __launch_bounds__(256) void flip_w_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int W) {
     const int64_t total = rows * W;
@@ -54,25 +86,59 @@ __global__ __launch_bounds__(256) void final_preds_kernel(const fpd_finalpreds_t
     }
     m = block_argmax(m, s);
     if (threadIdx.x != 0) return;
-    float cx = m.v > 0.f ? (float)(m.i % p.W) : 0.f, cy = m.v > 0.f ? (float)(m.i / p.W) : 0.f;
-    if (p.post_process) {                                   // inference.py:57-70
-        const int px = (int)floorf(cx + 0.5f), py = (int)floorf(cy + 0.5f);
-        if (1 < px && px < p.W - 1 && 1 < py && py < p.H - 1) {
-            const float dx = hm[py * p.W + px + 1] - hm[py * p.W + px - 1];
-            const float dy = hm[(py + 1) * p.W + px] - hm[(py - 1) * p.W + px];
-            cx += (dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f));
-            cy += (dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f));
-        }
-    }
+    float cx, cy;
+    peak_coords(m, p.H, p.W, p.post_process, [&](int y, int x) { return hm[y * p.W + x]; }, cx, cy);
     p.coords[2 * blockIdx.x] = cx;
     p.coords[2 * blockIdx.x + 1] = cy;
     p.maxvals[blockIdx.x] = m.v;
-    if (p.trans != nullptr && p.preds != nullptr) {         // transforms.py:50-55,99-102 in float64
-        const double* t = p.trans + 6 * n;
-        // numpy.dot of a [2,3] matrix with a 3-vector: row . vector accumulated left to right
-        const double X = (double)cx, Y = (double)cy;
-        p.preds[2 * blockIdx.x] = (float)(t[0] * X + t[1] * Y + t[2] * 1.0);
-        p.preds[2 * blockIdx.x + 1] = (float)(t[3] * X + t[4] * Y + t[5] * 1.0);
+    if (p.trans != nullptr && p.preds != nullptr)
+        map_coords(p.trans + 6 * n, cx, cy, p.preds[2 * blockIdx.x], p.preds[2 * blockIdx.x + 1]);
+}
+
+// merged[n,y,x,j] of fpd_val_post_t from the NHWC maps: a widened, or (a + f') * 0.5f with flip_merge_kernel's f'
+template <typename T>
+__device__ __forceinline__ float val_merged_at(const fpd_val_post_t& p, int64_t n, int y, int x, int j, int sj) {
+    const int64_t row = (n * p.H + y) * p.W;
+    const float va = DT<T>::ld((const T*)p.a + (row + x) * p.J + j);
+    if (p.b == nullptr) return va;
+    const int xs = (p.shift && x >= 1) ? x - 1 : x;
+    const float f = DT<T>::ld((const T*)p.b + (row + (p.W - 1 - xs)) * p.J + sj);
+    return (va + f) * 0.5f;
+}
+
+// One block per (sample, joint), like final_preds_kernel.  A block's loads and stores are J elements apart; the J blocks of
+// a sample run side by side and share every line, and the two maps of a batch (N*H*W*J elements, 8 MiB in fp32 at
+// 32x64x64x16) stay in L2.  Thread 0 re-forms the four neighbours of the peak from a and b instead of reading `merged`
+// back: the same fp32 expression, no ordering between the block's own stores and loads needed.
+template <typename T>
+__global__ __launch_bounds__(256) void val_post_kernel(const fpd_val_post_t p) {
+    __shared__ ArgMax s[4];
+    const int64_t n = blockIdx.x / p.J;
+    const int j = blockIdx.x % p.J;
+    const int sj = p.b != nullptr ? p.src[j] : j;
+    const int HW = p.H * p.W;
+    ArgMax m = {-3.4e38f, 0x7fffffff};
+    for (int q = threadIdx.x; q < HW; q += blockDim.x) {
+        const int y = q / p.W;
+        ArgMax t = {val_merged_at<T>(p, n, y, q - y * p.W, j, sj), q};
+        p.merged[(n * HW + q) * p.J + j] = t.v;
+        m = better(m, t);
+    }
+    m = block_argmax(m, s);
+    if (threadIdx.x != 0) return;
+    float cx, cy;
+    peak_coords(m, p.H, p.W, p.post_process, [&](int y, int x) { return val_merged_at<T>(p, n, y, x, j, sj); }, cx, cy);
+    const double c0 = p.center[2 * n], c1 = p.center[2 * n + 1], s0 = p.scale[2 * n], s1 = p.scale[2 * n + 1];
+    double t[6];
+    fpd_val_inverse_affine(c0, c1, s0, p.box_f32, p.W, p.H, t);
+    float* o = p.all_preds + ((p.row0 + n) * p.J + j) * 3;
+    map_coords(t, cx, cy, o[0], o[1]);
+    o[2] = m.v;
+    if (j == 0) {
+        double* bx = p.all_boxes + (p.row0 + n) * 6;
+        bx[0] = c0; bx[1] = c1; bx[2] = s0; bx[3] = s1;
+        bx[4] = fpd_val_box_area(s0, s1, p.box_f32);
+        bx[5] = p.score[n];
     }
 }
 
@@ -94,5 +160,11 @@ int fpd_flip_merge_launch(const fpd_flipmerge_t& p, hipStream_t st) {
 
 int fpd_final_preds_launch(const fpd_finalpreds_t& p, hipStream_t st) {
     FPD_LAUNCH(final_preds_kernel, dim3(p.N * p.J), dim3(256), 0, st, p);
+    return 0;
+}
+
+int fpd_val_post_launch(const fpd_val_post_t& p, hipStream_t st) {
+    if (p.dtype == FPD_BF16) FPD_LAUNCH(val_post_kernel<bf16_t>, dim3(p.N * p.J), dim3(256), 0, st, p);
+    else FPD_LAUNCH(val_post_kernel<float>, dim3(p.N * p.J), dim3(256), 0, st, p);
     return 0;
 }

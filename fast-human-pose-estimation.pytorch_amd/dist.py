@@ -106,3 +106,50 @@ class DataParallelReplica(torch.nn.Module):
 
     def forward(self, *a, **kw):
         return self.module(*a, **kw)
+
+
+def make_gather(dist, group=None):
+    """Returns gather(all_preds [n,J,3] float32, all_boxes [n,6] float64, rows [n] int, sums [4] float64) for
+    core.function.validate(gather=...): every rank's four, each concatenated in rank order, on rank 0; None elsewhere.
+
+    The ranks hold different numbers of rows (block_range), so each packs its rows into one float64 matrix (float32
+    predictions and row numbers are exact in float64), pads it to the largest count and all_gather delivers them; the
+    counts travel first.  The buffers are device tensors with the RCCL backend ('nccl') and host tensors with gloo.
+    gather.broadcast(value) hands rank 0's performance indicator to every rank."""
+    import numpy as np
+
+    def device():
+        return torch.device('cuda', torch.cuda.current_device()) if dist.get_backend(group) == 'nccl' else torch.device('cpu')
+
+    def gather(all_preds, all_boxes, rows, sums):
+        world, rank, dev = dist.get_world_size(group), dist.get_rank(group), device()
+        n = len(rows)
+        k = int(np.prod(all_preds.shape[1:])) + all_boxes.shape[1] + 1
+        count = torch.tensor([n], dtype=torch.int64, device=dev)
+        counts = [torch.zeros_like(count) for _ in range(world)]
+        dist.all_gather(counts, count, group=group)
+        counts = [int(c.item()) for c in counts]
+        m = max(counts)
+        host = np.zeros(m * k + 4, np.float64)
+        block = host[:m * k].reshape(m, k)
+        block[:n, :k - 7] = np.asarray(all_preds, np.float32).reshape(n, -1)
+        block[:n, k - 7:k - 1] = all_boxes
+        block[:n, k - 1] = rows
+        host[m * k:] = sums
+        mine = torch.from_numpy(host).to(dev)
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine, group=group)
+        if rank != 0:
+            return None
+        parts = [p.cpu().numpy() for p in parts]
+        blocks = [p[:m * k].reshape(m, k)[:c] for p, c in zip(parts, counts)]
+        cat = np.concatenate(blocks) if blocks else np.zeros((0, k))
+        return (cat[:, :k - 7].astype(np.float32).reshape((-1,) + tuple(all_preds.shape[1:])), np.ascontiguousarray(cat[:, k - 7:k - 1]),
+                cat[:, k - 1].astype(np.int64), np.stack([p[m * k:] for p in parts]))
+
+    def broadcast(value):
+        t = torch.tensor([0.0 if value is None else float(value)], dtype=torch.float64, device=device())
+        dist.broadcast(t, src=0, group=group)
+        return value if dist.get_rank(group) == 0 else float(t.item())
+    gather.broadcast = broadcast
+    return gather

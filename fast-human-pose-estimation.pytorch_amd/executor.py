@@ -1188,3 +1188,123 @@ class FusedFPDStep:
 
     def set_lr(self, lr):
         self.lr_dev.fill_(lr)
+
+
+class ValidateStep:
+    """One validation batch of core.function.validate as enqueued work only: copy the batch in, the eval-mode forward, the
+    forward of the width-flipped batch (TEST.FLIP_TEST), one fpd_val_post launch (flip_back + shift + average, arg-max,
+    quarter-pixel shift, the inverse affine map of every sample, the batch's rows of the device-resident all_preds /
+    all_boxes), fpd_loss on the merged map and fpd_pck, which appends {avg_acc, cnt, loss, -} to the device log ring.
+    Nothing waits for the device; the caller drains `metric` when it prints a line and downloads the results once.
+
+    The step runs the module's own eval-mode GraphInstance (the one `model(x)` runs), so its maps hold the bits `model(x)`
+    returns.  'prep' (working weight copies, folded BN tables) runs once per validation in begin(): the weights do not
+    change while it lasts.  For the flip test the last map of the first forward is kept as a copy of that one map
+    (N*h*w*J elements) rather than in a second instance, which would hold a second activation arena to save one small
+    device-to-device copy."""
+
+    def __init__(self, inst):
+        from .lib.core.evaluate import DeviceAccuracy
+        assert not inst.train
+        self.inst = inst
+        o = inst.g.outputs[-1]
+        self.N, self.H, self.W, self.J = n, h, w, j = o.shape
+        if j > R.MAX_JOINTS:
+            raise R.FpdError('ValidateStep: at most %d joints, got %d' % (R.MAX_JOINTS, j))
+        self.dtype, dev = inst.dtype, inst.A.device
+        self.device = dev
+        self.out_ptr = inst.A.ptr(o.buf)
+        self.map_a = torch.empty((n, h, w, j), dtype=act_torch_dtype(self.dtype), device=dev)
+        self.merged = torch.empty((n, h, w, j), dtype=torch.float32, device=dev)
+        self.meta = torch.empty(5 * n, dtype=torch.float64, device=dev)        # center [n,2] | scale [n,2] | score [n]
+        self.ones = torch.ones((n, j), dtype=torch.float32, device=dev)
+        self.losses = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.metric = DeviceAccuracy(n, j, h, w, R.F32, dev, slots=64)
+        self._image_copy = None
+        self._keep = None
+        a = self.args = R.ValPostT()
+        a.N, a.J, a.H, a.W, a.dtype = n, j, h, w, self.dtype
+        a.center, a.scale, a.score = self.meta.data_ptr(), self.meta.data_ptr() + 16 * n, self.meta.data_ptr() + 32 * n
+        a.merged = self.merged.data_ptr()
+        s = self.loss = R.LossT()
+        s.B, s.J, s.H, s.W, s.S, s.dtype, s.target_nchw, s.alpha = n, j, h, w, 1, R.F32, 1, 0.0
+        s.out[0] = s.teacher = self.merged.data_ptr()
+        s.losses, s.grad_scale = self.losses.data_ptr(), 1.0
+
+    def begin(self, all_preds, all_boxes, flip_pairs=None, shift=False, post_process=False, use_target_weight=True,
+              min_slots=1):
+        """Start a validation: all_preds [rows,J,3] float32 and all_boxes [rows,6] float64 device tensors the batches write
+        into; flip_pairs None = no flip test.  Refreshes the working weights (the model may have trained since).  The ring
+        holds at least `min_slots` batches between two drains."""
+        from .lib.utils.transforms import channel_sources
+        assert all_preds.dtype == torch.float32 and all_preds.is_contiguous() and tuple(all_preds.shape[1:]) == (self.J, 3)
+        assert all_boxes.dtype == torch.float64 and all_boxes.is_contiguous() and tuple(all_boxes.shape[1:]) == (6,)
+        assert all_preds.shape[0] == all_boxes.shape[0]
+        if self.metric.slots < min_slots:
+            from .lib.core.evaluate import DeviceAccuracy
+            self.metric = DeviceAccuracy(self.N, self.J, self.H, self.W, R.F32, self.device, slots=int(min_slots))
+        self.metric.cursor.zero_()                 # an empty ring without asking the device what an earlier run left in it
+        self.metric.read = 0
+        self.all_preds, self.all_boxes = all_preds, all_boxes
+        a = self.args
+        a.rows, a.all_preds, a.all_boxes = all_preds.shape[0], all_preds.data_ptr(), all_boxes.data_ptr()
+        self.flip = flip_pairs is not None
+        a.shift, a.post_process = int(bool(shift) and self.flip), int(bool(post_process))
+        for k, s in enumerate(channel_sources(self.J, flip_pairs or [])):
+            a.src[k] = s
+        self.use_w = bool(use_target_weight)
+        self.inst.run('prep')
+
+    @staticmethod
+    def _host(v):
+        import numpy as np
+        return v.numpy() if torch.is_tensor(v) else np.asarray(v)
+
+    def run(self, inp, target, target_weight, center, scale, score, row0):
+        """Enqueue one batch; its results land in rows row0 .. row0+N-1.  center / scale [N,2] and score [N] are host arrays
+        or tensors in the dtype the dataset delivers (a float32 scale keeps numpy's float32 scale * 200)."""
+        import numpy as np
+        inst, l, st, n = self.inst, R.lib(), R.current_stream(), self.N
+        c, s, sc = self._host(center), self._host(scale), self._host(score)
+        host = torch.empty(5 * n, dtype=torch.float64, pin_memory=True)     # a fresh block per batch, as the loader stages
+        rows = host.numpy()
+        rows[0:2 * n] = np.asarray(c).reshape(-1)
+        rows[2 * n:4 * n] = np.asarray(s).reshape(-1)
+        rows[4 * n:5 * n] = np.asarray(sc).reshape(-1)
+        self.meta.copy_(host, non_blocking=True)
+        direct = inp.is_cuda and inp.dtype == torch.float32 and inp.is_contiguous()
+        inst.image().copy_(inp, non_blocking=True)
+        inst.run('fwd')
+        a = self.args
+        a.box_f32, a.row0 = int(s.dtype == np.float32), int(row0)
+        if self.flip:
+            self.map_a.copy_(inst.output_view(-1))
+            src = inp
+            if not direct:
+                if self._image_copy is None:
+                    self._image_copy = torch.empty_like(inst.image())
+                self._image_copy.copy_(inst.image())
+                src = self._image_copy
+            R.check(l.fpd_flip_w(src.data_ptr(), inst.image().data_ptr(), src.numel() // src.shape[-1], src.shape[-1], st), 'fpd_flip_w')
+            inst.run('fwd')
+            a.a, a.b = self.map_a.data_ptr(), self.out_ptr
+        else:
+            a.a, a.b = self.out_ptr, None
+        R.check(l.fpd_val_post(a, st), 'fpd_val_post')
+        tgt = target.to(self.device, non_blocking=True).float().contiguous()
+        wt = (target_weight.to(self.device, non_blocking=True).float().reshape(n, self.J).contiguous() if self.use_w else self.ones)
+        self._keep = (inp, tgt, wt)
+        self.losses.zero_()
+        self.loss.target, self.loss.weight = tgt.data_ptr(), wt.data_ptr()
+        R.check(l.fpd_loss(self.loss, st), 'fpd_loss')
+        self.metric.bind(self.merged.data_ptr(), tgt.data_ptr(), self.losses.data_ptr()).enqueue()
+
+
+def validate_step_for(model, batch_shape):
+    """One ValidateStep per (model, batch shape), cached on the module like core.function.fused_step_for caches train steps."""
+    inst = model.instance(tuple(batch_shape), False)
+    cache = model.__dict__.setdefault('_validate_steps', {})
+    hit = cache.get(tuple(batch_shape))
+    if hit is None or hit.inst is not inst:        # (.cuda() / .to() drop the module's instances: the step goes with them)
+        hit = cache[tuple(batch_shape)] = ValidateStep(inst)
+    return hit

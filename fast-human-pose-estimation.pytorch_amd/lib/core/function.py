@@ -190,16 +190,133 @@ def _to_numpy(v):
     return v.numpy() if torch.is_tensor(v) else np.asarray(v)
 
 
-def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None):
+def _image_of(val_dataset, row):
+    """Image path of dataset row `row` from the dataset's own records (host data every rank has)."""
+    recs = getattr(val_dataset, 'db', None)
+    if isinstance(recs, list):
+        return recs[row]['image']
+    names = getattr(val_dataset, 'all_names', None) or val_dataset.names
+    return names[row]
+
+
+def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None, gather=None):
     """function.py:189-332 with the reference's signature and return value (the dataset's perf indicator).
+
+    Every batch is enqueued work only (executor.ValidateStep): the eval-mode forward, TEST.FLIP_TEST's second forward on
+    the width-flipped batch, and one launch that merges the two maps, takes the arg-max with the TEST.POST_PROCESS
+    quarter-pixel shift, computes every sample's inverse affine map and writes the batch's rows of the device-resident
+    all_preds [num,J,3] / all_boxes [num,6]; JointsMSELoss and the PCK accuracy read the merged map and append to a device
+    ring.  The host waits for the device when a `Test:` line is due (PRINT_FREQ) and once after the last batch, when the
+    result arrays are downloaded.  A smaller last batch gets a step of its own shape.
+
+    gather (None: this process validates everything its loader yields): a callable taking this rank's
+    (all_preds, all_boxes, dataset rows, [sum loss*n, n, sum acc*cnt, cnt]) that returns every rank's four, each
+    concatenated in rank order, on rank 0 and None elsewhere (dist.make_gather).  Rank 0 then places the rows, takes the
+    image paths of the other ranks' rows from the dataset's own records and calls val_dataset.evaluate; the other ranks
+    return the indicator rank 0 broadcasts (gather.broadcast, where the callable has one)."""
+    import numpy as np
+    if type(criterion) is not JointsMSELoss:
+        raise R.FpdError('validate: the fused validation step evaluates core.loss.JointsMSELoss, got %s' % type(criterion).__name__)
+    net = _unwrap(model)
+    if not hasattr(net, 'instance') or not hasattr(net, '_flat'):
+        raise R.FpdError('validate: %s is not a HIP-backed model (lib.models)' % type(net).__name__)
+    batch_time, losses, acc = AverageMeter(), AverageMeter(), AverageMeter()
+    model.eval()
+    dev = net._flat['param'].device
+    num_samples, J = len(val_dataset), config.MODEL.NUM_JOINTS
+    all_preds = torch.zeros((num_samples, J, 3), dtype=torch.float32, device=dev)
+    all_boxes = torch.zeros((num_samples, 6), dtype=torch.float64, device=dev)
+    flip_pairs = val_dataset.flip_pairs if config.TEST.FLIP_TEST else None
+    image_path, filenames, imgnums, rows = [], [], [], []
+    idx = 0
+    step, n_img = None, {}
+    pending = []                    # steps whose ring holds undrained entries, in order of first use
+
+    def drain():
+        """Feed the meters with every batch since the last drain; synchronises."""
+        for s in pending:
+            for avg_acc, cnt, loss, _ in s.metric.drain(full=True):
+                losses.update(loss, n_img[id(s)])
+                acc.update(avg_acc, cnt)
+        del pending[:]
+
+    with torch.no_grad():
+        end = time.time()
+        for i, (inp, target, target_weight, meta) in enumerate(val_loader):
+            shape = tuple(inp.shape)
+            if step is None or shape != tuple(step.inst.image().shape):
+                step = E.validate_step_for(net, shape)
+                if step in pending:                          # a shape that comes back: keep the entries in batch order
+                    drain()
+                if id(step) not in n_img:
+                    step.begin(all_preds, all_boxes, flip_pairs, config.TEST.SHIFT_HEATMAP, config.TEST.POST_PROCESS,
+                               criterion.use_target_weight, min_slots=config.PRINT_FREQ + 1)
+                    n_img[id(step)] = shape[0]
+            if idx + shape[0] > num_samples:
+                raise R.FpdError('validate: the loader yields more than the %d samples of the dataset' % num_samples)
+            step.run(inp, target, target_weight, meta['center'], meta['scale'], meta['score'], idx)
+            if step not in pending:
+                pending.append(step)
+            image_path.extend(meta['image'])
+            if gather is not None:
+                rows.append(_to_numpy(meta['index']).astype(np.int64).reshape(-1))
+            idx += shape[0]
+            if i % config.PRINT_FREQ == 0:
+                drain()                                      # the only host sync of the loop
+                batch_time.update(time.time() - end)
+                logger.info('Test: [{0}/{1}]\t'
+                            'Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
+                            'Loss {loss.val:.4f} ({loss.avg:.4f})\t'
+                            'Accuracy {acc.val:.3f} ({acc.avg:.3f})'.format(i, len(val_loader), batch_time=batch_time,
+                                                                             loss=losses, acc=acc))
+            else:
+                batch_time.update(time.time() - end)
+            end = time.time()
+        drain()
+        all_preds, all_boxes = all_preds.cpu().numpy(), all_boxes.cpu().numpy()       # the one download
+        loss_avg, acc_avg = losses.avg, acc.avg
+        if gather is not None:
+            rows = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+            got = gather(all_preds[:idx], all_boxes[:idx], rows, np.array([losses.sum, losses.count, acc.sum, acc.count], np.float64))
+            if got is None:                                  # not rank 0: the indicator rank 0 broadcasts
+                bc = getattr(gather, 'broadcast', None)
+                return bc(None) if bc is not None else None
+            g_preds, g_boxes, g_rows, sums = got
+            g_rows = np.asarray(g_rows, np.int64)
+            all_preds = np.zeros((num_samples, J, 3), dtype=np.float32)
+            all_boxes = np.zeros((num_samples, 6))
+            all_preds[g_rows], all_boxes[g_rows] = g_preds, g_boxes
+            own = dict(zip(rows.tolist(), image_path))
+            image_path = [own[r] if r in own else _image_of(val_dataset, r) for r in range(num_samples)]
+            sums = np.asarray(sums, np.float64).reshape(-1, 4).sum(0)
+            loss_avg = sums[0] / sums[1] if sums[1] else 0
+            acc_avg = sums[2] / sums[3] if sums[3] else 0
+        name_values, perf_indicator = val_dataset.evaluate(config, all_preds, output_dir, all_boxes, image_path,
+                                                           filenames, imgnums)
+        for nv in (name_values if isinstance(name_values, list) else [name_values]):
+            _print_name_value(nv, config.MODEL.NAME)
+        if writer_dict and writer_dict.get('writer') is not None:
+            writer, gs = writer_dict['writer'], writer_dict['valid_global_steps']
+            writer.add_scalar('valid_loss', loss_avg, gs)
+            writer.add_scalar('valid_acc', acc_avg, gs)
+            for nv in (name_values if isinstance(name_values, list) else [name_values]):
+                writer.add_scalars('valid', dict(nv), gs)
+            writer_dict['valid_global_steps'] = gs + 1
+    validate.last = {'loss': loss_avg, 'acc': acc_avg, 'all_preds': all_preds, 'all_boxes': all_boxes, 'image_path': image_path}
+    if gather is not None and getattr(gather, 'broadcast', None) is not None:
+        return gather.broadcast(perf_indicator)
+    return perf_indicator
+
+
+def _validate_per_batch(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None):
+    """The per-batch body `validate` had before the fused step, kept as the yardstick of tests/test_val_post_gpu.py and
+    tools/validate_bench.py; nothing else calls it.
 
     Per batch: eval-mode forward (the folded-BN plan: fused frozen Bottlenecks / heads in bf16, the parity kernels in
     fp32), TEST.FLIP_TEST second forward on the width-flipped batch, flip_back + TEST.SHIFT_HEATMAP shift + average
     (one kernel), JointsMSELoss, PCK accuracy (csrc/pck.hip), and get_final_preds (arg-max, TEST.POST_PROCESS
-    quarter-pixel shift, affine map to image coordinates: one kernel).  The reference moves every one of these tensors
-    to the host and back (np.flip / flip_back / accuracy / get_final_preds are numpy); here only the final
-    [N,J,2]+[N,J,1] predictions and two scalars per batch cross PCIe.  The result arrays handed to
-    `val_dataset.evaluate(...)` have the reference's layout (all_preds [num,J,3], all_boxes [num,6])."""
+    quarter-pixel shift, affine map to image coordinates: one kernel), with the per-sample matrices from a host loop and
+    four host synchronisations: predictions, max values, loss and accuracy cross PCIe every batch."""
     import numpy as np
 
     from ..utils.transforms import flip_input, flip_merge, get_affine_transform
@@ -273,7 +390,8 @@ def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_l
             for nv in (name_values if isinstance(name_values, list) else [name_values]):
                 writer.add_scalars('valid', dict(nv), gs)
             writer_dict['valid_global_steps'] = gs + 1
-    validate.last = {'loss': losses.avg, 'acc': acc.avg, 'all_preds': all_preds, 'all_boxes': all_boxes}
+    _validate_per_batch.last = {'loss': losses.avg, 'acc': acc.avg, 'all_preds': all_preds, 'all_boxes': all_boxes,
+                                'image_path': image_path}
     return perf_indicator
 
 

@@ -192,20 +192,24 @@ class COCODataset:
         logger.info('=> Total boxes after fliter low score@{}: {}'.format(self.image_thre, len(db)))
         return db
 
-    def to_device(self, device='cuda', chunk_bytes=None):
+    def to_device(self, device='cuda', chunk_bytes=None, rows=None):
         """-> DeviceJointsDB as MPIIDataset.to_device builds it: every distinct picture decoded once and shared by its people,
         streamed into one device buffer; `names` are the picture paths (evaluate reads the picture id out of them); the box
         scores of a detection-box set travel as the database's `scores`."""
         from .device_dataset import DEFAULT_CHUNK_BYTES, DeviceJointsDB
+        lo, hi = (0, len(self.db)) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= lo <= hi <= len(self.db):
+            raise R.FpdError('COCODataset.to_device: rows (%d, %d) outside the %d records' % (lo, hi, len(self.db)))
+        recs = self.db[lo:hi]        # rows=(lo, hi): only the pictures these records refer to are decoded and uploaded
         paths, slot = [], {}
-        for rec in self.db:
+        for rec in recs:
             if rec['image'] not in slot:
                 slot[rec['image']] = len(paths)
                 paths.append(rec['image'])
-        index = np.array([slot[rec['image']] for rec in self.db], np.int64)
+        index = np.array([slot[rec['image']] for rec in recs], np.int64)
         j = self.num_joints
-        stack = lambda k, shape, dt: np.stack([rec[k] for rec in self.db]) if self.db else np.zeros(shape, dt)  # noqa: E731
-        scores = np.array([rec['score'] for rec in self.db], np.float64) if self.db and 'score' in self.db[0] else None
+        stack = lambda k, shape, dt: np.stack([rec[k] for rec in recs]) if recs else np.zeros(shape, dt)  # noqa: E731
+        scores = np.array([rec['score'] for rec in recs], np.float64) if recs and 'score' in recs[0] else None
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             shapes = list(pool.map(image_shape, paths))
             db = DeviceJointsDB(shapes, stack('joints_3d', (0, j, 3), np.float64), stack('joints_3d_vis', (0, j, 3), np.float64),
@@ -214,7 +218,8 @@ class COCODataset:
                                 pixel_std=self.pixel_std, image_index=index,
                                 load=_Prefetch(pool, paths, self.color_rgb, 2 * self.workers),
                                 chunk_bytes=DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes, scores=scores)
-        db.names = [rec['image'] for rec in self.db]
+        db.names = [rec['image'] for rec in recs]
+        db.row0, db.n_total = lo, len(self.db)
         logger.info('=> %s: %d samples over %d images, %.1f MB on %s', self.image_set, len(db), len(paths),
                     db.pixels.numel() / 1e6, db.device)
         return db
@@ -283,14 +288,16 @@ class COCODataset:
 def coco(cfg, device, rank=0, world_size=1, train=True):
     """DATASET.DATASET 'coco' of the tools, as `mpii`: DATASET.ROOT / TRAIN_SET behind an augmenting loader that takes this
     rank's share of every epoch, DATASET.ROOT / TEST_SET (ground-truth or detection boxes per TEST.USE_GT_BBOX) behind a
-    validation loader on rank 0.  -> (train_loader or None, valid_loader or None, valid_set or None)."""
-    from .device_dataset import DeviceAugmentLoader
-    loader = valid_loader = valid_set = None
+    validation loader over this rank's block of the set (every rank validates, rank 0 evaluates).
+    -> (train_loader or None, valid_loader, valid_set)."""
+    from .device_dataset import DeviceAugmentLoader, block_range
+    loader = None
     if train:
         train_set = COCODataset(cfg, cfg.DATASET.ROOT, cfg.DATASET.TRAIN_SET, True)
         loader = DeviceAugmentLoader(train_set.to_device(device), cfg, cfg.TRAIN.BATCH_SIZE_PER_GPU, True, shuffle=cfg.TRAIN.SHUFFLE,
                                      drop_last=True, seed=0, rank=rank, world_size=world_size)
-    if rank == 0:
-        valid_set = COCODataset(cfg, cfg.DATASET.ROOT, cfg.DATASET.TEST_SET, False)
-        valid_loader = DeviceAugmentLoader(valid_set.to_device(device), cfg, cfg.TEST.BATCH_SIZE_PER_GPU, False)
+    valid_set = COCODataset(cfg, cfg.DATASET.ROOT, cfg.DATASET.TEST_SET, False)
+    rows = block_range(len(valid_set), rank, world_size)
+    valid_loader = DeviceAugmentLoader(valid_set.to_device(device, rows=rows), cfg, cfg.TEST.BATCH_SIZE_PER_GPU, False,
+                                       rank=rank, world_size=world_size, partition='block')
     return loader, valid_loader, valid_set

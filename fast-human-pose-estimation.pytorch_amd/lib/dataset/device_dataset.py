@@ -9,7 +9,8 @@ get_affine_transform, the crop (cv2.warpAffine + ToTensor + Normalize), the join
                         vectorised call into a pinned staging buffer, copies it to the device and enqueues three kernels
                         (csrc/data.hip: augment_params, warp_affine_aug, render_targets_w).  There is no loop over samples
                         and nothing waits for the device.  With world_size > 1 it yields this rank's share of
-                        the epoch (epoch_order)
+                        the epoch: partition 'strided' (epoch_order, training and the default) or 'block' (block_range:
+                        validation, every row exactly once across the ranks)
 
 The draw table has one row per sample: the six numbers the reference pulls from np.random / random in its order of use
 (include/fpd_amd.h fpd_augment_t): u_half, n_half, n_scale, n_rot, u_rot, u_flip.  u_* are uniform [0,1), n_* standard
@@ -75,6 +76,8 @@ class DeviceJointsDB:
         self.h_joints, self.h_vis = joints, vis
         self.h_center, self.h_scale = np.ascontiguousarray(center, np.float64), np.ascontiguousarray(scale, np.float64)
         self.names = ['scene/%d' % i for i in range(n)]
+        # a database that holds rows [row0, row0 + n) of a dataset of n_total rows (the datasets' to_device(rows=...))
+        self.row0, self.n_total = 0, n
         self.h_scores = None if scores is None else np.ascontiguousarray(scores, np.float64).reshape(-1)
         if self.h_scores is not None and self.h_scores.size != n:
             raise R.FpdError('DeviceJointsDB: %d scores for %d samples' % (self.h_scores.size, n))
@@ -185,14 +188,40 @@ def epoch_order(n, seed, epoch, shuffle, rank=0, world_size=1):
     return np.ascontiguousarray(order[rank::world_size]), rng
 
 
+def block_range(n, rank, world_size):
+    """Rows [n*r//w, n*(r+1)//w) of n: contiguous blocks that tile [0, n) with no padding and no duplicate."""
+    rank, world_size = int(rank), int(world_size)
+    if not 0 <= rank < world_size:
+        raise R.FpdError('block_range: rank %d is not in [0, %d)' % (rank, world_size))
+    return n * rank // world_size, n * (rank + 1) // world_size
+
+
 class DeviceAugmentLoader:
     def __init__(self, db, cfg, batch_size, is_train, shuffle=None, drop_last=None, seed=0,
-                 mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), rank=0, world_size=1):
+                 mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), rank=0, world_size=1, partition='strided'):
+        """partition: how world_size > 1 ranks share the rows.  'strided' = epoch_order's rank::world_size of the padded
+        epoch permutation (training; every rank sees the same number of batches, rows may repeat).  'block' (validation
+        only) = block_range of the dataset in database order: no padding, no duplicate, so the ranks' results concatenate
+        to the whole set; the database may hold just that block (to_device(rows=...))."""
         self.db, self.batch_size, self.is_train = db, int(batch_size), bool(is_train)
         self.rank, self.world_size = int(rank), int(world_size)
         if not 0 <= self.rank < self.world_size:
             raise R.FpdError('DeviceAugmentLoader: rank %d is not in [0, %d)' % (self.rank, self.world_size))
+        if partition not in ('strided', 'block'):
+            raise R.FpdError("DeviceAugmentLoader: partition must be 'strided' or 'block', got %r" % (partition,))
+        self.partition = partition
         self.shuffle = self.is_train if shuffle is None else bool(shuffle)
+        if partition == 'block':
+            if self.is_train:
+                raise R.FpdError("DeviceAugmentLoader: partition='block' is for validation (is_train=False); training "
+                                 'ranks need equal batch counts, which the strided rule pads for')
+            if self.shuffle:
+                raise R.FpdError("DeviceAugmentLoader: partition='block' yields database order; shuffle must be off")
+            self.rows = block_range(getattr(db, 'n_total', len(db)), self.rank, self.world_size)
+            row0 = getattr(db, 'row0', 0)
+            if not (row0 <= self.rows[0] and self.rows[1] <= row0 + len(db)):
+                raise R.FpdError('DeviceAugmentLoader: rank %d validates rows [%d, %d) and the database holds [%d, %d)'
+                                 % (self.rank, self.rows[0], self.rows[1], row0, row0 + len(db)))
         self.drop_last = self.is_train if drop_last is None else bool(drop_last)
         self.seed, self.epoch = int(seed), 0
         self.image_size = tuple(int(v) for v in cfg.MODEL.IMAGE_SIZE)
@@ -210,10 +239,15 @@ class DeviceAugmentLoader:
 
     def __len__(self):
         n, b = (len(self.db) + self.world_size - 1) // self.world_size, self.batch_size      # samples of this rank
+        if self.partition == 'block':
+            n = self.rows[1] - self.rows[0]
         return n // b if self.drop_last else (n + b - 1) // b
 
     def __iter__(self):
-        order, rng = epoch_order(len(self.db), self.seed, self.epoch, self.shuffle, self.rank, self.world_size)
+        if self.partition == 'block':
+            order, rng = np.arange(self.rows[0], self.rows[1], dtype=np.int32) - np.int32(getattr(self.db, 'row0', 0)), None
+        else:
+            order, rng = epoch_order(len(self.db), self.seed, self.epoch, self.shuffle, self.rank, self.world_size)
         self.epoch += 1
         for k in range(len(self)):
             yield self.batch(order[k * self.batch_size:(k + 1) * self.batch_size], rng)
@@ -250,7 +284,7 @@ class DeviceAugmentLoader:
             contiguous = b > 0 and int(idx[-1]) - int(idx[0]) == b - 1
             meta = {'center': torch.from_numpy(db.h_center[idx]), 'scale': torch.from_numpy(db.h_scale[idx]),
                     'score': torch.ones(b, dtype=torch.float64) if db.h_scores is None else torch.from_numpy(db.h_scores[idx]),
-                    'index': torch.from_numpy(np.asarray(idx)),
+                    'index': torch.from_numpy(np.asarray(idx) + np.int32(getattr(db, 'row0', 0))),      # dataset rows
                     'image': db.names[int(idx[0]):int(idx[0]) + b] if contiguous else [db.names[i] for i in idx],
                     'joints': p['joints'], 'joints_vis': p['vis']}
         meta['trans'] = p['trans']
@@ -299,9 +333,10 @@ class DeviceAugmentLoader:
         return inp, target, weight, p
 
 
-def synthetic_aug(cfg, device, rank=0, train=True):
+def synthetic_aug(cfg, device, rank=0, train=True, world_size=1):
     """DATASET.DATASET 'synthetic_aug' of the tools: seeded scenes (synth.make_scenes) about 1.25x the network input in
-    size, resident on the device, behind augmenting loaders.  -> (train_loader or None, valid_loader, valid_db)."""
+    size, resident on the device, behind augmenting loaders; every rank validates its block of the validation scenes.
+    -> (train_loader or None, valid_loader, valid_db)."""
     w, h = (int(v) for v in cfg.MODEL.IMAGE_SIZE)
     side = max(w, h)
 
@@ -313,4 +348,5 @@ def synthetic_aug(cfg, device, rank=0, train=True):
         loader = DeviceAugmentLoader(db(rank * 1000003 + 17, cfg.DATASET.NUM_SCENES), cfg, cfg.TRAIN.BATCH_SIZE_PER_GPU, True,
                                      shuffle=cfg.TRAIN.SHUFFLE, drop_last=True, seed=rank)
     valid_db = db(1009, cfg.DATASET.NUM_VALID_SAMPLES)
-    return loader, DeviceAugmentLoader(valid_db, cfg, cfg.TEST.BATCH_SIZE_PER_GPU, False), valid_db
+    return loader, DeviceAugmentLoader(valid_db, cfg, cfg.TEST.BATCH_SIZE_PER_GPU, False, rank=rank, world_size=world_size,
+                                       partition='block'), valid_db

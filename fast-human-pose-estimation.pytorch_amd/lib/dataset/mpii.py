@@ -131,17 +131,21 @@ class MPIIDataset:
                        'joints_3d': joints_3d, 'joints_3d_vis': joints_3d_vis, 'filename': '', 'imgnum': 0})
         return db
 
-    def to_device(self, device='cuda', chunk_bytes=None):
+    def to_device(self, device='cuda', chunk_bytes=None, rows=None):
         """-> DeviceJointsDB: every distinct image decoded once by min(16, WORKERS) threads a few images ahead of the
         upload, streamed into one device buffer; `names` are the image paths (validate's image_path)."""
         from .device_dataset import DEFAULT_CHUNK_BYTES, DeviceJointsDB
+        lo, hi = (0, len(self.db)) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= lo <= hi <= len(self.db):
+            raise R.FpdError('MPIIDataset.to_device: rows (%d, %d) outside the %d records' % (lo, hi, len(self.db)))
+        recs = self.db[lo:hi]        # rows=(lo, hi): only the pictures these records refer to are decoded and uploaded
         paths, slot = [], {}
-        for rec in self.db:
+        for rec in recs:
             if rec['image'] not in slot:
                 slot[rec['image']] = len(paths)
                 paths.append(rec['image'])
-        index = np.array([slot[rec['image']] for rec in self.db], np.int64)
-        stack = lambda k, shape: np.stack([rec[k] for rec in self.db]) if self.db else np.zeros(shape)  # noqa: E731
+        index = np.array([slot[rec['image']] for rec in recs], np.int64)
+        stack = lambda k, shape: np.stack([rec[k] for rec in recs]) if recs else np.zeros(shape)  # noqa: E731
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             shapes = list(pool.map(image_shape, paths))
             db = DeviceJointsDB(shapes, stack('joints_3d', (0, self.num_joints, 3)), stack('joints_3d_vis', (0, self.num_joints, 3)),
@@ -149,7 +153,8 @@ class MPIIDataset:
                                 self.aspect_ratio, device=device, pixel_std=self.pixel_std, image_index=index,
                                 load=_Prefetch(pool, paths, self.color_rgb, 2 * self.workers),
                                 chunk_bytes=DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes)
-        db.names = [rec['image'] for rec in self.db]
+        db.names = [rec['image'] for rec in recs]
+        db.row0, db.n_total = lo, len(self.db)
         logger.info('=> %s: %d samples over %d images, %.1f MB on %s', self.image_set, len(db), len(paths),
                     db.pixels.numel() / 1e6, db.device)
         return db
@@ -194,15 +199,17 @@ class MPIIDataset:
 
 def mpii(cfg, device, rank=0, world_size=1, train=True):
     """DATASET.DATASET 'mpii' of the tools: DATASET.ROOT / TRAIN_SET behind an augmenting loader that takes this rank's share
-    of every epoch (every rank holds the whole training set), DATASET.ROOT / TEST_SET behind a validation loader over
-    the whole set on rank 0, the only rank that validates.  -> (train_loader or None, valid_loader or None, valid_set or None)."""
-    from .device_dataset import DeviceAugmentLoader
-    loader = valid_loader = valid_set = None
+    of every epoch (every rank holds the whole training set), DATASET.ROOT / TEST_SET behind a validation loader over this
+    rank's block of the set (block_range; only that block's pictures are decoded and uploaded; every rank validates, rank 0
+    evaluates: core.function.validate(gather=)).  -> (train_loader or None, valid_loader, valid_set)."""
+    from .device_dataset import DeviceAugmentLoader, block_range
+    loader = None
     if train:
         train_set = MPIIDataset(cfg, cfg.DATASET.ROOT, cfg.DATASET.TRAIN_SET, True)
         loader = DeviceAugmentLoader(train_set.to_device(device), cfg, cfg.TRAIN.BATCH_SIZE_PER_GPU, True, shuffle=cfg.TRAIN.SHUFFLE,
                                      drop_last=True, seed=0, rank=rank, world_size=world_size)
-    if rank == 0:
-        valid_set = MPIIDataset(cfg, cfg.DATASET.ROOT, cfg.DATASET.TEST_SET, False)
-        valid_loader = DeviceAugmentLoader(valid_set.to_device(device), cfg, cfg.TEST.BATCH_SIZE_PER_GPU, False)
+    valid_set = MPIIDataset(cfg, cfg.DATASET.ROOT, cfg.DATASET.TEST_SET, False)
+    rows = block_range(len(valid_set), rank, world_size)
+    valid_loader = DeviceAugmentLoader(valid_set.to_device(device, rows=rows), cfg, cfg.TEST.BATCH_SIZE_PER_GPU, False,
+                                       rank=rank, world_size=world_size, partition='block')
     return loader, valid_loader, valid_set

@@ -35,6 +35,11 @@ class SyntheticPose(torch.utils.data.Dataset):
     def __len__(self):
         return self.n
 
+    @property
+    def names(self):
+        """meta['image'] of every row (what validate needs for rows another rank processed)."""
+        return ['synthetic/%d' % i for i in range(self.n)]
+
     def __getitem__(self, i):
         return i
 

@@ -21,6 +21,7 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
 EWM_MAXPOOL_BWD, EWM_SUMPOOL = 0, 1
 AFFSUM_MAX = 4
 MAX_STACKS = 8
+MAX_JOINTS = 32     # include/fpd_amd.h FPD_MAX_JOINTS
 MAXC = 512
 
 _i32, _i64, _f32, _f64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -122,6 +123,12 @@ class FlipMergeT(C.Structure):
 class FinalPredsT(C.Structure):
     _fields_ = [('N', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('post_process', _i32), ('_pad', _i32), ('hm', _vp),
                 ('trans', _vp), ('coords', _vp), ('preds', _vp), ('maxvals', _vp)]
+
+
+class ValPostT(C.Structure):
+    _fields_ = [('N', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('dtype', _i32), ('shift', _i32), ('post_process', _i32),
+                ('box_f32', _i32), ('row0', _i64), ('rows', _i64), ('a', _vp), ('b', _vp), ('center', _vp), ('scale', _vp),
+                ('score', _vp), ('merged', _vp), ('all_preds', _vp), ('all_boxes', _vp), ('src', _i32 * MAX_JOINTS)]
 
 
 class TargetsT(C.Structure):
@@ -239,7 +246,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
             'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
-            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT}
+            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -275,6 +282,7 @@ SYMBOLS = {
     'fpd_flip_w': (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     'fpd_flip_merge': (C.c_int, [C.POINTER(FlipMergeT), _vp]),
     'fpd_final_preds': (C.c_int, [C.POINTER(FinalPredsT), _vp]),
+    'fpd_val_post': (C.c_int, [C.POINTER(ValPostT), _vp]),
     'fpd_render_targets': (C.c_int, [C.POINTER(TargetsT), _vp]),
     'fpd_warp_affine': (C.c_int, [C.POINTER(WarpT), _vp]),
     'fpd_augment_params': (C.c_int, [C.POINTER(AugmentT), _vp]),

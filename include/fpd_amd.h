@@ -546,6 +546,35 @@ typedef struct {
 } fpd_finalpreds_t;
 int fpd_final_preds(const fpd_finalpreds_t* a, fpd_stream_t stream);
 
+/* The post-processing of one validation batch in ONE launch, reading the network's last map where it lies in the arena
+ * (NHWC) and writing straight into the device-resident result arrays of the whole validation -- what
+ * fpd_nhwc_to_nchw x 2 + fpd_flip_merge + fpd_nchw_to_nhwc + a host loop of get_affine_transform + fpd_final_preds did:
+ *   merged[n,y,x,j] = b ? (a[n,y,x,j] + f'[n,y,x,j]) * 0.5f : (float)a[n,y,x,j]        (f' as in fpd_flipmerge_t, fp32)
+ *   all_preds[row0+n, j] = {x, y, maxval}: arg-max, zeroing and quarter-pixel shift of final_preds on `merged`, mapped by
+ *                          get_affine_transform(center[n], scale[n], 0, [W, H], inv=1) computed on the device in
+ *                          numpy's dtypes and operation order (csrc/val_post_math.h), float64 product stored as float32
+ *   all_boxes[row0+n]    = {center, scale, prod(scale * 200), score} in float64
+ * Bit-identical to that chain.  Rows outside [row0, row0+N) are not touched.  Refused before any launch: null pointers,
+ * J > FPD_MAX_JOINTS, merged aliasing a or b, row0 < 0, row0 + N > rows. */
+typedef struct {
+    int32_t N, J, H, W;
+    int32_t dtype;                 /* of a and b: FPD_F32 or FPD_BF16 */
+    int32_t shift, post_process;   /* TEST.SHIFT_HEATMAP (only with b), TEST.POST_PROCESS */
+    int32_t box_f32;               /* 1: center/scale hold float32 values (fpd_aug_db_t.box_f32): scale * 200 stays float32 */
+    int64_t row0;                  /* first result row of this batch */
+    int64_t rows;                  /* rows all_preds / all_boxes hold: row0 + N <= rows */
+    const void* a;                 /* [N,H,W,J] last map of the network for the batch */
+    const void* b;                 /* the same for the width-flipped batch, or NULL: no flip test */
+    const double* center;          /* [N,2] device */
+    const double* scale;           /* [N,2] device */
+    const double* score;           /* [N] device */
+    float* merged;                 /* [N,H,W,J] fp32 (what fpd_loss with S = 1 and fpd_pck read) */
+    float* all_preds;              /* [rows,J,3] float32 */
+    double* all_boxes;             /* [rows,6] float64 */
+    int32_t src[FPD_MAX_JOINTS];   /* as in fpd_flipmerge_t */
+} fpd_val_post_t;
+int fpd_val_post(const fpd_val_post_t* a, fpd_stream_t stream);
+
 /* ---- device data pipeline (lib/dataset/JointsDataset.py:113-198,233-289) ---- */
 /* generate_target (JointsDataset.py:233-289) for a batch: Gaussian heat-map targets + target weights from joint
  * positions in network-input pixels.  mu = int(joint / feat_stride + 0.5) in float64 (feat_stride = image/heat-map size),

@@ -35,6 +35,7 @@ from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import fpd_train, train, validate  # noqa: E402
 from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa: E402
+from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
 from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
                                      save_checkpoint)
@@ -127,20 +128,21 @@ def run(args, normal=False):
     bs = cfg.TRAIN.BATCH_SIZE_PER_GPU
     if cfg.DATASET.DATASET == 'mpii':
         # DATASET.ROOT decoded once and resident on every rank's device; each rank augments its rank::world share of the
-        # epoch's permutation (lib/dataset/mpii.py); the validation set lives on rank 0
+        # epoch's permutation (lib/dataset/mpii.py); every rank holds and validates its block of the validation set
         loader, valid_loader, valid_set = mpii(cfg, dev, rank, world)
     elif cfg.DATASET.DATASET == 'coco':                  # the same for a COCO directory (lib/dataset/coco.py)
         loader, valid_loader, valid_set = coco(cfg, dev, rank, world)
     elif cfg.DATASET.DATASET == 'synthetic_aug':
         # seeded scenes resident on the device; every batch is augmented there (half-body, scale / rotation jitter, flip),
         # cropped and given its targets by three kernels (lib/dataset/device_dataset.py)
-        loader, valid_loader, valid_set = synthetic_aug(cfg, dev, rank)
+        loader, valid_loader, valid_set = synthetic_aug(cfg, dev, rank, world_size=world)
     else:
         train_set = SyntheticPose(cfg, cfg.DATASET.NUM_SAMPLES, seed=rank)
         loader = torch.utils.data.DataLoader(train_set, batch_size=bs, shuffle=cfg.TRAIN.SHUFFLE, num_workers=0,
                                              pin_memory=cfg.PIN_MEMORY, drop_last=True, collate_fn=train_set.collate)
         valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
-        valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, shuffle=False, num_workers=0,
+        valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, num_workers=0,
+                                                   sampler=range(*block_range(len(valid_set), rank, world)),
                                                    pin_memory=cfg.PIN_MEMORY, collate_fn=valid_set.collate)
     if args.max_iters:
         import itertools
@@ -175,15 +177,13 @@ def run(args, normal=False):
     optimizer.param_groups[0]['initial_lr'] = base_lr
     allreduce = fdist.make_allreduce(dist) if world > 1 else None
     writer_dict = {'writer': None, 'train_global_steps': 0, 'valid_global_steps': 0}
-    if rank == 0:
-        # :243-250: before the first epoch the reference evaluates the teacher and then the student on the validation set
-        # (the two "Test:" blocks in front of epoch 0 in its logs).  Both go through core.function.validate; rank 0 only, like
-        # the per-epoch validation below.
-        if tmodel is not None:
-            validate(cfg, valid_loader, valid_set, tmodel, val_criterion, out_dir, cfg.LOG_DIR, writer_dict)
-        validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict)
-    if world > 1:
-        dist.barrier()
+    # :243-250: before the first epoch the reference evaluates the teacher and then the student on the validation set (the
+    # two "Test:" blocks in front of epoch 0 in its logs).  Both go through core.function.validate on EVERY rank, each over
+    # its block of the set (the reference validates on its DataParallel model, :143,244); rank 0 gathers and evaluates.
+    gather = fdist.make_gather(dist) if world > 1 else None
+    if tmodel is not None:
+        validate(cfg, valid_loader, valid_set, tmodel, val_criterion, out_dir, cfg.LOG_DIR, writer_dict, gather=gather)
+    validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict, gather=gather)
     for epoch in range(begin_epoch, cfg.TRAIN.END_EPOCH):                                     # :252-286
         t0 = time.time()
         optimizer.param_groups[0]['lr'] = multistep_lr(base_lr, cfg.TRAIN.LR_STEP, cfg.TRAIN.LR_FACTOR, epoch)   # :253
@@ -196,18 +196,19 @@ def run(args, normal=False):
         torch.cuda.synchronize()
         logger.info('=> epoch %d done in %.1fs, %.1f samples/s, last logged loss %.5f', epoch, time.time() - t0,
                     len(loader) * bs * world / max(time.time() - t0, 1e-9), loss)
+        # :266-285: evaluate on the validation set (flip test etc. per cfg.TEST) on every rank, keep the best model on rank 0
+        # float(): MPII's indicator is a numpy scalar, which a weights-only torch.load of the checkpoint refuses
+        perf_indicator = float(validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict,
+                                        gather=gather))
         if rank == 0:
-            # :266-285: evaluate on the validation set (flip test etc. per cfg.TEST), keep the best model
-            # float(): MPII's indicator is a numpy scalar, which a weights-only torch.load of the checkpoint refuses
-            perf_indicator = float(validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict))
             best_model = perf_indicator >= best_perf
             best_perf = max(best_perf, perf_indicator)
             save_checkpoint({'epoch': epoch + 1, 'model': cfg.MODEL.NAME, 'state_dict': model.state_dict(),
                              'best_state_dict': model.module.state_dict(), 'perf': perf_indicator,
                              'optimizer': optimizer.state_dict()}, best_model, out_dir)
         if world > 1:
-            dist.barrier()       # ranks != 0 wait for rank 0's validation + checkpoint HERE, explicitly, rather than inside
-                                 # the first gradient all-reduce of the next epoch
+            dist.barrier()       # ranks != 0 wait for rank 0's checkpoint HERE, explicitly, rather than inside the first
+                                 # gradient all-reduce of the next epoch
     if rank == 0:
         torch.save(model.module.state_dict(), os.path.join(out_dir, 'final_state.pth'))      # :288-294
     if world > 1:
