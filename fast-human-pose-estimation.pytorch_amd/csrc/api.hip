@@ -80,6 +80,7 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "stem_act")) return fpd_stem_s2d_option(0, value);             // eval-mode BN + ReLU in the stem's epilogue (fpd_stem_t.act)
     if (!strcmp(name, "ew_merge")) return fpd_ew_merge_option(value < 0 ? 0 : value);      // BN-backward applies inside the pool backward (fpd_ew_merge_t) offered at all
     if (!strcmp(name, "ew_merge_blocks")) return fpd_ew_merge_blocks_option(value);      // their grid cap (tests: several windows per thread on small tensors)
+    if (!strcmp(name, "ew_blocks")) return fpd_ew_blocks_option(value);      // grid cap of the plain elementwise, pair and affsum launches (tests: several trips per thread), 0 = none
     if (!strcmp(name, "conv_c3")) return fpd_conv_c3_option(0, value);
     if (!strcmp(name, "conv_c3_blocks")) return fpd_conv_c3_option(1, value);
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);

@@ -126,6 +126,7 @@ const char* fpd_ew_merge_why_not(const fpd_ew_merge_t& m);
 int fpd_ew_merge_launch(const fpd_ew_merge_t& m, hipStream_t st);
 int fpd_ew_merge_option(int value);      // >= 0: set; returns the previous value
 int fpd_ew_merge_blocks_option(int value);      // >= 1: set the grid cap of the merged launches; returns the previous value
+int fpd_ew_blocks_option(int value);      // >= 1: grid cap of fpd_elementwise_launch (each half of a pair launch) and fpd_affsum_launch, 0: none (default); returns the previous value
 int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
 int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& a, hipStream_t st);      // csrc/loss_ohkm.hip: two launches
 int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a);

@@ -24,7 +24,7 @@ __device__ __forceinline__ void stv(T* p, const float* f) {
 // (bx, gx): this block's index and the number of blocks working on `a` (grid-stride over pixels)
 // NA ("no alias"): no input tensor of the op is its output tensor (decided on the host by comparing the pointers): the
 // inputs and the output are then __restrict__, which is what lets the loads of the next pixel pass the stores of this one
-// (two pixels in flight per thread).  An op that works IN PLACE (`add` / `x` may be `y`: include/fpd_amd.h) takes the
+// (two pixels in flight per thread).  An op that works IN PLACE (`add`, and for the per-pixel ops `x`, may be `y`: include/fpd_amd.h) takes the
 // instantiation without the qualifiers -- reading an object through one restrict pointer and writing it through another is
 // undefined behaviour, however the code object of the day happens to schedule it.
 template <typename T, bool NA> struct EwPtr { typedef const T* in; typedef T* out; };
@@ -239,24 +239,15 @@ static int ew_stats_blocks() {
     return v;
 }
 
-template <typename T, int OP>
-int launch_ew(const fpd_ew_t& a, hipStream_t st) {
-    constexpr int VEC = DT<T>::VEC;
-    const int VP = a.C / VEC, PB = 256 / VP;
-    const bool half = (OP == FPD_EW_MAXPOOL_FWD || OP == FPD_EW_MAXPOOL_BWD || OP == FPD_EW_SUMPOOL);
-    const int npix = a.N * (half ? a.H / 2 : a.H) * (half ? a.W / 2 : a.W);
-    // grid-stride kernels: ops that end with per-channel statistics atomics get few, long-lived blocks -- every block
-    // adds into the SAME [2][C] buffer and same-address device atomics serialise (~12 ns each)
-    const bool stats = (OP == FPD_EW_BNRELU_FWD || OP == FPD_EW_MAXPOOL_FWD || OP == FPD_EW_UPADD_FWD) ? a.out_stats != nullptr
-                                                                                                   : OP == FPD_EW_BNRELU_BWD_R;
-    const int grid = std::max(1, std::min(cdiv(npix, PB), stats ? ew_stats_blocks() : 2048));
-    if (ew_no_alias(a)) FPD_LAUNCH((ew_kernel<T, OP, true>), dim3(grid), dim3(256), 0, st, a);
-    else FPD_LAUNCH((ew_kernel<T, OP, false>), dim3(grid), dim3(256), 0, st, a);
-    return 0;
-}
+// option "ew_blocks": 0 = the rule of ew_rule() alone (default); n >= 1: no launch of ew_kernel, neither half of ew_pair_kernel and no
+// affsum_kernel gets more than n blocks (tests: several trips of the pixel loop per thread on small tensors)
+int g_ew_blocks = 0;
+static int ew_cap(const int grid) { return g_ew_blocks >= 1 ? std::min(grid, g_ew_blocks) : grid; }
 
+// the grid rule of the grid-stride kernels: ops that end with per-channel statistics atomics get few, long-lived blocks -- every
+// block adds into the SAME [2][C] buffer and same-address device atomics serialise (~12 ns each)
 template <typename T, int OP>
-int ew_grid(const fpd_ew_t& a) {
+int ew_rule(const fpd_ew_t& a) {
     constexpr int VEC = DT<T>::VEC;
     const int VP = a.C / VEC, PB = 256 / VP;
     const bool half = (OP == FPD_EW_MAXPOOL_FWD || OP == FPD_EW_MAXPOOL_BWD || OP == FPD_EW_SUMPOOL);
@@ -264,6 +255,18 @@ int ew_grid(const fpd_ew_t& a) {
     const bool stats = (OP == FPD_EW_BNRELU_FWD || OP == FPD_EW_MAXPOOL_FWD || OP == FPD_EW_UPADD_FWD) ? a.out_stats != nullptr
                                                                                                    : OP == FPD_EW_BNRELU_BWD_R;
     return std::max(1, std::min(cdiv(npix, PB), stats ? ew_stats_blocks() : 2048));
+}
+
+// blocks of an ew_kernel launch / of one half of an ew_pair_kernel launch: the rule under the cap of option "ew_blocks"
+template <typename T, int OP>
+int ew_grid(const fpd_ew_t& a) { return ew_cap(ew_rule<T, OP>(a)); }
+
+template <typename T, int OP>
+int launch_ew(const fpd_ew_t& a, hipStream_t st) {
+    const int grid = ew_grid<T, OP>(a);
+    if (ew_no_alias(a)) FPD_LAUNCH((ew_kernel<T, OP, true>), dim3(grid), dim3(256), 0, st, a);
+    else FPD_LAUNCH((ew_kernel<T, OP, false>), dim3(grid), dim3(256), 0, st, a);
+    return 0;
 }
 
 template <typename T>
@@ -456,11 +459,11 @@ __global__ __launch_bounds__(256) void ew_merge_kernel(const fpd_ew_merge_t m) {
     }
 }
 
-int g_ew_merge_blocks = 2048;      // grid cap (option "ew_merge_blocks"; 2048 = the cap of ew_grid)
+int g_ew_merge_blocks = 2048;      // grid cap (option "ew_merge_blocks"; 2048 = the cap of ew_rule)
 
 template <typename T, int KIND, bool FULL, bool ADDF, bool ADDH>
 int launch_ew_merge(const fpd_ew_merge_t& m, hipStream_t st) {
-    const int grid = std::min(ew_grid<T, FPD_EW_SUMPOOL>(m.pool), g_ew_merge_blocks);      // the grid rule of the pooled ops: one window per thread and trip
+    const int grid = std::min(ew_rule<T, FPD_EW_SUMPOOL>(m.pool), g_ew_merge_blocks);      // the grid rule of the pooled ops: one window per thread and trip
     FPD_LAUNCH((ew_merge_kernel<T, KIND, FULL, ADDF, ADDH>), dim3(grid), dim3(256), 0, st, m);
     return 0;
 }
@@ -551,6 +554,12 @@ int fpd_ew_merge_blocks_option(int value) {
     return prev;
 }
 
+int fpd_ew_blocks_option(int value) {
+    const int prev = g_ew_blocks;
+    if (value >= 0) g_ew_blocks = value;
+    return prev;
+}
+
 static bool ew_apply_ok(const fpd_ew_t& a, const fpd_ew_t& pool, const int div) {
     return a.op == FPD_EW_BN_BWD_APPLY && a.dtype == pool.dtype && a.N == pool.N && a.H == pool.H / div && a.W == pool.W / div && a.C == pool.C &&
            a.x && a.dy && a.y && a.bstats && a.bn.gamma && a.bn.beta &&
@@ -609,7 +618,7 @@ int fpd_affsum_launch(const fpd_affsum_t& a, hipStream_t st) {
     if (a.C % vec != 0 || a.C > FPD_MAXC || a.C / vec > 128)
         return fpd_fail(-3, "affsum: C=%d must be a multiple of %d and <= %d", a.C, vec, FPD_MAXC);
     const int PB = 256 / (a.C / vec);
-    const int grid = std::max(1, std::min(cdiv(a.N * a.H * a.W, PB), 2048));
+    const int grid = ew_cap(std::max(1, std::min(cdiv(a.N * a.H * a.W, PB), 2048)));
     if (a.dtype == FPD_BF16) FPD_LAUNCH((affsum_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, a);
     else FPD_LAUNCH((affsum_kernel<float>), dim3(grid), dim3(256), 0, st, a);
     return 0;

@@ -259,7 +259,7 @@ enum {
 typedef struct {
     int32_t op, dtype;
     int32_t N, H, W, C;    /* shape of the LARGER spatial tensor involved (pool input / up output) */
-    const void* x;         /* see table */
+    const void* x;         /* see table (BNRELU_FWD, UPADD_FWD, ADD: may alias y -- a thread reads the element it then writes) */
     const void* x2;
     const void* dy;
     const void* add;       /* optional accumulate source (may alias y) */
@@ -835,7 +835,9 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * 0: fpd_conv_skip_supported() / fpd_stem_act_supported() answer 0 and such launches are refused (default 1); "bneck_upadd" = 0: fpd_bneck_upadd_supported() answers 0 and a Bottleneck
  * launch with x2 is refused (default 1, or what FPD_BNECK_UPADD says); "ew_merge" = 0:
  * the same for fpd_ew_merge_supported() / fpd_ew_merge() (default 1, or what FPD_EW_MERGE says); "ew_merge_blocks" = grid cap of those launches (default 2048, any
- * n >= 1).  Returns the
+ * n >= 1); "ew_blocks" = n >= 1: no fpd_elementwise() launch, neither half of an fpd_elementwise_pair() launch and no fpd_affsum() launch
+ * gets more than n blocks, so that a thread walks several pixels on a small tensor (tests); 0 = the library's own grid rule alone
+ * (default); a negative value changes nothing.  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */
 int fpd_set_option(const char* name, int32_t value);
 int fpd_abi_sizeof(const char* struct_name);  /* sizeof of a struct above, -1 if unknown */
