@@ -6,6 +6,7 @@ PyTorch is used here only as the HBM allocator, stream provider and RCCL front e
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import torch
 
@@ -82,6 +83,28 @@ def _abuf(a):
     return None if a is None else (a.buf if isinstance(a, G.Act) else a)
 
 
+def _nop():
+    """What an op lowers to when it launches nothing (graph.Op.absorbed(), a fused weight gradient, a marker)."""
+    return R.OP_NOP, R.MemsetT()
+
+
+def _readers_of(readers, t, exclude=(), by_buf=True):
+    """(position in `readers`, member op) of every launch member that lists tensor `t` among its acts_in(), the ops in
+    `exclude` left out.  by_buf=True compares the planned Buf, which also catches a tensor aliased into another Act;
+    by_buf=False compares the Act itself -- the only key there is before plan_memory, while every buf is still None."""
+    key = _abuf if by_buf else (lambda a: a)
+    y = key(t)
+    for j, top in enumerate(readers):
+        for o in (top.members() if top is not None else ()):
+            if not any(o is e for e in exclude) and any(key(a) is y for a in o.acts_in()):
+                yield j, o
+
+
+# One weight gradient's slabs: `s` is the struct finish_partials patches (the very object the plan copies, for a pair a
+# view INTO the pair struct), n slabs of `stride` floats from float `off` of the workspace, each dw (numel) + nbias bias sums.
+Slabs = namedtuple('Slabs', 's dw numel stride n off dbias nbias')
+
+
 # FPD_WHATIF=token[,token...]: TIMING-ONLY experiments (results are wrong when set): the named class of ops is lowered to
 # no-ops, which shows what that class costs inside the pipelined step (experiments/r03/whatif.sh).  Student graph:
 # nowgrad / nowgrad_small / nowgrad_big (weight gradients, by map height <= 16 / >= 64), noapply (BN-backward applies),
@@ -152,6 +175,9 @@ class Lowering:
         return s
 
     def conv(self, op, plain=False):
+        """plain=True: the convolution as the graph states it, every decision ignored (the planners and the pair launches start there)."""
+        if not plain and op.absorbed():        # formed inside the launch of the conv3 it is the residual of (plan_skips)
+            return _nop()
         s = R.ConvT()
         (s.N, s.H, s.W, s.C, s.K, s.R, s.S, s.stride, s.pad, s.P, s.Q) = op.dims
         s.dtype = self.dtype
@@ -161,18 +187,16 @@ class Lowering:
         s.out_stats = p(op.out_stats)
         s.bn = self.bn(op.bn)
         s.epi_x, s.epi_bn, s.epi_stats = p(_abuf(op.epi_x)), self.bn(op.epi_bn), p(op.epi_stats)
-        s.wg_partial, s.wg_stride, s.wg_bias, s.wg_count = None, 0, 0, 0
-        if not plain and getattr(op, 'skip_fused', False):  # formed inside the launch of the conv3 it is the residual of (plan_skips)
-            return R.OP_NOP, R.MemsetT()
-        if not plain and getattr(op, 'skip_active', False):
+        if plain:
+            return R.OP_CONV, s
+        if op.skip_active:
             self._fill_skip(op, s)
-        if not plain and getattr(op, 'fused_wgrad', None) is not None and self.use_partials:
+        if op.fused_wgrad is not None and self.use_partials:
             n = R.lib().fpd_conv_fused_wgrad_partials(C.byref(s))
             if n > 0:
                 self._fuse_wgrad(op, s, n)
-        if not plain:
-            self._fill_fold(op, s)
-        if getattr(op, 'w8', None) is not None and not plain:
+        self._fill_fold(op, s)
+        if op.w8 is not None:
             f = R.ConvF8T()
             f.c, f.w8, f.w8_scale = s, p(op.w8), p(op.w8s)
             return R.OP_CONV_F8, f
@@ -185,13 +209,11 @@ class Lowering:
         if os.environ.get('FPD_FOLD_APPLY', '1') == '0':
             return
         l = R.lib()
-        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
         for i, op in enumerate(ops):
             if op is None or op.kind not in ('conv', 'conv2'):
                 continue
-            members = members_of(op)
-            cands = [m for m in members if getattr(m, 'fold_apply', None) is not None and not getattr(m.fold_apply, 'folded', False)]
-            if not cands or any(getattr(m, 'w8', None) is not None for m in members):
+            cands = [m for m in op.members() if m.fold_apply is not None and not m.fold_apply.folded]
+            if not cands or any(m.w8 is not None for m in op.members()):
                 continue
             # Who else reads an apply's result?  Its own convolution's weight gradient is served from the launch's operand image
             # when that is fused too; ANY other reader (a tensor aliased into a residual-path gradient, an op on another lane)
@@ -199,18 +221,9 @@ class Lowering:
             # convolution in the list would read it before it exists: no fold.
             early = False
             for m in cands:
-                y = _abuf(m.fold_apply.y)
-                own = (id(m), id(m.fold_apply), id(getattr(m, 'fold_wgrad', None)))
-                m.fold_other_readers = False
-                for j, top in enumerate(ops):
-                    if top is None:
-                        continue
-                    for o in members_of(top):
-                        if id(o) in own or not any(_abuf(t) is y for t in o.acts_in()):
-                            continue
-                        if j < i:
-                            early = True
-                        m.fold_other_readers = True
+                at = [j for j, _ in _readers_of(ops, m.fold_apply.y, exclude=(m, m.fold_apply, m.fold_wgrad))]
+                m.fold_other_readers = bool(at)
+                early = early or any(j < i for j in at)
             if early:
                 continue
             if op.kind == 'conv2':
@@ -237,21 +250,19 @@ class Lowering:
         if os.environ.get('FPD_EW_MERGE', '1') == '0':
             return
         l = R.lib()
-        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
         iv = lambda b: (b.arena, b.off, b.off + b.numel)
         hit = lambda p, q: p[0] == q[0] and p[1] < q[2] and q[1] < p[2]
-        is_apply = lambda m: (m is not None and m.kind == 'ew' and m.op == 'bn_bwd_apply' and not getattr(m, 'folded', False)
-                              and not getattr(m, 'ewm_absorbed', False))
+        is_apply = lambda m: m.kind == 'ew' and m.op == 'bn_bwd_apply' and not m.folded and not m.ewm_absorbed
         lane0 = [i for i, op in enumerate(ops) if op is not None and (op.lane or 0) == 0]
         for k in range(1, len(lane0)):
             i, j = lane0[k - 1], lane0[k]
             prev, op = ops[i], ops[j]
-            if op.kind != 'ew' or op.op not in ('maxpool_bwd', 'sumpool') or getattr(op, 'ewm_kind', None) is not None:
+            if op.kind != 'ew' or op.op not in ('maxpool_bwd', 'sumpool') or op.ewm_kind is not None:
                 continue
             full = half = None
             if op.op == 'maxpool_bwd':
-                cands = [m for m in members_of(prev) if is_apply(m)] if prev.kind in ('ew', 'ew2') else []
-                if len(cands) != len(members_of(prev)):
+                cands = [m for m in prev.members() if is_apply(m)] if prev.kind in ('ew', 'ew2') else []
+                if len(cands) != len(prev.members()):
                     continue
                 half = next((m for m in cands if _abuf(m.y) is _abuf(op.dy)), None)
                 full = next((m for m in cands if m is not half), None)
@@ -260,16 +271,14 @@ class Lowering:
                     continue
                 if full is not None and not (_abuf(op.add) is _abuf(full.y) and _abuf(op.x) is _abuf(full.x) and tuple(full.dims) == tuple(op.dims)):
                     continue
-                hidden = [m.y for m in (full, half) if m is not None]      # never written: nobody else may read them
-                if any(o is not op and any(_abuf(t) is _abuf(y) for t in o.acts_in() for y in hidden)
-                       for top in ops if top is not None for o in members_of(top)):
+                if any(any(_readers_of(ops, m.y, exclude=(op,))) for m in cands):      # their results are never written: nobody else may read them
                     continue
             else:
                 if prev.kind != 'ew' or not is_apply(prev) or _abuf(prev.y) is not _abuf(op.x) or tuple(prev.dims) != tuple(op.dims):
                     continue
                 full = prev
                 # its result is written at the pool op's position now: a reader in between would see it too early
-                if any(any(_abuf(t) is _abuf(full.y) for t in o.acts_in()) for top in ops[i + 1:j] if top is not None for o in members_of(top)):
+                if any(i < at < j for at, _ in _readers_of(ops, full.y)):
                     continue
             group = [m for m in (full, half) if m is not None]
             if not self._ew_merge_intervals_ok(op, full, half, ops[i + 1:j], iv, hit):
@@ -314,9 +323,8 @@ class Lowering:
         """fpd_ew_merge_t of a pool-backward op that evaluates its apply(s) itself (plan_ew_merge decided)."""
         s = R.EwMergeT()
         s.kind = R.EWM_MAXPOOL_BWD if op.ewm_kind == 'maxpool_bwd' else R.EWM_SUMPOOL
-        s.has_full = 1 if op.ewm_full is not None else 0
         if op.ewm_full is not None:
-            s.full = self.ew(op.ewm_full, plain=True)[1]
+            s.has_full, s.full = 1, self.ew(op.ewm_full, plain=True)[1]
         if op.ewm_half is not None:
             s.half = self.ew(op.ewm_half, plain=True)[1]
         s.pool = self.ew(op, plain=True)[1]
@@ -338,17 +346,15 @@ class Lowering:
             return
         l = R.lib()
         readers = ops if readers is None else readers
-        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
         for op in ops:
-            sc = getattr(op, 'skip_conv', None) if op is not None and op.kind == 'conv' else None
+            sc = op.skip_conv if op is not None and op.kind == 'conv' else None
             if sc is None or not any(o is sc for o in ops) or (op.lane or 0) != (sc.lane or 0):
                 continue
-            if getattr(op, 'w8', None) is not None or getattr(sc, 'w8', None) is not None or sc.bn is not None:
+            if op.w8 is not None or sc.w8 is not None or sc.bn is not None:
                 continue
             if _abuf(sc.y) is not _abuf(op.residual) or sc.out_stats is not None:
                 continue
-            y = _abuf(sc.y)
-            if any(o is not op and any(_abuf(t) is y for t in o.acts_in()) for top in readers if top is not None for o in members_of(top)):
+            if any(_readers_of(readers, sc.y, exclude=(op,))):
                 continue
             s = self.conv(op, plain=True)[1]
             self._fill_skip(op, s)
@@ -363,22 +369,17 @@ class Lowering:
         if os.environ.get('FPD_STEM_ACT', '1') == '0':
             return
         readers = ops if readers is None else readers
-        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
         for op in ops:
-            ae = getattr(op, 'act_ew', None) if op is not None and op.kind == 'stem_fwd' else None
+            ae = op.act_ew if op is not None and op.kind == 'stem_fwd' else None
             if ae is None or not any(o is ae for o in ops) or (op.lane or 0) != (ae.lane or 0):
                 continue
             if ae.op != 'bnrelu_fwd' or ae.bn is None or ae.bn.mode != 'eval' or _abuf(ae.x) is not _abuf(op.y):
                 continue
             if op.out_stats is not None or ae.out_stats is not None:
                 continue
-            y = _abuf(op.y)
-            if any(o is not ae and any(_abuf(t) is y for t in o.acts_in()) for top in readers if top is not None for o in members_of(top)):
+            if any(_readers_of(readers, op.y, exclude=(ae,))):
                 continue
-            op.act_active = True
-            ok = R.lib().fpd_stem_act_supported(C.byref(self.stem(op)[1])) == 1
-            op.act_active = ok
-            ae.stem_fused = ok
+            op.act_active = ae.stem_fused = R.lib().fpd_stem_act_supported(C.byref(self.stem(op, act=True)[1])) == 1
 
     @staticmethod
     def plan_upadd(ops, readers=None, dtype=R.BF16):
@@ -392,18 +393,16 @@ class Lowering:
         if os.environ.get('FPD_BNECK_UPADD', '1') == '0':
             return 0
         readers = ops if readers is None else readers
-        members_of = lambda top: [m for m in ((top.a, top.b) if top.kind in ('conv2', 'ew2', 'bneck2') else (top,)) if m is not None]
         n = 0
         for op in ops:
-            if op is None or op.kind != 'bneck' or getattr(op, 'x2', None) is not None:
+            if op is None or op.kind != 'bneck' or op.x2 is not None:
                 continue
             ua = getattr(op.x, 'producer', None)
             if ua is None or ua.kind != 'ew' or ua.op != 'upadd_fwd' or ua.out_stats is not None or op.x.stats is not None:
                 continue
             if ua.y is not op.x or op.x.persistent or not any(o is ua for o in ops) or (op.lane or 0) != (ua.lane or 0):
                 continue
-            rd = [o for top in readers if top is not None for o in members_of(top) if any(t is op.x for t in o.acts_in())]
-            if len(rd) != 1 or rd[0] is not op:
+            if [o for _, o in _readers_of(readers, op.x, by_buf=False)] != [op]:      # (by Act: no tensor has a buf yet)
                 continue
             s = R.BneckT()
             (s.N, s.H, s.W, s.C, s.P), s.dtype = op.dims, dtype
@@ -416,7 +415,7 @@ class Lowering:
 
     def _fill_fold(self, op, s):
         """Fold fields of a data gradient that evaluates its BN-backward apply itself (plan_folds decided)."""
-        if not getattr(op, 'fold_active', False):
+        if not op.fold_active:
             return
         ap, p = op.fold_apply, self.A.ptr
         assert ap.add is None and _abuf(ap.y) is _abuf(op.x), 'fold: the apply must produce exactly this operand'
@@ -424,19 +423,26 @@ class Lowering:
         s.fold_x, s.fold_bn, s.fold_stats = p(_abuf(ap.x)), self.bn(ap.bn), p(ap.bstats)
         s.fold_dgamma, s.fold_dbeta = p(ap.dgamma), p(ap.dbeta)
         # its other consumer -- the convolution's weight gradient -- reads the evaluated operand unless it is formed right here
-        skip = getattr(op, 'fused_active', False) and not getattr(op, 'fold_other_readers', False)
+        skip = op.fused_active and not op.fold_other_readers
         s.fold_out = None if skip else p(_abuf(ap.y))
+
+    def _register_slabs(self, wg, s, n, nbias):
+        """The launch of struct `s` writes weight gradient `wg` (an IR 'wgrad' / 'stem_wgrad' op) as `n` slabs of its own, no
+        device-scope atomics: finish_partials() places them and patches `s`, the bucket's 'wreduce' sums them.  With n == 0, and in
+        every struct never registered, the slab fields stay null as ctypes made them: the launch sums into dw itself."""
+        if n > 0:
+            numel = wg.dw.numel
+            stride = (numel + nbias + 63) // 64 * 64        # weight slab + bias partials
+            self.partials[id(wg)] = Slabs(s, wg.dw, numel, stride, n, self.partial_elems, wg.dbias, nbias)
+            self.partial_elems += n * stride
 
     def _fuse_wgrad(self, op, s, n):
         """The data-gradient launch `op` (struct `s`, a ConvT -- possibly a field of a pair struct) also forms the weight
-        gradient of `op.fused_wgrad` into `n` slabs: register them like a weight-gradient kernel's (finish_partials patches
-        the struct, the bucket's 'wreduce' sums them) and turn the separate 'wgrad' op into a no-op."""
+        gradient of `op.fused_wgrad` into `n` slabs: register them like a weight-gradient kernel's and turn the separate
+        'wgrad' op into a no-op."""
         fw = op.fused_wgrad
-        numel = fw.dw.numel                                 # [Kf][1][1][Cf] = [s.C][s.K]
-        assert numel == s.C * s.K, (numel, s.C, s.K)
-        stride = (numel + s.C + 63) // 64 * 64              # weight slab + bias partials
-        self.partials[id(fw)] = [s, fw.dw, numel, stride, n, self.partial_elems, fw.dbias, s.C]
-        self.partial_elems += n * stride
+        assert fw.dw.numel == s.C * s.K, (fw.dw.numel, s.C, s.K)     # [Kf][1][1][Cf] = [s.C][s.K]
+        self._register_slabs(fw, s, n, s.C)
         s.wg_bias = 1 if fw.dbias is not None else 0
         s.wg_count = n                                      # the launch refuses a geometry that writes another number of slabs
         self.fused.add(id(fw))
@@ -462,13 +468,12 @@ class Lowering:
         s.x, s.y = p(_abuf(op.x)), p(_abuf(op.y))
         s.w1, s.b1, s.w2, s.b2, s.w3, s.b3 = p(op.w1), p(op.b1), p(op.w2), p(op.b2), p(op.w3), p(op.b3)
         s.bn1, s.bn2, s.bn3 = self.bn(op.bn1), self.bn(op.bn2), self.bn(op.bn3)
-        s.folded = p(getattr(op, 'folded', None))
-        x2 = getattr(op, 'x2', None)
-        if x2 is not None:                                 # up-add on load (plan_upadd): y overlaps neither source in the arena
+        s.folded = p(op.folded)                            # (the fold table's Buf, or None)
+        if op.x2 is not None:                              # up-add on load (plan_upadd): y overlaps neither source in the arena
             yb = _abuf(op.y)
-            for t in (_abuf(op.x), _abuf(x2)):
+            for t in (_abuf(op.x), _abuf(op.x2)):
                 assert t.arena != yb.arena or t.off + t.numel <= yb.off or yb.off + yb.numel <= t.off, 'bneck: y overlaps a source of its up-add'
-            s.x2 = p(_abuf(x2))
+            s.x2 = p(_abuf(op.x2))
         return R.OP_BNECK, s
 
     def head(self, op):
@@ -480,34 +485,28 @@ class Lowering:
         s.w_fc, s.b_fc, s.w_score, s.b_score = p(op.w_fc), p(op.b_fc), p(op.w_score), p(op.b_score)
         s.w_fc2, s.b_fc2, s.w_score2, s.b_score2 = p(op.w_fc2), p(op.b_fc2), p(op.w_score2), p(op.b_score2)
         s.bn = self.bn(op.bn)
-        s.folded = p(getattr(op, 'folded', None))
+        s.folded = p(op.folded)
         return R.OP_HEAD, s
 
     def wgrad(self, op):
         if id(op) in self.fused:                           # formed by the data-gradient launch (fpd_conv_t.wg_partial)
-            return R.OP_NOP, R.MemsetT()
+            return _nop()
         s = R.WgradT()
         (s.N, s.H, s.W, s.C, s.K, s.R, s.S, s.stride, s.pad, s.P, s.Q) = op.dims
         s.dtype = self.dtype
         p = self.A.ptr
         s.x, s.dy, s.dw, s.dbias = p(_abuf(op.x)), p(_abuf(op.dy)), p(op.dw), p(op.dbias)
         s.bn = self.bn(op.bn)
-        s.partial, s.partial_stride = None, 0
         if self.use_partials:
             # two-stage reduction instead of device-scope atomics: ask the library how many slabs this launch writes
-            n = R.lib().fpd_wgrad_num_partials(C.byref(s))
-            if n > 0:
-                numel = op.dw.numel
-                stride = (numel + s.K + 63) // 64 * 64          # weight slab + bias partials
-                self.partials[id(op)] = [s, op.dw, numel, stride, n, self.partial_elems, op.dbias, s.K]
-                self.partial_elems += n * stride
+            self._register_slabs(op, s, R.lib().fpd_wgrad_num_partials(C.byref(s)), s.K)
         return R.OP_WGRAD, s
 
     def wreduce(self, op):
         """Second stage of the weight-gradient reduction for the convolutions of ONE gradient bucket (op.wgrads, all
         lowered before this op): dw += sum of slabs, one launch.  The table is filled in by finish_partials()."""
         if not any(id(w) in self.partials for w in op.wgrads):
-            return R.OP_NOP, R.MemsetT()
+            return _nop()
         t = R.TableT()
         self.reduces.append((op, t))
         return R.OP_WREDUCE, t
@@ -519,30 +518,27 @@ class Lowering:
             return
         ws = torch.empty(self.partial_elems, dtype=torch.float32, device=self.A.device)
         self.keep.append(ws)
-        for s, dw, numel, stride, n, off, dbias, nbias in self.partials.values():
-            if isinstance(s, R.ConvT):                    # fused into a data-gradient launch
-                s.wg_partial, s.wg_stride = ws.data_ptr() + 4 * off, stride
+        for wg, r in self.partials.items():
+            if wg in self.fused:                          # formed by a data-gradient launch: r.s is its ConvT
+                r.s.wg_partial, r.s.wg_stride = ws.data_ptr() + 4 * r.off, r.stride
             else:
-                s.partial, s.partial_stride = ws.data_ptr() + 4 * off, stride
+                r.s.partial, r.s.partial_stride = ws.data_ptr() + 4 * r.off, r.stride
         for op, t in self.reduces:
             ents, mx = [], 0
             for w in op.wgrads:
-                rec = self.partials.get(id(w))
-                if rec is None:
+                r = self.partials.get(id(w))
+                if r is None:
                     continue
-                s, dw, numel, stride, n, off, dbias, nbias = rec
-                base = ws.data_ptr() + 4 * off
-                e = R.WreduceEntryT()
-                e.partial, e.dw, e.n, e.stride, e.count = base, self.A.ptr(dw), numel, stride, n
-                ents.append(e)
-                if dbias is not None:
-                    e = R.WreduceEntryT()
-                    e.partial, e.dw, e.n, e.stride, e.count = base + 4 * numel, self.A.ptr(dbias), nbias, stride, n
-                    ents.append(e)
-                mx = max(mx, numel)
+                for at, dst, count in ((r.off, r.dw, r.numel), (r.off + r.numel, r.dbias, r.nbias)):      # a slab: weights, then bias sums
+                    if dst is not None:
+                        e = R.WreduceEntryT()
+                        e.partial, e.dw, e.n, e.stride, e.count = ws.data_ptr() + 4 * at, self.A.ptr(dst), count, r.stride, r.n
+                        ents.append(e)
+                mx = max(mx, r.numel)
             t.table, t.n, t.dtype, t.max_elems = self._table(ents, R.WreduceEntryT), len(ents), self.dtype, mx
 
-    def stem(self, op):
+    def stem(self, op, act=None):
+        """act: whether a 'stem_fwd' applies its `act_ew`; None = as decided (`act_active`), True = plan_stem_act's candidate."""
         s = R.StemT()
         (s.N, s.H, s.W, s.K, s.P, s.Q) = op.dims
         s.dtype = self.dtype
@@ -550,31 +546,20 @@ class Lowering:
         s.x = p(op.image)
         if op.kind == 'stem_fwd':
             s.w, s.bias, s.y, s.out_stats = p(op.w), p(op.bias), p(_abuf(op.y)), p(op.out_stats)
-            if getattr(op, 'act_active', False):           # bn1 + ReLU in the epilogue: the stem writes the activation (plan_stem_act)
+            if op.act_active if act is None else act:      # bn1 + ReLU in the epilogue: the stem writes the activation
                 s.act, s.y = self.bn(op.act_ew.bn), p(_abuf(op.act_ew.y))
             return R.OP_STEM_FWD, s
         s.dy, s.dw, s.dbias = p(_abuf(op.dy)), p(op.dw), p(op.dbias)
-        s.partial, s.partial_stride = None, 0
         if self.use_partials:                  # same two-stage reduction as the other weight gradients (no atomics)
-            n = R.lib().fpd_stem_wgrad_num_partials(C.byref(s))
-            if n > 0:
-                numel = op.dw.numel
-                stride = (numel + s.K + 63) // 64 * 64
-                self.partials[id(op)] = [s, op.dw, numel, stride, n, self.partial_elems, op.dbias, s.K]
-                self.partial_elems += n * stride
+            self._register_slabs(op, s, R.lib().fpd_stem_wgrad_num_partials(C.byref(s)), s.K)
         return R.OP_STEM_WGRAD, s
 
     def ew(self, op, plain=False):
-        if not plain and getattr(op, 'ewm_absorbed', False):   # evaluated inside the pool-backward op that reads it (plan_ew_merge)
-            return R.OP_NOP, R.MemsetT()
-        if getattr(op, 'upadd_absorbed', False):           # formed on load by the fused Bottleneck that reads it (plan_upadd)
-            return R.OP_NOP, R.MemsetT()
-        if not plain and getattr(op, 'ewm_kind', None) is not None:
+        """plain=True: the op's own struct as a member of an OP_EW_MERGE -- plan_ew_merge's decisions are ignored, the others are not."""
+        if op.absorbed(merged=not plain):
+            return _nop()
+        if not plain and op.ewm_kind is not None:
             return self.ew_merge(op)
-        if getattr(op, 'folded', False):                   # evaluated by the data gradient that consumes it (plan_folds)
-            return R.OP_NOP, R.MemsetT()
-        if getattr(op, 'stem_fused', False):               # applied in the epilogue of the stem that produces its input (plan_stem_act)
-            return R.OP_NOP, R.MemsetT()
         s = R.EwT()
         s.op, s.dtype = _EW[op.op], self.dtype
         (s.N, s.H, s.W, s.C) = op.dims
@@ -623,12 +608,11 @@ class Lowering:
 
     def op(self, op):
         if _WHATIF and _whatif_drop(op, getattr(self, 'train', True)):
-            return R.OP_NOP, R.MemsetT()
+            return _nop()
         if op.kind == 'conv2':
             s = R.ConvPairT()
             s.a, s.b = self.conv(op.a, plain=True)[1], self.conv(op.b, plain=True)[1]
-            if (self.use_partials and getattr(op.a, 'fused_wgrad', None) is not None and
-                    getattr(op.b, 'fused_wgrad', None) is not None):
+            if self.use_partials and op.a.fused_wgrad is not None and op.b.fused_wgrad is not None:
                 na, nb = C.c_int32(0), C.c_int32(0)
                 R.check(R.lib().fpd_conv_pair_fused_wgrad_partials(C.byref(s), C.byref(na), C.byref(nb)), 'fpd_conv_pair_fused_wgrad_partials')
                 if na.value > 0 and nb.value > 0:          # s.a / s.b are views INTO the pair struct: patched in place later
@@ -638,11 +622,9 @@ class Lowering:
             self._fill_fold(op.b, s.b)
             return R.OP_CONV_PAIR, s
         if op.kind == 'ew2':
-            if getattr(op.a, 'ewm_absorbed', False) and getattr(op.b, 'ewm_absorbed', False):      # both inside the pool backward behind them
-                return R.OP_NOP, R.MemsetT()
-            fa, fb = getattr(op.a, 'folded', False), getattr(op.b, 'folded', False)
-            if fa or fb:                                   # folded members leave the pair
-                return (R.OP_NOP, R.MemsetT()) if (fa and fb) else self.ew(op.b if fa else op.a)
+            live = [m for m in op.members() if not m.absorbed()]
+            if len(live) < 2:                              # absorbed members leave the pair: a folded apply's partner goes out
+                return self.ew(live[0]) if live else _nop()      # alone, a pair inside the pool backward behind it not at all
             s = R.EwPairT()
             s.a, s.b = self.ew(op.a)[1], self.ew(op.b)[1]
             return R.OP_EW_PAIR, s
@@ -650,8 +632,6 @@ class Lowering:
             s = R.BneckPairT()
             s.a, s.b = self.bneck(op.a)[1], self.bneck(op.b)[1]
             return R.OP_BNECK_PAIR, s
-        if op.kind == 'head':
-            return self.head(op)
         if op.kind == 'head_fold':
             return R.OP_HEAD_FOLD, self.head(op.target)[1]
         if op.kind == 'bneck_fold':
@@ -670,12 +650,10 @@ class Lowering:
             (s.N, s.C, s.H, s.W) = op.dims
             s.src, s.dst, s.dtype = self.A.ptr(op.image), self.A.ptr(_abuf(op.y)), self.dtype
             return R.OP_NCHW2NHWC, s
-        if op.kind == 'wreduce':
-            return self.wreduce(op)
         if op.kind == 'grad_ready':
-            return R.OP_NOP, R.MemsetT()
-        return {'conv': self.conv, 'bneck': self.bneck, 'wgrad': self.wgrad, 'stem_fwd': self.stem, 'stem_wgrad': self.stem, 'ew': self.ew,
-                'bnupd': self.bnupd}[op.kind](op)
+            return _nop()
+        return {'conv': self.conv, 'bneck': self.bneck, 'head': self.head, 'wgrad': self.wgrad, 'wreduce': self.wreduce, 'stem_fwd': self.stem,
+                'stem_wgrad': self.stem, 'ew': self.ew, 'bnupd': self.bnupd}[op.kind](op)
 
 
 class ModelState:
@@ -783,11 +761,9 @@ class GraphInstance:
             self.A.alloc('w8s', g.w8s_size)
             p.add(*self.low.wquant([(self.state.table[k], q, sc) for k, (q, sc) in w8.items()]))
         for op in g.fwd:                           # frozen fused Bottlenecks: fold BN + biases into tables once
-            for sub in ((op.a, op.b) if op.kind == 'bneck2' else (op,)):
-                if sub.kind == 'bneck' and getattr(sub, 'folded', None) is not None:
-                    p.add(*self.low.op(G.Op('bneck_fold', target=sub)))
-                if sub.kind == 'head' and getattr(sub, 'folded', None) is not None:
-                    p.add(*self.low.op(G.Op('head_fold', target=sub)))
+            for sub in op.members():
+                if sub.kind in ('bneck', 'head') and sub.folded is not None:
+                    p.add(*self.low.op(G.Op(sub.kind + '_fold', target=sub)))
         self.rng['prep'] = (b, len(p))
         b = len(p)
         self.op_index = {}                         # id(IR op) -> plan op (bench.py times single recorded ops through it)

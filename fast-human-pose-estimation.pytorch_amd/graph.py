@@ -96,12 +96,52 @@ def f8_conv_domain(dims):
 
 
 class Op:
-    """kind in {conv, wgrad, stem_fwd, stem_wgrad, ew, loss, adam, memset, wprep, bnupd}; free-form fields."""
+    """kind in {conv, wgrad, stem_fwd, stem_wgrad, ew, loss, adam, memset, wprep, bnupd}; free-form fields.
+
+    Lowering-time fusion state is declared, with class-level defaults, so that a misspelt name is an AttributeError and not "not
+    fused".  The graph builder sets a relation, which only offers a fusion; a planner of executor.Lowering takes the decision
+    before the list is lowered, and accesses() / acts_in() / acts_out() follow it: that is what schedule and memory plan see.
+
+    field              kind       set by           meaning (accesses | lowering)
+    fold_apply         conv       builder          the BN-backward apply that produces this data gradient's operand
+    fold_wgrad         conv       builder          that convolution's weight gradient: the apply result's one expected other reader
+    fused_wgrad        conv       builder          the 1x1 weight gradient this data gradient may form itself
+    skip_conv          conv       builder          the downsample 1x1 whose result is this conv3's residual (acts_in keeps its x)
+    act_ew             stem_fwd   builder          the frozen bn1 + ReLU behind the stem (acts_out keeps its y)
+    w8, w8s            conv       builder          e4m3 weight copy and scales: read | lowered as OP_CONV_F8
+    fold_active        conv       plan_folds       evaluates fold_apply: reads its inputs, writes its outputs | fpd_conv_t.fold_*
+    folded             ew         plan_folds       True: the apply is evaluated by the data gradient that consumes it | absorbed
+                       bneck,head builder          NOT a flag: the Buf of the folded BN table, hence the default None | the arena takes None, not False
+    fold_other_readers conv       plan_folds       somebody else reads the apply's result | the launch writes it out (fold_out)
+    fused_active       conv       _fuse_wgrad      forms fused_wgrad: writes its dw / dbias | the 'wgrad' op is a no-op
+    skip_active        conv       plan_skips       forms skip_conv: reads its x, w, bias | fpd_conv_t.x2, no residual
+    skip_fused         conv       plan_skips       the downsample formed by its conv3 | absorbed
+    act_active         stem_fwd   plan_stem_act    applies act_ew: reads its BN, writes its y | fpd_stem_t.act
+    stem_fused         ew         plan_stem_act    the activation applied by the stem | absorbed
+    ewm_kind           ew         plan_ew_merge    'maxpool_bwd' / 'sumpool': this pool backward evaluates the applies ewm_full / ewm_half
+    ewm_full, ewm_half ew         plan_ew_merge    (full / half resolution, either may be None): reads their inputs, writes their outputs | OP_EW_MERGE
+    ewm_absorbed       ew         plan_ew_merge    an apply evaluated by that pool backward | absorbed
+    upadd_absorbed     ew         plan_upadd       an up-add formed on load: no accesses, no tensors, y never placed | absorbed
+    upadd_op, x2       bneck      plan_upadd       the absorbed up-add; x / x2 are its sources, both read | fpd_bneck_t.x2
+    """
+    PAIRS = ('conv2', 'ew2', 'bneck2')     # containers: two independent convs / elementwise ops / fused Bottlenecks `a`, `b`, one launch
+    fold_apply = fold_wgrad = fused_wgrad = skip_conv = act_ew = w8 = w8s = folded = ewm_kind = ewm_full = ewm_half = upadd_op = x2 = None
+    fold_active = fold_other_readers = fused_active = skip_active = skip_fused = act_active = stem_fused = ewm_absorbed = upadd_absorbed = False
 
     def __init__(self, kind, **kw):
         self.kind = kind
         self.lane = None               # execution lane (HIP stream) -- stamped by the builder's op lists
         self.__dict__.update(kw)
+
+    def members(self):
+        """The ops one launch carries: the filled halves of a 'conv2' / 'ew2' / 'bneck2' container, else the op itself."""
+        if self.kind in self.PAIRS:
+            return [m for m in (self.a, self.b) if m is not None]
+        return [self]
+
+    def absorbed(self, merged=True):
+        """Another launch does this op's work: it lowers to a no-op.  merged=False: but for `ewm_absorbed` (the merged launch builds that struct)."""
+        return bool(self.skip_fused or self.upadd_absorbed or self.stem_fused or (self.kind == 'ew' and self.folded) or (merged and self.ewm_absorbed))
 
     def accesses(self):
         """(reads, writes) as lists of Buf -- what the dependency analysis of the multi-lane schedule sees.
@@ -114,30 +154,27 @@ class Op:
                 return []
             return [bn.gamma, bn.beta] + ([bn.stats] if bn.mode == 'train' else [bn.rmean, bn.rvar])
         k = self.kind
-        if k in ('conv2', 'bneck2', 'ew2'):    # two independent convs / fused Bottlenecks / elementwise ops, one launch
-            (ra, wa), (rb, wb) = self.a.accesses(), self.b.accesses()
-            return ra + rb, wa + wb
+        if k in self.PAIRS:
+            acc = [m.accesses() for m in self.members()]
+            return sum((r for r, _ in acc), []), sum((w for _, w in acc), [])
         if k == 'conv':
             rd = [b(self.x), self.w, self.bias, b(self.residual), b(self.epi_x)] + bn_bufs(self.bn) + bn_bufs(self.epi_bn)
-            rd += [getattr(self, 'w8', None), getattr(self, 'w8s', None)]
+            rd += [self.w8, self.w8s]
             wr = [b(self.y), self.out_stats, self.epi_stats]
-            fw = getattr(self, 'fused_wgrad', None)        # this data gradient also writes the slabs of that weight gradient
-            if fw is not None and getattr(self, 'fused_active', False):
+            fw, fa, sc = self.fused_wgrad, self.fold_apply, self.skip_conv
+            if fw is not None and self.fused_active:       # this data gradient also writes the slabs of that weight gradient
                 wr += [fw.dw, fw.dbias]
-            fa = getattr(self, 'fold_apply', None)         # it may evaluate that BN-backward apply itself (executor decides,
-            if fa is not None and getattr(self, 'fold_active', False):     # before the schedule is built): then it reads the
-                # apply's inputs and writes its outputs
+            if fa is not None and self.fold_active:        # it evaluates that BN-backward apply itself (executor.plan_folds decided, before the schedule is built)
                 rd += [b(fa.x), b(fa.dy), fa.bstats] + bn_bufs(fa.bn)
                 wr += [b(fa.y), fa.dgamma, fa.dbeta]
-            sc = getattr(self, 'skip_conv', None)          # conv3 of a downsample Bottleneck may form the skip convolution itself
-            if sc is not None and getattr(self, 'skip_active', False):      # (executor.plan_skips): then it reads that op's inputs
+            if sc is not None and self.skip_active:        # conv3 of a downsample Bottleneck forms the skip convolution itself (executor.plan_skips)
                 rd += [b(sc.x), sc.w, sc.bias]
         elif k == 'head':
             rd = [b(self.y0), b(self.x), self.w_fc, self.b_fc, self.w_score, self.b_score, self.w_fc2, self.b_fc2,
                   self.w_score2, self.b_score2] + bn_bufs(self.bn)
             wr = [b(self.score), b(self.next)]
         elif k == 'bneck':                     # (x2: the low branch of an up-add it forms on load, executor.plan_upadd)
-            rd = [b(self.x), b(getattr(self, 'x2', None)), self.w1, self.b1, self.w2, self.b2, self.w3, self.b3] + bn_bufs(self.bn1) + \
+            rd = [b(self.x), b(self.x2), self.w1, self.b1, self.w2, self.b2, self.w3, self.b3] + bn_bufs(self.bn1) + \
                 bn_bufs(self.bn2) + bn_bufs(self.bn3)
             wr = [b(self.y)]
         elif k == 'wgrad':
@@ -156,19 +193,18 @@ class Op:
             rd, wr = [self.region], []
         elif k == 'stem_fwd':
             rd, wr = [self.image, self.w, self.bias], [b(self.y), self.out_stats]
-            ae = getattr(self, 'act_ew', None)             # the frozen stem may apply its BN + ReLU itself (executor.plan_stem_act)
-            if ae is not None and getattr(self, 'act_active', False):
-                rd += bn_bufs(ae.bn)
-                wr += [b(ae.y)]
+            if self.act_ew is not None and self.act_active:      # the frozen stem applies its BN + ReLU itself (executor.plan_stem_act)
+                rd += bn_bufs(self.act_ew.bn)
+                wr += [b(self.act_ew.y)]
         elif k == 'stem_wgrad':
             rd, wr = [self.image, b(self.dy)], [self.dw, self.dbias]
         elif k == 'ew':
-            if getattr(self, 'upadd_absorbed', False):           # formed on load by the fused Bottleneck that reads it: accesses nothing
+            if self.upadd_absorbed:                # formed on load by the fused Bottleneck that reads it: accesses nothing
                 return [], []
             rd = [b(self.x), b(self.x2), b(self.dy), b(self.add)] + bn_bufs(self.bn)
             wr = [b(self.y), self.out_stats, self.bstats, self.dgamma, self.dbeta]    # bstats: produced or consumed
-            if getattr(self, 'ewm_kind', None) is not None:      # a pool backward that evaluates its BN-backward apply(s) itself
-                for m in (self.ewm_full, self.ewm_half):         # (executor.plan_ew_merge): it reads their inputs and writes their outputs
+            if self.ewm_kind is not None:          # a pool backward that evaluates its BN-backward apply(s) itself: it reads
+                for m in (self.ewm_full, self.ewm_half):         # their inputs and writes their outputs (executor.plan_ew_merge)
                     if m is not None:
                         rd += [b(m.x), b(m.dy), b(m.add)] + bn_bufs(m.bn)
                         wr += [b(m.y), m.bstats, m.dgamma, m.dbeta]
@@ -177,30 +213,29 @@ class Op:
         return [x for x in rd if x is not None], [x for x in wr if x is not None]
 
     def acts_in(self):
-        if self.kind in ('conv2', 'bneck2', 'ew2'):
-            return self.a.acts_in() + self.b.acts_in()
+        if self.kind in self.PAIRS:
+            return [t for m in self.members() for t in m.acts_in()]
         if self.kind == 'head':
             return [t for t in (self.y0, self.x) if t is not None]
-        if getattr(self, 'upadd_absorbed', False):         # its sources are inputs of the Bottleneck, its result does not exist
+        if self.upadd_absorbed:                            # its sources are inputs of the Bottleneck, its result does not exist
             return []
-        fa = getattr(self, 'fold_apply', None)
+        fa, sc = self.fold_apply, self.skip_conv
         folded = [t for t in (fa.x, fa.dy) if isinstance(t, Act)] if fa is not None else []
-        sc = getattr(self, 'skip_conv', None)              # (conservatively, whatever the lowering decides: x stays alive up to conv3)
-        if sc is not None and isinstance(sc.x, Act):
+        if sc is not None and isinstance(sc.x, Act):       # (conservatively, whatever the lowering decides: x stays alive up to conv3)
             folded = folded + [sc.x]
         return [getattr(self, f) for f in ('x', 'x2', 'dy', 'add', 'residual', 'epi_x') if
                 isinstance(getattr(self, f, None), Act)] + [a for a in getattr(self, 'extra_in', []) if a is not None] + folded
 
     def acts_out(self):
-        if self.kind in ('conv2', 'bneck2', 'ew2'):
-            return self.a.acts_out() + self.b.acts_out()
+        if self.kind in self.PAIRS:
+            return [t for m in self.members() for t in m.acts_out()]
         if self.kind == 'head':
             return [t for t in (self.score, self.next) if t is not None]
-        if getattr(self, 'upadd_absorbed', False):
+        if self.upadd_absorbed:
             return []
-        ae = getattr(self, 'act_ew', None)                 # (conservatively: the activation's buffer exists when the stem runs)
         return [getattr(self, f) for f in ('y',) if isinstance(getattr(self, f, None), Act)] + \
-               [a for a in getattr(self, 'extra_out', []) if a is not None] + ([ae.y] if ae is not None else [])
+               [a for a in getattr(self, 'extra_out', []) if a is not None] + \
+               ([self.act_ew.y] if self.act_ew is not None else [])      # (conservatively: the activation's buffer exists when the stem runs)
 
 
 # ------------------------------------------------------------------------------------------------
