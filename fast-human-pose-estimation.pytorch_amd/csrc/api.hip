@@ -99,6 +99,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
     SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t);
+    SZ(fpd_vis_minmax_t); SZ(fpd_vis_max_preds_t); SZ(fpd_vis_joints_grid_t); SZ(fpd_vis_heatmap_grid_t);
 #undef SZ
     return -1;
 }
@@ -491,6 +492,62 @@ int fpd_val_post(const fpd_val_post_t* a, fpd_stream_t stream) {
     if (a->b != nullptr)
         for (int j = 0; j < a->J; ++j) FPD_REQUIRE(a->src[j] >= 0 && a->src[j] < a->J, "val_post: src[%d] = %d out of range", j, a->src[j]);
     int rc = fpd_val_post_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
+// ---- debug images (csrc/vis.hip) ----
+static int validate_vis_map(const char* what, int dtype, int layout) {
+    FPD_REQUIRE(layout == FPD_VIS_NCHW || layout == FPD_VIS_NHWC, "%s: bad layout %d", what, layout);
+    FPD_REQUIRE(dtype == FPD_F32 || (dtype == FPD_BF16 && layout == FPD_VIS_NHWC), "%s: bad dtype %d for layout %d (NCHW maps are float32)",
+                what, dtype, layout);
+    return 0;
+}
+int fpd_vis_minmax(const fpd_vis_minmax_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->x && a->out, "vis_minmax: null pointer");
+    FPD_REQUIRE(a->n > 0, "vis_minmax: n = %lld is not positive", (long long)a->n);
+    FPD_REQUIRE((const void*)a->out != (const void*)a->x, "vis_minmax: out aliases the input");
+    int rc = fpd_vis_minmax_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_vis_max_preds(const fpd_vis_max_preds_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->hm && a->preds && a->maxvals, "vis_max_preds: null pointer");
+    FPD_REQUIRE(a->N > 0 && a->J > 0 && a->h > 0 && a->w > 0, "vis_max_preds: bad dims");
+    FPD_REQUIRE((int64_t)a->N * a->J * a->h * a->w < ((int64_t)1 << 31), "vis_max_preds: map too large");
+    int rc = validate_vis_map("vis_max_preds", a->dtype, a->layout);
+    if (rc) return rc;
+    FPD_REQUIRE((const void*)a->preds != a->hm && (const void*)a->maxvals != a->hm && a->preds != a->maxvals, "vis_max_preds: an output aliases another buffer");
+    rc = fpd_vis_max_preds_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_vis_joints_grid(const fpd_vis_joints_grid_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->image && a->minmax && a->joints && a->vis && a->canvas, "vis_joints_grid: null pointer");
+    FPD_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->J > 0, "vis_joints_grid: bad dims");
+    FPD_REQUIRE(a->nrow >= 1, "vis_joints_grid: nrow = %d (>= 1)", a->nrow);
+    FPD_REQUIRE(a->padding >= 0 && a->padding <= 4096, "vis_joints_grid: padding = %d (0..4096)", a->padding);
+    FPD_REQUIRE(a->joints_stride >= 2, "vis_joints_grid: joints_stride = %d (>= 2)", a->joints_stride);
+    FPD_REQUIRE((int64_t)a->N * 3 * a->H * a->W < ((int64_t)1 << 40), "vis_joints_grid: image too large");
+    const int64_t bytes = fpd_vis_joints_canvas_bytes(*a);
+    FPD_REQUIRE(bytes < ((int64_t)1 << 31), "vis_joints_grid: canvas too large");
+    FPD_REQUIRE(a->canvas_bytes == bytes, "vis_joints_grid: canvas_bytes = %lld, the grid takes %lld", (long long)a->canvas_bytes, (long long)bytes);
+    const void* c = a->canvas;
+    FPD_REQUIRE(c != (const void*)a->image && c != (const void*)a->minmax && c != a->joints && c != (const void*)a->vis,
+                "vis_joints_grid: canvas aliases an input");
+    int rc = fpd_vis_joints_grid_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+int fpd_vis_heatmap_grid(const fpd_vis_heatmap_grid_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->image && a->hm && a->preds && a->table && a->canvas && (a->minmax || !a->normalize), "vis_heatmap_grid: null pointer");
+    FPD_REQUIRE(a->N > 0 && a->h > 0 && a->w > 0 && a->J > 0 && a->J <= FPD_MAX_JOINTS, "vis_heatmap_grid: bad dims (J <= %d)", FPD_MAX_JOINTS);
+    FPD_REQUIRE(a->H == 4 * a->h && a->W == 4 * a->w, "vis_heatmap_grid: image %dx%d is not 4x the %dx%d heat map", a->H, a->W, a->h, a->w);
+    FPD_REQUIRE((int64_t)a->N * a->J * a->h * a->w < ((int64_t)1 << 31), "vis_heatmap_grid: map too large");
+    int rc = validate_vis_map("vis_heatmap_grid", a->dtype, a->layout);
+    if (rc) return rc;
+    const int64_t bytes = (int64_t)a->N * a->h * (a->J + 1) * a->w * 3;
+    FPD_REQUIRE(a->canvas_bytes == bytes, "vis_heatmap_grid: canvas_bytes = %lld, the grid takes %lld", (long long)a->canvas_bytes, (long long)bytes);
+    const void* c = a->canvas;
+    FPD_REQUIRE(c != (const void*)a->image && c != (const void*)a->minmax && c != a->hm && c != (const void*)a->preds && c != (const void*)a->table,
+                "vis_heatmap_grid: canvas aliases an input");
+    rc = fpd_vis_heatmap_grid_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 int fpd_render_targets(const fpd_targets_t* a, fpd_stream_t stream) {

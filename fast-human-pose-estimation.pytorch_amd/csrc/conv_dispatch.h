@@ -110,6 +110,11 @@ int fpd_flip_w_launch(const float* x, float* y, int64_t rows, int W, hipStream_t
 int fpd_flip_merge_launch(const fpd_flipmerge_t& p, hipStream_t st);
 int fpd_final_preds_launch(const fpd_finalpreds_t& p, hipStream_t st);
 int fpd_val_post_launch(const fpd_val_post_t& p, hipStream_t st);
+int fpd_vis_minmax_launch(const fpd_vis_minmax_t& p, hipStream_t st);             // csrc/vis.hip
+int fpd_vis_max_preds_launch(const fpd_vis_max_preds_t& p, hipStream_t st);
+int fpd_vis_joints_grid_launch(const fpd_vis_joints_grid_t& p, hipStream_t st);
+int fpd_vis_heatmap_grid_launch(const fpd_vis_heatmap_grid_t& p, hipStream_t st);
+int64_t fpd_vis_joints_canvas_bytes(const fpd_vis_joints_grid_t& p);
 int fpd_render_targets_launch(const fpd_targets_t& a, hipStream_t st);
 int fpd_warp_affine_launch(const fpd_warp_t& a, hipStream_t st);
 int fpd_render_targets_w_launch(const fpd_targets_w_t& a, hipStream_t st);

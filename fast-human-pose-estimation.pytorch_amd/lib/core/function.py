@@ -9,6 +9,7 @@ synchronisation of the loop -- when a log line is due (PRINT_FREQ) and at the en
 Not silently substituted: the fused step implements Adam and SGD (lib.utils.utils.FusedAdam / FusedSGD) and JointsMSELoss /
 JointsOHKMMSELoss criteria; any other optimizer / criterion object raises instead of being ignored."""
 import logging
+import os
 import time
 
 import torch
@@ -84,8 +85,45 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     return step
 
 
-def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha):
+DEBUG_WRITER_ASYNC = True      # tools/vis_bench.py measures the loops with the writer forced synchronous
+
+
+def _debug_on(config):
+    """DEBUG.DEBUG; a config object without the DEBUG node (callers that build only the keys the loops read) means off."""
+    try:
+        return bool(config.DEBUG.DEBUG)
+    except (AttributeError, KeyError):
+        return False
+
+
+def _debug_writer(config, rank):
+    """(utils.vis, writer) of one fpd_train / train / validate call when DEBUG.DEBUG asks rank 0 for debug images, else
+    (None, None): with the flag off nothing of utils.vis is imported or touched.  The caller closes the writer before it
+    returns, so the files exist by then."""
+    if rank != 0 or not _debug_on(config):
+        return None, None
+    from ..utils import vis
+    return vis, (vis.AsyncImageWriter() if DEBUG_WRITER_ASYNC else None)
+
+
+def _on_device(t, dev):
+    return t if t.is_cuda else t.to(dev, non_blocking=True)
+
+
+def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
+               output_dir='', rank=0):
     """The loop shared by fpd_train (function.py:99-187) and train (function.py:28-96; tmodel None, alpha 0)."""
+    vis, img_writer = _debug_writer(config, rank)
+    try:
+        return _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
+                               alpha, output_dir, vis, img_writer)
+    finally:
+        if img_writer is not None:
+            img_writer.close()
+
+
+def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
+                    output_dir, vis, img_writer):
     kd_mode = tmodel is not None
     use_w, ohkm = crit
     batch_time, data_time = AverageMeter(), AverageMeter()
@@ -127,6 +165,13 @@ def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writ
             step.teacher_async(nxt[0])                 # teacher runs one batch ahead, overlapping this student step
         step.student_step(allreduce)
         if i % config.PRINT_FREQ == 0:
+            if vis is not None:
+                # function.py:94-96,185-187, enqueued behind the step: the student's last map is read where the forward left
+                # it in the arena (the update does not touch it); the drain below is the wait these launches share
+                dev = step.student.image().device
+                vis.save_debug_images(config, _on_device(inp, dev), meta, _on_device(target, dev), None,
+                                      step.student.output_view(-1).permute(0, 3, 1, 2),
+                                      '{}_{}'.format(os.path.join(output_dir, 'train'), i), writer=img_writer)
             drain()                                    # the only host sync of the loop
             batch_time.update(time.time() - end)
             speed = inp.size(0) * world_size / max(batch_time.val, 1e-9)
@@ -170,19 +215,20 @@ def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writ
 
 
 def fpd_train(config, train_loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch,
-              output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1):
-    """function.py:99-187 (same positional signature; allreduce / world_size are the data-parallel extras).  Returns the
-    epoch's average loss (the reference returns None)."""
+              output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1, rank=0):
+    """function.py:99-187 (same positional signature; allreduce / world_size / rank are the data-parallel extras: only
+    rank 0 writes DEBUG images).  Returns the epoch's average loss (the reference returns None)."""
     crit = _check_supported(optimizer, pose_criterion, kd_pose_criterion)
     return _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
-                      float(config.KD.ALPHA))['loss']
+                      float(config.KD.ALPHA), output_dir, rank)['loss']
 
 
 def train(config, train_loader, model, criterion, optimizer, epoch, output_dir, tb_log_dir, writer_dict,
-          allreduce=None, world_size=1):
+          allreduce=None, world_size=1, rank=0):
     """function.py:28-96: plain (non-distillation) training = the same fused step without a teacher graph (alpha 0)."""
     crit = _check_supported(optimizer, criterion, criterion)
-    return _run_epoch(config, train_loader, model, None, crit, optimizer, epoch, writer_dict, allreduce, world_size, 0.0)['loss']
+    return _run_epoch(config, train_loader, model, None, crit, optimizer, epoch, writer_dict, allreduce, world_size, 0.0,
+                      output_dir, rank)['loss']
 
 
 def _to_numpy(v):
@@ -199,8 +245,19 @@ def _image_of(val_dataset, row):
     return names[row]
 
 
-def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None, gather=None):
-    """function.py:189-332 with the reference's signature and return value (the dataset's perf indicator).
+def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None, gather=None, rank=0):
+    """function.py:189-332 with the reference's signature and return value (the dataset's perf indicator); see
+    _validate_body.  rank: only rank 0 writes DEBUG images (function.py:286-290), through a writer this call owns."""
+    vis, img_writer = _debug_writer(config, rank)
+    try:
+        return _validate_body(config, val_loader, val_dataset, model, criterion, output_dir, writer_dict, gather, vis, img_writer)
+    finally:
+        if img_writer is not None:
+            img_writer.close()
+
+
+def _validate_body(config, val_loader, val_dataset, model, criterion, output_dir, writer_dict, gather, vis, img_writer):
+    """The body of validate.
 
     Every batch is enqueued work only (executor.ValidateStep): the eval-mode forward, TEST.FLIP_TEST's second forward on
     the width-flipped batch, and one launch that merges the two maps, takes the arg-max with the TEST.POST_PROCESS
@@ -262,6 +319,10 @@ def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_l
                 rows.append(_to_numpy(meta['index']).astype(np.int64).reshape(-1))
             idx += shape[0]
             if i % config.PRINT_FREQ == 0:
+                if vis is not None:                          # the loader's tensor: the instance's image may hold the flipped batch
+                    vis.save_debug_images(config, _on_device(inp, dev), meta, _on_device(target, dev), None,
+                                          step.merged.permute(0, 3, 1, 2), '{}_{}'.format(os.path.join(output_dir, 'val'), i),
+                                          writer=img_writer)
                 drain()                                      # the only host sync of the loop
                 batch_time.update(time.time() - end)
                 logger.info('Test: [{0}/{1}]\t'
@@ -308,7 +369,7 @@ def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_l
     return perf_indicator
 
 
-def _validate_per_batch(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None):
+def _validate_per_batch(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None, rank=0):
     """The per-batch body `validate` had before the fused step, kept as the yardstick of tests/test_val_post_gpu.py and
     tools/validate_bench.py; nothing else calls it.
 
@@ -374,6 +435,9 @@ def _validate_per_batch(config, val_loader, val_dataset, model, criterion, outpu
             image_path.extend(meta['image'])
             idx += num_images
             if i % config.PRINT_FREQ == 0:
+                if rank == 0 and _debug_on(config):          # function.py:286-290 (this yardstick waits every batch anyway)
+                    from ..utils.vis import save_debug_images
+                    save_debug_images(config, inp, meta, target, None, output, '{}_{}'.format(os.path.join(output_dir, 'val'), i))
                 logger.info('Test: [{0}/{1}]\t'
                             'Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
                             'Loss {loss.val:.4f} ({loss.avg:.4f})\t'

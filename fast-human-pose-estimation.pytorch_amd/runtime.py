@@ -131,6 +131,30 @@ class ValPostT(C.Structure):
                 ('score', _vp), ('merged', _vp), ('all_preds', _vp), ('all_boxes', _vp), ('src', _i32 * MAX_JOINTS)]
 
 
+VIS_NCHW, VIS_NHWC = 0, 1     # include/fpd_amd.h FPD_VIS_*
+
+
+class VisMinmaxT(C.Structure):
+    _fields_ = [('n', _i64), ('x', _vp), ('out', _vp)]
+
+
+class VisMaxPredsT(C.Structure):
+    _fields_ = [('N', _i32), ('J', _i32), ('h', _i32), ('w', _i32), ('dtype', _i32), ('layout', _i32), ('hm', _vp),
+                ('preds', _vp), ('maxvals', _vp)]
+
+
+class VisJointsGridT(C.Structure):
+    _fields_ = [('N', _i32), ('H', _i32), ('W', _i32), ('J', _i32), ('nrow', _i32), ('padding', _i32), ('joints_f64', _i32),
+                ('joints_stride', _i32), ('coord_scale', _f32), ('_pad', _i32), ('canvas_bytes', _i64), ('image', _vp),
+                ('minmax', _vp), ('joints', _vp), ('vis', _vp), ('canvas', _vp)]
+
+
+class VisHeatmapGridT(C.Structure):
+    _fields_ = [('N', _i32), ('J', _i32), ('h', _i32), ('w', _i32), ('H', _i32), ('W', _i32), ('dtype', _i32), ('layout', _i32),
+                ('normalize', _i32), ('_pad', _i32), ('canvas_bytes', _i64), ('image', _vp), ('minmax', _vp), ('hm', _vp),
+                ('preds', _vp), ('table', _vp), ('canvas', _vp)]
+
+
 class TargetsT(C.Structure):
     _fields_ = [('B', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('patch', _i32), ('_pad', _i32), ('stride_x', _f64),
                 ('stride_y', _f64), ('joints', _vp), ('vis', _vp), ('g', _vp), ('target', _vp), ('weight', _vp)]
@@ -246,7 +270,9 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
             'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
-            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT}
+            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT,
+            'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
+            'fpd_vis_heatmap_grid_t': VisHeatmapGridT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -283,6 +309,10 @@ SYMBOLS = {
     'fpd_flip_merge': (C.c_int, [C.POINTER(FlipMergeT), _vp]),
     'fpd_final_preds': (C.c_int, [C.POINTER(FinalPredsT), _vp]),
     'fpd_val_post': (C.c_int, [C.POINTER(ValPostT), _vp]),
+    'fpd_vis_minmax': (C.c_int, [C.POINTER(VisMinmaxT), _vp]),
+    'fpd_vis_max_preds': (C.c_int, [C.POINTER(VisMaxPredsT), _vp]),
+    'fpd_vis_joints_grid': (C.c_int, [C.POINTER(VisJointsGridT), _vp]),
+    'fpd_vis_heatmap_grid': (C.c_int, [C.POINTER(VisHeatmapGridT), _vp]),
     'fpd_render_targets': (C.c_int, [C.POINTER(TargetsT), _vp]),
     'fpd_warp_affine': (C.c_int, [C.POINTER(WarpT), _vp]),
     'fpd_augment_params': (C.c_int, [C.POINTER(AugmentT), _vp]),

@@ -575,6 +575,78 @@ typedef struct {
 } fpd_val_post_t;
 int fpd_val_post(const fpd_val_post_t* a, fpd_stream_t stream);
 
+/* ---- debug images (lib/utils/vis.py of the reference: save_batch_image_with_joints, save_batch_heatmaps) ---- */
+/* The canvases the reference composes on the host with torchvision, cv2 and numpy, rendered on the device from the tensors
+ * of the iteration; per-pixel arithmetic in csrc/vis_math.h.  The caller owns every buffer, downloads the uint8 canvases
+ * and encodes them.  Nothing here synchronises.  Heat maps come in one of three forms:
+ *   layout FPD_VIS_NCHW, dtype FPD_F32             the loader's target
+ *   layout FPD_VIS_NHWC, dtype FPD_F32 / FPD_BF16  a merged validation map / a network's last map where it lies in the arena */
+#define FPD_VIS_NCHW 0
+#define FPD_VIS_NHWC 1
+
+/* out[0] = min, out[1] = max of n float32 values (exact: no rounding is involved; -0 counts as 0). */
+typedef struct {
+    int64_t n;
+    const float* x;
+    float* out;            /* float[2], device */
+} fpd_vis_minmax_t;
+int fpd_vis_minmax(const fpd_vis_minmax_t* a, fpd_stream_t stream);
+
+/* get_max_preds (lib/core/inference.py:18-46): per (sample, joint) the arg-max of the map (first maximum wins) as
+ * (x, y) = (idx % w, idx / w), zeroed where the maximum is <= 0, and the maximum itself. */
+typedef struct {
+    int32_t N, J, h, w;
+    int32_t dtype, layout;
+    const void* hm;
+    float* preds;          /* [N,J,2] */
+    float* maxvals;        /* [N,J] */
+} fpd_vis_max_preds_t;
+int fpd_vis_max_preds(const fpd_vis_max_preds_t* a, fpd_stream_t stream);
+
+/* save_batch_image_with_joints up to the file write: make_grid(image, nrow, padding, normalize=True) as bytes,
+ *   xmaps = min(nrow, N), ymaps = ceil(N / xmaps), canvas [(H+padding)*ymaps+padding, (W+padding)*xmaps+padding, 3],
+ *   cell k at (k / xmaps * (H+padding) + padding, k % xmaps * (W+padding) + padding), everything else 0;
+ *   N == 1: the canvas is the bare [H, W, 3] image (make_grid returns it unpadded) and the marks keep the +padding offset;
+ *   byte = trunc(clamp(((x + float32(-min)) / float32(double(max) - double(min) + 1e-5)) * 255, 0, 255)) in float32;
+ * the tensor's channels in positions 0, 1, 2.  Then for every joint with vis != 0 the pixels 1 <= dx^2 + dy^2 <= 9 around
+ *   (int(cx * (W+padding) + padding + jx * coord_scale), int(cy * (H+padding) + padding + jy * coord_scale))   (float64 sums)
+ * are set to (255, 0, 0), clipped to the canvas (a compose launch, then a scatter launch: every mark stores one value). */
+typedef struct {
+    int32_t N, H, W, J;
+    int32_t nrow, padding;
+    int32_t joints_f64;            /* joints hold float64 (1) or float32 (0) */
+    int32_t joints_stride;         /* elements per joint (>= 2): x, y first */
+    float coord_scale;
+    int32_t _pad;
+    int64_t canvas_bytes;          /* size of canvas: must be GH * GW * 3 */
+    const float* image;            /* [N,3,H,W] */
+    const float* minmax;           /* fpd_vis_minmax of the image */
+    const void* joints;            /* [N,J,joints_stride] */
+    const float* vis;              /* [N,J] */
+    uint8_t* canvas;               /* [GH,GW,3] */
+} fpd_vis_joints_grid_t;
+int fpd_vis_joints_grid(const fpd_vis_joints_grid_t* a, fpd_stream_t stream);
+
+/* save_batch_heatmaps up to the file write: canvas [N*h, (J+1)*w, 3] from image [N,3,H,W] with H == 4*h, W == 4*w.
+ *   resized = (a + b + c + d + 2) >> 2 over rows / columns 4i+1, 4i+2 of the byte image (normalize: as above; else x itself)
+ *   mark(k) = the four pixels dx^2 + dy^2 == 1 around (int(preds[n,k,0]), int(preds[n,k,1])), clipped to the tile
+ *   tile 0   = resized, (0,0,255) at the marks of all joints
+ *   tile j+1 = trunc(table[heat byte] * 0.7 + base * 0.3) in float64, base = resized with (0,0,255) at the marks of joints
+ *              0..j; then (0,0,255) at mark(j).  heat byte = trunc(clamp(float32(m) * 255, 0, 255)). */
+typedef struct {
+    int32_t N, J, h, w, H, W;
+    int32_t dtype, layout;         /* of hm */
+    int32_t normalize, _pad;
+    int64_t canvas_bytes;          /* must be N*h * (J+1)*w * 3 */
+    const float* image;            /* [N,3,H,W] */
+    const float* minmax;           /* fpd_vis_minmax of the image; may be NULL when normalize == 0 */
+    const void* hm;
+    const float* preds;            /* [N,J,2] of fpd_vis_max_preds */
+    const uint8_t* table;          /* [256,3] colour of every heat byte */
+    uint8_t* canvas;
+} fpd_vis_heatmap_grid_t;
+int fpd_vis_heatmap_grid(const fpd_vis_heatmap_grid_t* a, fpd_stream_t stream);
+
 /* ---- device data pipeline (lib/dataset/JointsDataset.py:113-198,233-289) ---- */
 /* generate_target (JointsDataset.py:233-289) for a batch: Gaussian heat-map targets + target weights from joint
  * positions in network-input pixels.  mu = int(joint / feat_stride + 0.5) in float64 (feat_stride = image/heat-map size),

@@ -182,24 +182,24 @@ def run(args, normal=False):
     # its block of the set (the reference validates on its DataParallel model, :143,244); rank 0 gathers and evaluates.
     gather = fdist.make_gather(dist) if world > 1 else None
     if tmodel is not None:
-        validate(cfg, valid_loader, valid_set, tmodel, val_criterion, out_dir, cfg.LOG_DIR, writer_dict, gather=gather)
-    validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict, gather=gather)
+        validate(cfg, valid_loader, valid_set, tmodel, val_criterion, out_dir, cfg.LOG_DIR, writer_dict, gather=gather, rank=rank)
+    validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict, gather=gather, rank=rank)
     for epoch in range(begin_epoch, cfg.TRAIN.END_EPOCH):                                     # :252-286
         t0 = time.time()
         optimizer.param_groups[0]['lr'] = multistep_lr(base_lr, cfg.TRAIN.LR_STEP, cfg.TRAIN.LR_FACTOR, epoch)   # :253
         if train_type == 'FPD':                                                               # :255-264
             loss = fpd_train(cfg, loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch, out_dir,
-                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world)
+                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank)
         else:
             loss = train(cfg, loader, model, pose_criterion, optimizer, epoch, out_dir, cfg.LOG_DIR, writer_dict,
-                         allreduce=allreduce, world_size=world)
+                         allreduce=allreduce, world_size=world, rank=rank)
         torch.cuda.synchronize()
         logger.info('=> epoch %d done in %.1fs, %.1f samples/s, last logged loss %.5f', epoch, time.time() - t0,
                     len(loader) * bs * world / max(time.time() - t0, 1e-9), loss)
         # :266-285: evaluate on the validation set (flip test etc. per cfg.TEST) on every rank, keep the best model on rank 0
         # float(): MPII's indicator is a numpy scalar, which a weights-only torch.load of the checkpoint refuses
         perf_indicator = float(validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict,
-                                        gather=gather))
+                                        gather=gather, rank=rank))
         if rank == 0:
             best_model = perf_indicator >= best_perf
             best_perf = max(best_perf, perf_indicator)

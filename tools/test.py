@@ -81,7 +81,7 @@ def main():
         valid_set = SyntheticPose(cfg, cfg.DATASET.NUM_VALID_SAMPLES, seed=1009)
         valid_loader = torch.utils.data.DataLoader(valid_set, batch_size=cfg.TEST.BATCH_SIZE_PER_GPU, num_workers=0,
                                                    sampler=range(*block_range(len(valid_set), rank, world)), pin_memory=cfg.PIN_MEMORY, collate_fn=valid_set.collate)
-    perf = validate(cfg, valid_loader, valid_set, model, criterion, out_dir, cfg.LOG_DIR, gather=gather)    # :130-132
+    perf = validate(cfg, valid_loader, valid_set, model, criterion, out_dir, cfg.LOG_DIR, gather=gather, rank=rank)    # :130-132
     if rank == 0:
         logger.info('=> validation done: perf indicator %.4f, loss %.5f, accuracy %.4f', perf, validate.last['loss'], validate.last['acc'])
     if world > 1:
