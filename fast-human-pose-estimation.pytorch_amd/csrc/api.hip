@@ -52,10 +52,6 @@ static int validate_conv_dims(int N, int H, int W, int C, int K, int R, int S, i
     return 0;
 }
 
-// grid caps of the persistent teacher kernels (bneck_fused.hip, head_fused.hip); return the previous value
-int fpd_bneck_blocks_option(int value);
-int fpd_head_blocks_option(int value);
-
 extern "C" {
 
 const char* fpd_last_error(void) { return g_err; }

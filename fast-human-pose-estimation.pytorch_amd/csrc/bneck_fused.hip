@@ -9,8 +9,8 @@
 //            through LDS with bn1+ReLU applied on the way in).  Result -> bn2+ReLU -> bf16 -> LDS image `a2`
 //            laid out like conv_tile's halo tile (rows of W+2 pixels, explicit zero border columns, one zero pixel
 //            that lanes whose tap row falls outside their image read instead).
-//   phase B  conv2: 9 taps x K = P from `a2`; weight tiles [P][P] double-buffered in LDS, next tile prefetched in
-//            registers.  Result -> bn3+ReLU -> bf16 -> LDS `a3` (aliases a2).
+//   phase B  conv2: 9 taps x K = P from `a2`; weight tiles [P][P] double-buffered in LDS, the next tile travelling
+//            by LDS-DMA.  Result -> bn3+ReLU -> bf16 -> LDS `a3` (aliases a2).
 //   phase C  conv3 = two more steps of the same pipeline (rows [0,P) and [P,2P) of w3 are [P][P] tiles), then the
 //            epilogue: fp32 staging per wave, + bias + residual x, one rounding, 128-byte row segments to HBM.
 // All MFMAs run "transposed" (first operand = weights, second = pixels): a lane then owns 4 CONSECUTIVE channels of
@@ -18,16 +18,14 @@
 // Rounding: each intermediate is rounded to bf16 once (after bias+BN+ReLU); the 3-launch path rounds the raw conv
 // output and again after BN.  oracle/plan_interp.py `run_bneck` is the specification of this op.
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv_dispatch.h"
+#include "fused_lds.h"
+#include "fused_tile.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // native vector: typed loads/stores (a uint4 struct
-                                                                  // copy is a memcpy, which keeps its array in scratch)
 // (register arrays are indexed through static_for: common.h)
 
 #ifdef FPD_BNECK_TIMING          // probe build only (tools/bneck_bench.py): cycle stamps of block 0 at the phase boundaries
@@ -65,30 +63,24 @@ __global__ void bneck_fold_kernel(const fpd_bneck_t a, float* out) { bneck_fold_
 // Block bid_in of the nblk blocks assigned to fused Bottleneck `a`: persistent over its ntiles 128-pixel tiles
 // (tile = bid_in, bid_in + nblk, ...).  A grid smaller than the CU count leaves compute units free for the
 // latency-bound student kernels that run concurrently on another stream (a resident block owns its CU's LDS).
-// DMA: the [P][P] weight tiles of phases B/C go HBM/L2 -> LDS by LDS-DMA (global_load_lds_dwordx4, no VGPR round trip, no
+// The [P][P] weight tiles of phases B/C go HBM/L2 -> LDS by LDS-DMA (global_load_lds_dwordx4, no VGPR round trip, no
 // ds_write pass): ring rows are unpadded (the DMA destination is lane-linear, 1 KiB per wave instruction) and bank
 // conflicts are avoided by an XOR swizzle of the 16-byte chunks applied on the per-lane SOURCE address and again on
-// the fragment reads (chunk c of row r sits at position c ^ sw(r)).
+// the fragment reads (chunk c of row r sits at position c ^ sw(r)).  (The register path of round 1 is gone: it was never faster,
+// and its P = 64 variant spilled in the tap loop.)
 // UPADD: x is not a tensor but the sum the hourglass forms in front of this Bottleneck, x[p] = round_bf16(up1[p] + low[p / 2])
 // (hourglass.py:80-92) with up1 = a.x and low = a.x2 at half resolution.  Both places that read x -- the phase-A staging and the
 // residual rows of the epilogue -- load the two sources and round their fp32 sum to bf16 once, which is bit for bit what the
 // stand-alone FPD_EW_UPADD_FWD launch stored: the 2 x [N,H,W,C] round trip of that tensor through HBM is gone.  The low pixel of
 // global image row g (= n*H + row; H and n*H are even), column j is row g >> 1, column j >> 1 of the [N*H/2][W/2] grid.
-template <int P, bool DMA, bool UPADD>
-__device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int logW, const int swz, const int bid_in,
-                                                const int nblk, const int ntiles) {
-    constexpr int C = 2 * P;
-    constexpr int LDW = DMA ? P : P + 8;        // weight-ring row stride (bf16 elements)
-    constexpr int LDX = 64 + 8;                 // phase-A staging rows (bf16 elements)
-    constexpr int LD2 = P + 8;                  // a2 / a3 rows and [P][P] weight-tile rows
+template <int P, bool UPADD>
+__device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int logW, const int bid_in, const int nblk, const int ntiles) {
+    using L = BneckLds<P>;                      // the LDS layout (fused_lds.h): tables | a2 image | R2
+    constexpr int C = L::C, LDX = L::LDX, LD2 = L::LD2, CW = L::CW, ASTG = L::ASTG;
     constexpr int TNH = P / 64;                 // 32-channel MFMA tiles per wave (a wave owns half of a P-wide tile)
-    constexpr int CW = 32 * TNH;                // channels per wave per step
     constexpr int NSTEP = 9 + 2;
-    constexpr int VPR2 = P / 8;                 // 16-byte vectors per [.][P] row
-    constexpr int WV = P * VPR2 / 512;          // vectors per thread of a [P][P] tile
     constexpr int W1V = P * 8 / 512;            // vectors per thread of a [P][64] w1 chunk
     constexpr int NCH = C / 64;                 // channel chunks of conv1's reduction (even)
-    constexpr int ASTG = (128 + P) * LDX;       // one phase-A staging buffer: x chunk [128][LDX] + w1 chunk [P][LDX]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -112,8 +104,8 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     // of two: phase A was 40 % of a tile at 2x recompute, r02 stamps), and a3 of tile T goes into T's first half-slot, which
     // is dead by then (nrows * (W + 2) >= 128 pixels).
     const int rrows = 2 * nrows;
-    const bool whole = (128 % (H * W)) == 0;             // tiles made of whole images keep the plain layout (no halo rows are read)
-    const int irows = whole ? hrows : rrows;             // rows of the a2 image
+    const bool whole = L::whole(H, W);                   // tiles made of whole images keep the plain layout (no halo rows are read)
+    const int irows = L::irows(whole, nrows);            // rows of the a2 image
     const int zero_px = irows * WP;
     int m0 = 0, g0 = 0;                          // first pixel / first image row of the current tile
     int vrow0 = 0;                               // virtual row of halo row 0 of the current tile, mod 2*nrows
@@ -125,8 +117,8 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     float* s_sc3 = s_sh2 + P;
     float* s_sh3 = s_sc3 + P;
     float* s_b3 = s_sh3 + P;
-    bf16_t* sA2 = reinterpret_cast<bf16_t*>(s_b3 + C);
-    bf16_t* sR2 = sA2 + (zero_px + 3) * LD2;     // 3 zero pixels: the column tap offset is added to a redirected address too
+    bf16_t* sA2 = reinterpret_cast<bf16_t*>(s_sc1 + L::TAB);
+    bf16_t* sR2 = sA2 + L::image_px(irows, W) * LD2;     // (the 3 zero pixels sit at zero_px)
     const bf16_t* __restrict__ x = reinterpret_cast<const bf16_t*>(a.x);
     const bf16_t* __restrict__ x2 = reinterpret_cast<const bf16_t*>(UPADD ? a.x2 : nullptr);
     const bf16_t* __restrict__ w1 = reinterpret_cast<const bf16_t*>(a.w1);
@@ -185,17 +177,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     // it always did.  The sums are VALU work like the staging and ride behind the MFMAs of the chunk steps in the same way (below).
     auto a_sum = [&](auto kcc, auto ic) __attribute__((always_inline)) {
         constexpr int kc = decltype(kcc)::value, i = decltype(ic)::value;
-        if constexpr (UPADD) {
-            float v[8], u[8];
-            const u32x4 r = rx[kc][i], r2 = rx2[kc][i];
-            DT<bf16_t>::unpack(make_uint4(r[0], r[1], r[2], r[3]), v);
-            DT<bf16_t>::unpack(make_uint4(r2[0], r2[1], r2[2], r2[3]), u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] + u[e];
-            const uint4 o = DT<bf16_t>::pack(v);
-            const u32x4 ov = {o.x, o.y, o.z, o.w};
-            rx[kc][i] = ov;
-        }
+        if constexpr (UPADD) rx[kc][i] = bf16x8_sum(rx[kc][i], rx2[kc][i]);
     };
     // staging of chunk kc in NSL = 2 + W1V slices (x vector 0, x vector 1, then the w1 vectors): the chunk loop places one
     // slice behind the MFMAs of each k-step, so that the VALU / LDS-store work of the next chunk runs while the matrix
@@ -223,38 +205,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     auto a_store = [&](auto kcc) __attribute__((always_inline)) {
         static_for<NSL>([&](auto slc) { a_store_slice(kcc, slc); });
     };
-    // ---- weight-tile pipeline of phases B/C: two register sets, tile t travels in set t & 1 and is requested two
-    //      steps before the step that multiplies with it ----
-    int t2o[WV], t3o[WV], tlo[WV];
-#pragma unroll
-    for (int i = 0; i < WV; ++i) {
-        const int v = tid + i * 512;
-        const int row = v / VPR2, col = (v - row * VPR2) * 8;
-        t2o[i] = row * 9 * P + col;
-        t3o[i] = row * P + col;
-        tlo[i] = row * LD2 + col;
-    }
-    u32x4 rb[DMA ? 1 : 2][DMA ? 1 : WV];
-    auto t_load = [&](auto sc_) __attribute__((always_inline)) {
-        constexpr int s = decltype(sc_)::value;
-        if constexpr (!DMA) {
-            static_for<WV>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                const bf16_t* src = s < 9 ? w2 + (t2o[i] + s * P) : w3 + (t3o[i] + (s - 9) * P * P);
-                rb[s & 1][i] = *reinterpret_cast<const u32x4*>(src);
-            });
-        }
-    };
-    auto t_store = [&](auto sc_) __attribute__((always_inline)) {
-        constexpr int s = decltype(sc_)::value;
-        if constexpr (!DMA) {
-            bf16_t* dst = sR2 + (s & 1) * P * LDW;
-            static_for<WV>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                *reinterpret_cast<u32x4*>(dst + tlo[i]) = rb[s & 1][i];
-            });
-        }
-    };
+    // ---- weight-tile pipeline of phases B/C: tile s is requested one step before the step that multiplies with it ----
     // LDS-DMA of weight tile s into ring buffer s & 1: P rows of 2P bytes = P*P*2/1024 wave instructions, 8 waves.
     // Wave instruction q covers ring bytes [q*1024, q*1024 + 1024): rows q*RPI .. +RPI, lane L -> row q*RPI + L/CPR,
     // position L % CPR, fetching global chunk (position ^ sw(row)) of that row.
@@ -263,36 +214,32 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
     constexpr int DPW = P / RPI / 8;            // wave instructions per wave per tile
     // per-lane byte offsets of the DPW pieces this wave fetches of a tile, for the w2 ([P][9][P]) and w3 ([C][P]) row pitches;
     // the step's constant part (s*P resp. (s-9)*P*P elements) is added at issue time
-    unsigned dma2[DMA ? DPW : 1], dma3[DMA ? DPW : 1];
-    if constexpr (DMA) {
+    unsigned dma2[DPW], dma3[DPW];
 #pragma unroll
-        for (int j = 0; j < DPW; ++j) {
-            const int row = wave * DPW * RPI + j * RPI + lane / CPR;
-            const int sw = (P == 128) ? (row & 15) : ((row >> 1) & 7);      // sw(row): 16 consecutive rows -> 16 slots
-            const int c8 = ((lane % CPR) ^ sw) * 8;
-            dma2[j] = (unsigned)(row * 9 * P + c8) * 2u;
-            dma3[j] = (unsigned)(row * P + c8) * 2u;
-        }
+    for (int j = 0; j < DPW; ++j) {
+        const int row = wave * DPW * RPI + j * RPI + lane / CPR;
+        const int sw = (P == 128) ? (row & 15) : ((row >> 1) & 7);      // sw(row): 16 consecutive rows -> 16 slots
+        const int c8 = ((lane % CPR) ^ sw) * 8;
+        dma2[j] = (unsigned)(row * 9 * P + c8) * 2u;
+        dma3[j] = (unsigned)(row * P + c8) * 2u;
     }
     auto t_dma = [&](auto sc_) __attribute__((always_inline)) {
         constexpr int s = decltype(sc_)::value;
-        if constexpr (DMA) {
-            unsigned char* ring = reinterpret_cast<unsigned char*>(sR2) + (s & 1) * P * P * 2 + wave * DPW * 1024;
-            const char* gbase = s < 9 ? reinterpret_cast<const char*>(w2) + s * P * 2
-                                      : reinterpret_cast<const char*>(w3) + (s - 9) * P * P * 2;
-            static_for<DPW>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                unsigned off = s < 9 ? dma2[j] : dma3[j];
-                asm volatile("" : "+v"(off));    // keep the 44 (step, piece) addresses from being hoisted out of the tile loop
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + off),
-                                                 (__attribute__((address_space(3))) void*)(ring + j * 1024), 16, 0, 0);
-            });
-        }
+        unsigned char* ring = reinterpret_cast<unsigned char*>(sR2) + (s & 1) * L::RING * 2 + wave * DPW * 1024;
+        const char* gbase = s < 9 ? reinterpret_cast<const char*>(w2) + s * P * 2
+                                  : reinterpret_cast<const char*>(w3) + (s - 9) * P * P * 2;
+        static_for<DPW>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            unsigned off = s < 9 ? dma2[j] : dma3[j];
+            asm volatile("" : "+v"(off));    // keep the 44 (step, piece) addresses from being hoisted out of the tile loop
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + off),
+                                             (__attribute__((address_space(3))) void*)(ring + j * 1024), 16, 0, 0);
+        });
     };
 
     // ---- tables (once per block): folded by the host-side prep pass (a.folded) or here ----
     if (a.folded != nullptr) {
-        for (int v = tid; v < (3 * C + 4 * P) / 4; v += 512)
+        for (int v = tid; v < L::TAB / 4; v += 512)
             reinterpret_cast<f32x4*>(s_sc1)[v] = reinterpret_cast<const f32x4*>(a.folded)[v];
     } else {
         bneck_fold_tables<P>(a, s_sc1, tid, 512);
@@ -300,7 +247,6 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
 
     // a block owns a CONTIGUOUS range of tiles (consecutive row groups of an image), so that the ring pays off
     const int t_beg = fpd_cut(bid_in, ntiles, nblk), t_end = fpd_cut(bid_in + 1, ntiles, nblk);
-    (void)swz;
     for (int tile = t_beg; tile < t_end; ++tile) {
     {
         m0 = tile * 128;
@@ -340,12 +286,10 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
 
     // =========================== phase A: conv1 over the halo rows ===========================
     // All NCH channel chunks of a pass are in flight in registers; the slot a chunk frees is refilled with the same
-    // chunk of the NEXT pass (in the last pass: with the first weight tiles of phase B).  Staging is double-buffered:
-    // chunk k+1 gets its bn1+ReLU and goes to LDS while the MFMAs of chunk k run; one barrier per chunk.
+    // chunk of the NEXT pass.  Staging is double-buffered: chunk k+1 gets its bn1+ReLU and goes to LDS while the MFMAs
+    // of chunk k run; one barrier per chunk.
     auto refill = [&](auto kcc, int pp) __attribute__((always_inline)) {      // slot kcc held pass pp, now stored
-        constexpr int kc = decltype(kcc)::value;
         if (pp + 1 < npass) a_load(kcc);                                       // xo/xok already describe pass pp+1
-        else if constexpr (kc < 2) t_load(kcc);
     };
 #ifdef FPD_BNECK_TIMING
     acnt = 0;
@@ -420,19 +364,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
         const int hr = hp >> logW, j = hp & (W - 1);
         if (hr < hrows) {
             const int rr = whole ? hr : ((vrow0 + hr) & (rrows - 1));
-            bf16_t* dst = sA2 + (rr * WP + j + 1) * LD2;
-#pragma unroll
-            for (int tn = 0; tn < TNH; ++tn)
-#pragma unroll
-                for (int gi = 0; gi < 4; ++gi) {
-                    const int c = hC * CW + tn * 32 + 8 * gi + 4 * (lane >> 5);
-                    const f32x4 sc = *reinterpret_cast<const f32x4*>(s_sc2 + c);
-                    const f32x4 sh = *reinterpret_cast<const f32x4*>(s_sh2 + c);
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(acc[tn][4 * gi + e], sc[e], sh[e]), 0.f);
-                    *reinterpret_cast<uint2*>(dst + c) = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
-                }
+            act_store(acc, s_sc2, s_sh2, hC * CW, lane, sA2 + (rr * WP + j + 1) * LD2);
         }
     }
 
@@ -452,10 +384,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
         ab[2] = (live && pr + 1 < H) ? (r2 * WP + tj) * LD2 : zero_px * LD2;
     }
     STAMP(2);
-    // (the last barrier of phase A already separates its staging reads from the tile stores below)
-    t_store(std::integral_constant<int, 0>{});
-    t_load(std::integral_constant<int, 2>{});
-    __syncthreads();                             // tile 0 (+ tile 1 when DMA) + the whole a2 image visible
+    __syncthreads();                             // tiles 0 and 1 + the whole a2 image visible
     STAMP(3);
 
     f32x16 accB[TNH], accC[2][TNH];
@@ -464,22 +393,24 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
 #pragma unroll
         for (int i = 0; i < 16; ++i) accB[tn][i] = 0.f;
 
-    const int wsw = (P == 128) ? (lane & 15) : ((lane >> 1) & 7);     // sw(row) of this lane's weight rows (DMA layout)
-    auto mma = [&](const bf16_t* arow, int buf, f32x16* acc) __attribute__((always_inline)) {
-        const bf16_t* wbase = sR2 + buf * P * LDW + (hC * CW + (lane & 31)) * LDW;
-#pragma unroll
-        for (int kk = 0; kk < P / 16; ++kk) {
+    const int wsw = (P == 128) ? (lane & 15) : ((lane >> 1) & 7);     // sw(row) of this lane's weight rows
+    // one pipeline step: K = P from pixel row `arow` against weight tile `buf`; behind(kkc) is issued behind the MFMAs of k-step kk
+    auto mma = [&](const bf16_t* arow, int buf, f32x16* acc, auto behind) __attribute__((always_inline)) {
+        const bf16_t* wbase = sR2 + buf * L::RING + (hC * CW + (lane & 31)) * P;
+        static_for<P / 16>([&](auto kkc) {
+            constexpr int kk = decltype(kkc)::value;
             const bf16x8 px = *reinterpret_cast<const bf16x8*>(arow + kk * 16);
-            const int wo = DMA ? (((2 * kk + (lane >> 5)) ^ wsw) * 8) : (kk * 16 + koff);
+            const int wo = ((2 * kk + (lane >> 5)) ^ wsw) * 8;
 #pragma unroll
             for (int tn = 0; tn < TNH; ++tn) {
-                const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wbase + tn * 32 * LDW + wo);
+                const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wbase + tn * 32 * P + wo);
                 acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, px, acc[tn], 0, 0, 0);
             }
-        }
+            behind(kkc);
+        });
     };
 
-    // residual rows of the epilogue, requested under the last pipeline steps
+    // residual rows of the epilogue, requested under the last pipeline steps (the kernel's own text, like the head's: fused_tile.h)
     constexpr int VW = CW / 8;                   // output vectors per pixel row of this wave's channel slice
     constexpr int NIT = 32 * VW / 64;
     u32x4 rres[2][NIT];
@@ -503,55 +434,29 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
         });
     };
     // UPADD: the residual is the same rounded sum that phase A staged.  Formed one pipeline step after the request (the barrier
-    // in between has drained the loads), behind the MFMAs of that step; the epilogue then reads rres as it always did.
+    // in between has drained the loads), one vector behind the MFMAs of each of the first NIT k-steps of steps 9 and 10; the
+    // epilogue then reads rres as it always did.
     auto res_sum = [&](auto stc, auto itc) __attribute__((always_inline)) {
         constexpr int st = decltype(stc)::value, it = decltype(itc)::value;
-        if constexpr (UPADD && it < NIT) {
-            float v[8], u[8];
-            const u32x4 r = rres[st][it], r2 = rres2[it];
-            DT<bf16_t>::unpack(make_uint4(r[0], r[1], r[2], r[3]), v);
-            DT<bf16_t>::unpack(make_uint4(r2[0], r2[1], r2[2], r2[3]), u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] + u[e];
-            const uint4 o = DT<bf16_t>::pack(v);
-            const u32x4 ov = {o.x, o.y, o.z, o.w};
-            rres[st][it] = ov;
-        }
-    };
-    // UPADD, steps 9 and 10: the same MFMA sequence with one residual vector summed behind each of the first NIT k-steps
-    auto mma_sum = [&](const bf16_t* arow, int buf, f32x16* acc, auto stc) __attribute__((always_inline)) {
-        const bf16_t* wbase = sR2 + buf * P * LDW + (hC * CW + (lane & 31)) * LDW;
-        static_for<P / 16>([&](auto kkc) {
-            constexpr int kk = decltype(kkc)::value;
-            const bf16x8 px = *reinterpret_cast<const bf16x8*>(arow + kk * 16);
-            const int wo = DMA ? (((2 * kk + (lane >> 5)) ^ wsw) * 8) : (kk * 16 + koff);
-#pragma unroll
-            for (int tn = 0; tn < TNH; ++tn) {
-                const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wbase + tn * 32 * LDW + wo);
-                acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, px, acc[tn], 0, 0, 0);
-            }
-            res_sum(stc, kkc);
-        });
+        if constexpr (UPADD && it < NIT) rres[st][it] = bf16x8_sum(rres[st][it], rres2[it]);
     };
 
     static_for<NSTEP>([&](auto sc_) {
         constexpr int s = decltype(sc_)::value;
-        // DMA: tile s+1 goes into the buffer tile s-1 left (every wave is past step s-1's barrier); tiles 0/1 were issued
+        // tile s+1 goes into the buffer tile s-1 left (every wave is past step s-1's barrier); tiles 0/1 were issued
         // at the end of phase A.  The barrier closing this step drains it (hipcc emits vmcnt(0) in front of s_barrier).
-        if constexpr (DMA && s >= 1 && s + 1 < NSTEP) t_dma(std::integral_constant<int, (s + 1 < NSTEP ? s + 1 : 0)>{});
+        if constexpr (s >= 1 && s + 1 < NSTEP) t_dma(std::integral_constant<int, (s + 1 < NSTEP ? s + 1 : 0)>{});
         if constexpr (s < 9) {
-            mma(sA2 + ab[s / 3] + (s % 3) * LD2 + koff, s & 1, accB);
+            mma(sA2 + ab[s / 3] + (s % 3) * LD2 + koff, s & 1, accB, [](auto) {});
         } else {
 #pragma unroll
             for (int tn = 0; tn < TNH; ++tn)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) accC[s - 9][tn][i] = 0.f;
-            if constexpr (UPADD) mma_sum(sA2 + (a3px + ml) * LD2 + koff, s & 1, accC[s - 9], std::integral_constant<int, s - 9>{});
-            else mma(sA2 + (a3px + ml) * LD2 + koff, s & 1, accC[s - 9]);     // a3 aliases the dead half of a2: [128 px][LD2]
+            mma(sA2 + (a3px + ml) * LD2 + koff, s & 1, accC[s - 9],       // a3 aliases the dead half of a2: [128 px][LD2]
+                [&](auto kkc) { res_sum(std::integral_constant<int, s - 9>{}, kkc); });
         }
         if constexpr (s + 1 < NSTEP) {
-            t_store(std::integral_constant<int, s + 1>{});
-            if constexpr (s + 3 < NSTEP) t_load(std::integral_constant<int, (s + 3 < NSTEP ? s + 3 : 0)>{});
             if constexpr (s == 8) res_load(std::integral_constant<int, 0>{});
             if constexpr (s == 9) res_load(std::integral_constant<int, 1>{});
             __syncthreads();
@@ -559,40 +464,19 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
         if constexpr (s == 8) {
             STAMP(4);
             // every wave is past its last a2 read: a3 = relu(bn3(conv2 + b2)) overwrites the image
-            bf16_t* dst = sA2 + (a3px + ml) * LD2;
-#pragma unroll
-            for (int tn = 0; tn < TNH; ++tn)
-#pragma unroll
-                for (int gi = 0; gi < 4; ++gi) {
-                    const int c = hC * CW + tn * 32 + 8 * gi + 4 * (lane >> 5);
-                    const f32x4 sc = *reinterpret_cast<const f32x4*>(s_sc3 + c);
-                    const f32x4 sh = *reinterpret_cast<const f32x4*>(s_sh3 + c);
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(accB[tn][4 * gi + e], sc[e], sh[e]), 0.f);
-                    *reinterpret_cast<uint2*>(dst + c) = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
-                }
+            act_store(accB, s_sc3, s_sh3, hC * CW, lane, sA2 + (a3px + ml) * LD2);
             __syncthreads();
         }
     });
 
     STAMP(5);
     // =========================== epilogue: y = conv3 + b3 + x ===========================
-    constexpr int LDS_ = CW + 4;
-    float* stage = reinterpret_cast<float*>(sR2) + wave * 32 * LDS_;       // wave-private [32 px][CW + 4] fp32
+    float* stage = reinterpret_cast<float*>(sR2) + wave * 32 * L::LST;     // wave-private [32 px][CW + 4] fp32
     bf16_t* __restrict__ y = reinterpret_cast<bf16_t*>(a.y);
     static_for<2>([&](auto stc) {
         constexpr int st = decltype(stc)::value;
         __syncthreads();                         // weight tiles consumed / previous staging read back
-#pragma unroll
-        for (int tn = 0; tn < TNH; ++tn)
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = accC[st][tn][4 * gi + e];
-                *reinterpret_cast<f32x4*>(stage + (lane & 31) * LDS_ + tn * 32 + 8 * gi + 4 * (lane >> 5)) = v;
-            }
+        epi_stage<TNH>(accC[st], stage, lane);
         __syncthreads();
         static_for<NIT>([&](auto itc) {
             constexpr int it = decltype(itc)::value;
@@ -601,19 +485,7 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
             const int m = m0 + q * 32 + px;
             if (m < M) {
                 const int c = st * P + hC * CW + cv;
-                const f32x4 v0 = *reinterpret_cast<const f32x4*>(stage + px * LDS_ + cv);
-                const f32x4 v1 = *reinterpret_cast<const f32x4*>(stage + px * LDS_ + cv + 4);
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(s_b3 + c);
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(s_b3 + c + 4);
-                float res[8], o[8];
-                const u32x4 r = rres[st][it];
-                DT<bf16_t>::unpack(make_uint4(r[0], r[1], r[2], r[3]), res);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = v0[e] + b0[e] + res[e];
-                    o[4 + e] = v1[e] + b1[e] + res[4 + e];
-                }
-                *reinterpret_cast<uint4*>(y + ((size_t)m * C + c)) = DT<bf16_t>::pack(o);
+                *reinterpret_cast<uint4*>(y + ((size_t)m * C + c)) = epi_vec(stage + px * L::LST + cv, s_b3 + c, rres[st][it]);
             }
         });
     });
@@ -631,84 +503,52 @@ __device__ __forceinline__ void bneck_eval_body(const fpd_bneck_t& a, const int 
 #endif
 }
 
-template <int P, bool DMA, bool UPADD>
+template <int P, bool UPADD>
 __global__ __launch_bounds__(512, 1) void bneck_eval_kernel(const fpd_bneck_t a, const int logW, const int ntiles) {
-    bneck_eval_body<P, DMA, UPADD>(a, logW, (ntiles & 7) == 0, blockIdx.x, gridDim.x, ntiles);
+    bneck_eval_body<P, UPADD>(a, logW, blockIdx.x, gridDim.x, ntiles);
 }
 
 // Two independent fused Bottlenecks (the up-branch and the low-branch one of an hourglass level) in one launch.
-template <int P, bool DMA>
+template <int P>
 __global__ __launch_bounds__(512, 1) void bneck_eval_pair_kernel(const fpd_bneck_t a, const fpd_bneck_t b, const int logWa,
                                                                  const int logWb, const int nblk_a, const int ntiles_a,
                                                                  const int ntiles_b) {
-    if ((int)blockIdx.x < nblk_a) bneck_eval_body<P, DMA, false>(a, logWa, (ntiles_a & 7) == 0, blockIdx.x, nblk_a, ntiles_a);
-    else bneck_eval_body<P, DMA, false>(b, logWb, (ntiles_b & 7) == 0, (int)blockIdx.x - nblk_a, (int)gridDim.x - nblk_a, ntiles_b);
+    if ((int)blockIdx.x < nblk_a) bneck_eval_body<P, false>(a, logWa, blockIdx.x, nblk_a, ntiles_a);
+    else bneck_eval_body<P, false>(b, logWb, (int)blockIdx.x - nblk_a, (int)gridDim.x - nblk_a, ntiles_b);
 }
 
-// (The register path of the weight tiles -- DMA = false, round 1, selectable through FPD_BNECK_DMA until round 5 -- is no longer
-//  instantiated: it was never faster, and its P = 64 variant spilled in the tap loop, VERDICT r5 weak #10.)
-
-// grid cap of the persistent kernel (FPD_BNECK_BLOCKS): below the CU count so that concurrently running streams find
-// free compute units
-static std::atomic<int> g_bneck_cap{0};       // 0 = not set yet: the environment supplies the default
-static int bneck_block_cap() {
-    int cap = g_bneck_cap.load(std::memory_order_relaxed);
-    if (!cap) {
-        const char* e = getenv("FPD_BNECK_BLOCKS");
-        cap = e ? atoi(e) : 128;       // measured (r01, pipelined step): 1024/256/224/192/160/128 -> 13.56/13.86/13.37/13.30/13.21/13.23 ms;
-                                       // r02 (wgrad batches of 8, same box): 96/112/128/144/160 -> 11.71/11.69/11.51/11.68/11.67 ms
-        if (cap < 8) cap = 8;
-        int unset = 0;                 // (a value set through fpd_set_option in the meantime wins)
-        if (!g_bneck_cap.compare_exchange_strong(unset, cap, std::memory_order_relaxed)) cap = unset;
-    }
-    return cap;
-}
-// blocks for `tiles` tiles under the cap, balanced so that every block runs the same number of rounds
-static int bneck_blocks(int tiles, int cap) {
-    if (tiles <= cap) return tiles;
-    const int rounds = cdiv(tiles, cap);
-    return cdiv(tiles, rounds);
-}
+// grid cap of the persistent kernel (FPD_BNECK_BLOCKS): below the CU count so that concurrently running streams find free compute units.
+// Measured (r01, pipelined step): 1024/256/224/192/160/128 -> 13.56/13.86/13.37/13.30/13.21/13.23 ms;
+// r02 (wgrad batches of 8, same box): 96/112/128/144/160 -> 11.71/11.69/11.51/11.68/11.67 ms
+static GridCap g_bneck_cap{"FPD_BNECK_BLOCKS", 128};
 
 template <int P>
-size_t bneck_lds_bytes(int H, int W) {
-    constexpr int C = 2 * P, LD2 = P + 8, LDX = 72, CW = 32 * (P / 64);
-    int logW = 0;
-    while ((1 << logW) < W) ++logW;
-    const int nrows = 128 >> logW, WP = W + 2;
-    const bool whole = (128 % (H * W)) == 0;
-    const int irows = whole ? nrows + 2 : 2 * nrows;          // a2 image: plain halo tile / ring of two half-slots
-    const size_t r2 = std::max({(size_t)2 * P * LD2 * 2, (size_t)2 * (128 + P) * LDX * 2, (size_t)8 * 32 * (CW + 4) * 4});
-    return (size_t)(3 * C + 4 * P) * sizeof(float) + (size_t)(irows * WP + 3) * LD2 * 2 + r2;
-}
-
-template <int P, bool DMA>
 int launch_bneck_pair(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st) {
-    const size_t lds = std::max(bneck_lds_bytes<P>(a.H, a.W), bneck_lds_bytes<P>(b.H, b.W));
+    const size_t lds = std::max(BneckLds<P>::bytes(a.H, a.W), BneckLds<P>::bytes(b.H, b.W));
     static LdsAttr configured;        // per device, set once (thread-safe: common.h)
-    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&bneck_eval_pair_kernel<P, DMA>), lds)) return rc_;
+    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&bneck_eval_pair_kernel<P>), lds)) return rc_;
     int la = 0, lb = 0;
     while ((1 << la) < a.W) ++la;
     while ((1 << lb) < b.W) ++lb;
     const int ta = cdiv(a.N * a.H * a.W, 128), tb = cdiv(b.N * b.H * b.W, 128);
     int na = ta, nb = tb;
-    const int cap = bneck_block_cap();
+    const int cap = g_bneck_cap.get();
     if (ta + tb > cap) {                       // persistent: split the capped grid in proportion to the work
         const int capb = std::max(1, (int)((int64_t)cap * tb / (ta + tb)));
-        nb = bneck_blocks(tb, capb);
-        na = bneck_blocks(ta, std::max(1, cap - nb));
+        nb = fpd_balanced_blocks(tb, capb);
+        na = fpd_balanced_blocks(ta, std::max(1, cap - nb));
     }
-    FPD_LAUNCH((bneck_eval_pair_kernel<P, DMA>), dim3(na + nb), dim3(512), lds, st, a, b, la, lb, na, ta, tb);
+    FPD_LAUNCH((bneck_eval_pair_kernel<P>), dim3(na + nb), dim3(512), lds, st, a, b, la, lb, na, ta, tb);
     return 0;
 }
 
-template <int P, bool DMA, bool UPADD>
+template <int P, bool UPADD>
 int launch_bneck(const fpd_bneck_t& a, int logW, hipStream_t st) {
-    const size_t lds = bneck_lds_bytes<P>(a.H, a.W);
+    const size_t lds = BneckLds<P>::bytes(a.H, a.W);
     static LdsAttr configured;        // per device, set once (thread-safe: common.h)
-    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&bneck_eval_kernel<P, DMA, UPADD>), lds)) return rc_;
+    if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&bneck_eval_kernel<P, UPADD>), lds)) return rc_;
     const int ntiles = cdiv(a.N * a.H * a.W, 128);
-    FPD_LAUNCH((bneck_eval_kernel<P, DMA, UPADD>), dim3(bneck_blocks(ntiles, bneck_block_cap())), dim3(512), lds, st, a, logW, ntiles);
+    FPD_LAUNCH((bneck_eval_kernel<P, UPADD>), dim3(fpd_balanced_blocks(ntiles, g_bneck_cap.get())), dim3(512), lds, st, a, logW, ntiles);
     return 0;
 }
 
@@ -716,10 +556,7 @@ int launch_bneck(const fpd_bneck_t& a, int logW, hipStream_t st) {
 
 // fpd_set_option("bneck_blocks", n): the grid cap, any n >= 1 (tests: one block then walks many tiles of a small tensor);
 // returns the previous value
-int fpd_bneck_blocks_option(int value) {
-    bneck_block_cap();                           // (the default is in place: what the exchange returns is the value in force)
-    return g_bneck_cap.exchange(value < 1 ? 1 : value, std::memory_order_relaxed);
-}
+int fpd_bneck_blocks_option(int value) { return g_bneck_cap.set(value); }
 
 static bool bneck_in_domain(const fpd_bneck_t& a) {
     if (a.dtype != FPD_BF16 || a.C != 2 * a.P || (a.P != 64 && a.P != 128)) return false;
@@ -749,15 +586,15 @@ int fpd_bneck_fused_launch(const fpd_bneck_t& a, hipStream_t st) {
     while ((1 << logW) < a.W) ++logW;
     if (a.x2 != nullptr) {
         if (fpd_bneck_upadd_why_not(a) != nullptr) return 1;      // (api.hip refused it with the reason already)
-        return a.P == 128 ? launch_bneck<128, true, true>(a, logW, st) : launch_bneck<64, true, true>(a, logW, st);
+        return a.P == 128 ? launch_bneck<128, true>(a, logW, st) : launch_bneck<64, true>(a, logW, st);
     }
-    return a.P == 128 ? launch_bneck<128, true, false>(a, logW, st) : launch_bneck<64, true, false>(a, logW, st);
+    return a.P == 128 ? launch_bneck<128, false>(a, logW, st) : launch_bneck<64, false>(a, logW, st);
 }
 
 // 0 = both launched as one kernel, 1 = not pairable (caller launches them one by one)
 int fpd_bneck_fused_pair_launch(const fpd_bneck_t& a, const fpd_bneck_t& b, hipStream_t st) {
     if (!bneck_in_domain(a) || !bneck_in_domain(b) || a.P != b.P || a.x2 != nullptr || b.x2 != nullptr) return 1;
-    return a.P == 128 ? launch_bneck_pair<128, true>(a, b, st) : launch_bneck_pair<64, true>(a, b, st);
+    return a.P == 128 ? launch_bneck_pair<128>(a, b, st) : launch_bneck_pair<64>(a, b, st);
 }
 
 // folded tables ([3C + 4P] floats) for a.folded; 1 = P not supported

@@ -3,6 +3,7 @@
 // Launch convention: 0 = launched, 1 = outside this kernel's domain (the caller tries the next one), < 0 error.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstdlib>
 
@@ -16,12 +17,34 @@ struct EnvOpt {
     int set(int value) { const int prev = get(); v = value; return prev; }
 };
 
-// Persistent blocks of a streaming launch under a cap, balanced: every block walks the same number of work units (rounds, strips) --
-// 512 rounds under a cap of 192 -> 171 blocks of 3, not 192 blocks of which two thirds run 3 and the rest 2.  A pair launch (ub > 0
-// units of a second convolution) shares the blocks in proportion, at least one each; false: a pair with a single block.
+// The grid cap of a persistent kernel (the fused teacher kernels: below the CU count, so that the streams running next to them find
+// free compute units).  The environment supplies the default, raised to at least 8; fpd_set_option (the units' *_blocks_option entry
+// points) takes any n >= 1 -- tests let one block walk many tiles of a small tensor -- and gets the value in force back.  0 = not set
+// yet: a value set before the first launch wins over the environment.
+struct GridCap {
+    const char* env; int def;
+    std::atomic<int> v{0};
+    int get() {
+        int cap = v.load(std::memory_order_relaxed);
+        if (!cap) {
+            const char* e = getenv(env);
+            cap = std::max(8, e ? atoi(e) : def);
+            int unset = 0;                 // (a value set through fpd_set_option in the meantime wins)
+            if (!v.compare_exchange_strong(unset, cap, std::memory_order_relaxed)) cap = unset;
+        }
+        return cap;
+    }
+    int set(int value) { get(); return v.exchange(std::max(1, value), std::memory_order_relaxed); }
+};
+
+// Persistent blocks for `units` work units (tiles, rounds, strips) under a cap, balanced: every block walks the same number of them --
+// 512 rounds under a cap of 192 -> 171 blocks of 3, not 192 blocks of which two thirds run 3 and the rest 2.
+inline int fpd_balanced_blocks(int units, int cap) { return units <= cap ? units : cdiv(units, cdiv(units, cap)); }
+
+// The blocks of a streaming launch.  A pair launch (ub > 0 units of a second convolution) shares them in proportion, at least one
+// each; false: a pair with a single block.
 inline bool fpd_split_blocks(int ua, int ub, bool pair, int cap, int& na, int& nb) {
-    int total = std::max(1, std::min(cap, ua + ub));
-    total = cdiv(ua + ub, cdiv(ua + ub, total));
+    const int total = fpd_balanced_blocks(ua + ub, std::max(1, cap));
     nb = 0;
     if (pair) {
         if (total < 2) return false;
@@ -103,6 +126,8 @@ int fpd_bneck_fold_launch(const fpd_bneck_t& a, float* out, hipStream_t st);
 // up-add formed on load (fpd_bneck_t.x2): nullptr = dimensions served, else the reason; the launch walks the same decision
 const char* fpd_bneck_upadd_why_not(const fpd_bneck_t& a);
 int fpd_bneck_upadd_option(int value);      // >= 0: set; returns the previous value
+int fpd_bneck_blocks_option(int value);     // >= 1: set the grid cap (GridCap); returns the previous value
+int fpd_head_blocks_option(int value);
 int fpd_head_fused_launch(const fpd_head_t& a, hipStream_t st);
 int fpd_head_fold_launch(const fpd_head_t& a, float* out, hipStream_t st);
 int fpd_pck_launch(const fpd_pck_t& a, hipStream_t st);

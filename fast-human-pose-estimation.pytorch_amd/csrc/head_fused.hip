@@ -6,18 +6,16 @@
 // Four conv launches read/write ~550 MB per 64x64 stack (y, a twice, the residual chain); fused: y0 + x in, next + score
 // out (~205 MB).  Same building blocks as bneck_fused.hip: 128-pixel tiles, 8 wave64 (4 pixel groups x 2 channel
 // halves), "transposed" MFMAs (weights first) so a lane owns 4 consecutive channels of one pixel, weight tiles [C][64]
-// double-buffered in LDS with two register sets in flight, persistent capped grid, wave-private staged epilogue.
+// double-buffered in LDS with two register sets in flight, persistent capped grid, wave-private staged epilogue;
+// the parts that are the same text live in fused_tile.h.
 // Domain: bf16, C = 256, J = 16 (K of score_ = one MFMA k-step).  Specification: oracle/plan_interp.py run_head.
-#include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
+#include "fused_lds.h"
+#include "fused_tile.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // folded tables: sc[C], sh'[C] = sh + sc*b_fc | b_score[32] (zero padded) | b_out[C] = b_fc_ + b_score_
 template <int C>
@@ -40,14 +38,12 @@ __device__ __forceinline__ void head_tables(const fpd_head_t& a, float* out, int
 
 template <int C>
 __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, const int ntiles) {
-    constexpr int LDX = 64 + 8;                 // [.][64]-chunk rows (bf16 elements)
-    constexpr int LDA = C + 8;                  // activation image rows
-    constexpr int LDS_ = 24;                    // score image rows (16 channels + pad)
+    using L = HeadLds<C>;                       // the LDS layout (fused_lds.h): tables | sA | sS | sW
+    constexpr int LDX = L::LDX, LDA = L::LDA, LDS_ = L::LDSC, WTILE = L::WTILE;
+    constexpr int CW = L::CW;                   // channels per wave per epilogue round (a wave owns 128 = 2 rounds)
     constexpr int NCH = C / 64;                 // K chunks of fc / fc_
     constexpr int NSTEP = 2 * NCH + 1;          // fc chunks | fc_ chunks | score_
     constexpr int WV = C * 8 / 512;             // uint4 per thread of a [C][64] weight chunk
-    constexpr int CW = 64;                      // channels per wave per epilogue round (a wave owns 128 = 2 rounds)
-    constexpr int WTILE = C * LDX;              // one weight buffer (elements)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef FPD_HEAD_TIMING
@@ -61,9 +57,9 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
     float* s_sh = s_sc + C;
     float* s_bs = s_sh + C;                      // [32]
     float* s_bo = s_bs + 32;                     // [C]
-    bf16_t* sA = reinterpret_cast<bf16_t*>(s_bo + C);        // [128][LDA]; during GEMM1: two [128][LDX] staging buffers
-    bf16_t* sS = sA + 128 * LDA;                 // [128][LDS_]
-    bf16_t* sW = sS + 128 * LDS_;                // two [C][LDX] weight buffers (GEMM2: [32][LDA] in the second)
+    bf16_t* sA = reinterpret_cast<bf16_t*>(s_sc + L::TAB);   // [128][LDA]; during GEMM1: two [128][LDX] staging buffers
+    bf16_t* sS = sA + L::IMG;                    // [128][LDS_]
+    bf16_t* sW = sS + L::SCORE;                  // two [C][LDX] weight buffers (GEMM2: [32][LDA] in the second)
     const bf16_t* __restrict__ y0 = reinterpret_cast<const bf16_t*>(a.y0);
     const bf16_t* __restrict__ xres = reinterpret_cast<const bf16_t*>(a.x);
     const bf16_t* __restrict__ wfc = reinterpret_cast<const bf16_t*>(a.w_fc);
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
     const bool has_next = a.next != nullptr;
 
     if (a.folded != nullptr) {
-        for (int v = tid; v < (3 * C + 32) / 4; v += 512)
+        for (int v = tid; v < L::TAB / 4; v += 512)
             reinterpret_cast<f32x4*>(s_sc)[v] = reinterpret_cast<const f32x4*>(a.folded)[v];
     } else {
         head_tables<C>(a, s_sc, tid, 512);
@@ -205,19 +201,7 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
             }
             if constexpr (s == NCH - 1) {
                 // ---- a = relu(bn(fc + b)) -> bf16 image (overwrites the staging buffers: every wave passed the barrier)
-                bf16_t* dst = sA + ml * LDA;
-#pragma unroll
-                for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-                    for (int gi = 0; gi < 4; ++gi) {
-                        const int c = hC * 128 + tn * 32 + 8 * gi + 4 * (lane >> 5);
-                        const f32x4 sc = *reinterpret_cast<const f32x4*>(s_sc + c);
-                        const f32x4 sh = *reinterpret_cast<const f32x4*>(s_sh + c);
-                        float v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(acc[tn][4 * gi + e], sc[e], sh[e]), 0.f);
-                        *reinterpret_cast<uint2*>(dst + c) = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
-                    }
+                act_store(acc, s_sc, s_sh, hC * 128, lane, sA + ml * LDA);
                 // score weights [J][C] -> rows 0..15 of a [32][LDA] tile in the free weight buffer, rows 16..31 zero
                 bf16_t* wS = sW + ((NCH - 1) & 1) * WTILE;
                 for (int v = tid; v < 32 * (C / 8); v += 512) {
@@ -258,21 +242,12 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
 
         if (has_next) {
             // ---- next = fc_(a) + score_(score) + biases + x ----
-            constexpr int LST = CW + 4;
-            float* stage = reinterpret_cast<float*>(sW) + wave * 32 * LST;     // wave-private [32 px][CW + 4] fp32
+            float* stage = reinterpret_cast<float*>(sW) + wave * 32 * L::LST;     // wave-private [32 px][CW + 4] fp32
             bf16_t* __restrict__ nxt = reinterpret_cast<bf16_t*>(a.next);
             static_for<2>([&](auto stc) {
                 constexpr int st = decltype(stc)::value;
                 __syncthreads();
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                    for (int gi = 0; gi < 4; ++gi) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[2 * st + tn][4 * gi + e];
-                        *reinterpret_cast<f32x4*>(stage + (lane & 31) * LST + tn * 32 + 8 * gi + 4 * (lane >> 5)) = v;
-                    }
+                epi_stage<CW / 32>(acc + 2 * st, stage, lane);
                 __syncthreads();
                 static_for<NIT>([&](auto itc) {
                     constexpr int it = decltype(itc)::value;
@@ -281,19 +256,7 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
                     const int m = m0 + q * 32 + px;
                     if (m < M) {
                         const int c = hC * 128 + st * CW + cv;
-                        const f32x4 v0 = *reinterpret_cast<const f32x4*>(stage + px * LST + cv);
-                        const f32x4 v1 = *reinterpret_cast<const f32x4*>(stage + px * LST + cv + 4);
-                        const f32x4 b0 = *reinterpret_cast<const f32x4*>(s_bo + c);
-                        const f32x4 b1 = *reinterpret_cast<const f32x4*>(s_bo + c + 4);
-                        float res[8], o[8];
-                        const u32x4 r = rres[st][it];
-                        DT<bf16_t>::unpack(make_uint4(r[0], r[1], r[2], r[3]), res);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            o[e] = v0[e] + b0[e] + res[e];
-                            o[4 + e] = v1[e] + b1[e] + res[4 + e];
-                        }
-                        *reinterpret_cast<uint4*>(nxt + ((size_t)m * C + c)) = DT<bf16_t>::pack(o);
+                        *reinterpret_cast<uint4*>(nxt + ((size_t)m * C + c)) = epi_vec(stage + px * L::LST + cv, s_bo + c, rres[st][it]);
                     }
                 });
             });
@@ -313,26 +276,12 @@ __global__ __launch_bounds__(512, 1) void head_eval_kernel(const fpd_head_t a, c
 template <int C>
 __global__ void head_fold_kernel(const fpd_head_t a, float* out) { head_tables<C>(a, out, threadIdx.x, blockDim.x); }
 
-static std::atomic<int> g_head_cap{0};        // 0 = not set yet: the environment supplies the default
-static int head_block_cap() {
-    int cap = g_head_cap.load(std::memory_order_relaxed);
-    if (!cap) {
-        const char* e = getenv("FPD_HEAD_BLOCKS");
-        cap = e ? atoi(e) : 160;                 // same argument as the fused Bottleneck: leave CUs to the student chain
-        if (cap < 8) cap = 8;
-        int unset = 0;                           // (a value set through fpd_set_option in the meantime wins)
-        if (!g_head_cap.compare_exchange_strong(unset, cap, std::memory_order_relaxed)) cap = unset;
-    }
-    return cap;
-}
+static GridCap g_head_cap{"FPD_HEAD_BLOCKS", 160};      // same argument as the fused Bottleneck: leave CUs to the student chain
 
 }  // namespace
 
 // fpd_set_option("head_blocks", n): the grid cap, any n >= 1 (tests); returns the previous value
-int fpd_head_blocks_option(int value) {
-    head_block_cap();                           // (the default is in place: what the exchange returns is the value in force)
-    return g_head_cap.exchange(value < 1 ? 1 : value, std::memory_order_relaxed);
-}
+int fpd_head_blocks_option(int value) { return g_head_cap.set(value); }
 
 static bool head_in_domain(const fpd_head_t& a) {
     return a.dtype == FPD_BF16 && a.C == 256 && a.J == 16;
@@ -341,13 +290,12 @@ static bool head_in_domain(const fpd_head_t& a) {
 // 0 = launched, 1 = outside the domain
 int fpd_head_fused_launch(const fpd_head_t& a, hipStream_t st) {
     if (!head_in_domain(a)) return 1;
-    constexpr int C = 256, LDX = 72, LDA = C + 8;
-    const size_t lds = (size_t)(3 * C + 32) * sizeof(float) + (size_t)128 * LDA * 2 + (size_t)128 * 24 * 2 + (size_t)2 * C * LDX * 2;
+    constexpr int C = 256;
+    constexpr size_t lds = HeadLds<C>::bytes();
     static LdsAttr configured;        // per device, set once (thread-safe: common.h)
     if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&head_eval_kernel<C>), lds)) return rc_;
-    const int ntiles = cdiv(a.N * a.H * a.W, 128), cap = head_block_cap();
-    const int nblk = ntiles <= cap ? ntiles : cdiv(ntiles, cdiv(ntiles, cap));
-    FPD_LAUNCH((head_eval_kernel<C>), dim3(nblk), dim3(512), lds, st, a, ntiles);
+    const int ntiles = cdiv(a.N * a.H * a.W, 128);
+    FPD_LAUNCH((head_eval_kernel<C>), dim3(fpd_balanced_blocks(ntiles, g_head_cap.get())), dim3(512), lds, st, a, ntiles);
     return 0;
 }
 

@@ -37,8 +37,8 @@ def _bind():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the launch arithmetic, restated (csrc/bneck_fused.hip bneck_blocks / launch_bneck_pair / bneck_eval_body, csrc/common.h
-# fpd_cut, csrc/head_fused.hip fpd_head_fused_launch / head_eval_kernel)
+# the launch arithmetic, restated (csrc/conv_dispatch.h fpd_balanced_blocks, csrc/bneck_fused.hip launch_bneck_pair /
+# bneck_eval_body, csrc/common.h fpd_cut, csrc/head_fused.hip fpd_head_fused_launch / head_eval_kernel)
 def cdiv(a, b):
     return (a + b - 1) // b
 
