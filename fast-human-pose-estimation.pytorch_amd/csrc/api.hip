@@ -92,7 +92,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_bn_t); SZ(fpd_conv_t); SZ(fpd_wgrad_t); SZ(fpd_stem_t); SZ(fpd_ew_t); SZ(fpd_loss_t); SZ(fpd_adam_t);
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
-    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t);
+    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t); SZ(fpd_loss_kl_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
     SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t);
     SZ(fpd_vis_minmax_t); SZ(fpd_vis_max_preds_t); SZ(fpd_vis_joints_grid_t); SZ(fpd_vis_heatmap_grid_t);
@@ -678,6 +678,33 @@ int fpd_loss_ohkm(const fpd_loss_ohkm_t* k, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+int64_t fpd_loss_kl_scratch_bytes(const fpd_loss_t* a) {
+    const int rc = validate_loss_dims(a, "loss_kl_scratch_bytes");
+    return rc ? rc : fpd_loss_kl_scratch_size(*a);
+}
+
+int fpd_loss_kl(const fpd_loss_kl_t* k, fpd_stream_t stream) {
+    FPD_REQUIRE(k, "loss_kl: null pointer");
+    const fpd_loss_t* a = &k->base;
+    FPD_REQUIRE(a->teacher && a->target && a->weight && a->losses, "loss_kl: null pointer");
+    int rc = validate_loss_dims(a, "loss_kl");
+    if (rc) return rc;
+    FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "loss_kl: bad dtype %d", a->dtype);
+    for (int s = 0; s < a->S; ++s) FPD_REQUIRE(a->out[s], "loss_kl: null map of stack %d", s);
+    FPD_REQUIRE(k->kl_pose || k->kl_kd, "loss_kl: neither term is KL (two MSE terms are fpd_loss)");
+    FPD_REQUIRE(!k->kl_pose || (k->temp_pose > 0.f && k->temp_pose < INFINITY), "loss_kl: pose temperature %g is not positive", (double)k->temp_pose);
+    FPD_REQUIRE(!k->kl_kd || (k->temp_kd > 0.f && k->temp_kd < INFINITY), "loss_kl: distillation temperature %g is not positive", (double)k->temp_kd);
+    const int64_t need = fpd_loss_kl_scratch_size(*a);
+    FPD_REQUIRE(k->scratch && ((uintptr_t)k->scratch & 7) == 0, "loss_kl: scratch is null or not 8-byte aligned");
+    FPD_REQUIRE(k->scratch_bytes >= need, "loss_kl: scratch of %lld bytes, fpd_loss_kl_scratch_bytes() asks for %lld",
+                (long long)k->scratch_bytes, (long long)need);
+    fpd_loss_kl_t kk = *k;
+    if (!kk.kl_pose) kk.temp_pose = 1.f;         // (an MSE term's temperature is not read; keep its reciprocal finite)
+    if (!kk.kl_kd) kk.temp_kd = 1.f;
+    rc = fpd_loss_kl_launch(kk, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a && a->param && a->grad && a->m && a->v && a->n >= 0, "adam: null pointer");
     int rc = fpd_adam_launch(*a, (hipStream_t)stream);
@@ -722,7 +749,7 @@ int fpd_nhwc_to_nchw(const void* src, float* dst, int32_t N, int32_t C, int32_t 
 struct fpd_op {
     int32_t type;
     union {
-        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_adam_t adam; fpd_sgd_t sgd; fpd_ew_merge_t ewm;
+        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_loss_kl_t losskl; fpd_adam_t adam; fpd_sgd_t sgd; fpd_ew_merge_t ewm;
         fpd_memset_t mset; fpd_table_t table;
     } u;
 };
@@ -778,6 +805,7 @@ int fpd_plan_add(fpd_plan* p, int32_t op, const void* args, int64_t bytes) {
         case FPD_OP_EW_MERGE: want = sizeof(fpd_ew_merge_t); break;
         case FPD_OP_LOSS: want = sizeof(fpd_loss_t); break;
         case FPD_OP_LOSS_OHKM: want = sizeof(fpd_loss_ohkm_t); break;
+        case FPD_OP_LOSS_KL: want = sizeof(fpd_loss_kl_t); break;
         case FPD_OP_ADAM: want = sizeof(fpd_adam_t); break;
         case FPD_OP_SGD: want = sizeof(fpd_sgd_t); break;
         case FPD_OP_MEMSET: case FPD_OP_NOP: want = sizeof(fpd_memset_t); break;
@@ -856,6 +884,7 @@ static void set_op_tag(int idx, const fpd_op& o) {
         case FPD_OP_AFFSUM: snprintf(t, sizeof(t), "affsum N=%d H=%d W=%d C=%d terms=%d", o.u.affsum.N, o.u.affsum.H, o.u.affsum.W, o.u.affsum.C, o.u.affsum.nterms); break;
         case FPD_OP_LOSS: snprintf(t, sizeof(t), "loss B=%d J=%d H=%d W=%d S=%d", o.u.loss.B, o.u.loss.J, o.u.loss.H, o.u.loss.W, o.u.loss.S); break;
         case FPD_OP_LOSS_OHKM: snprintf(t, sizeof(t), "loss_ohkm B=%d J=%d H=%d W=%d S=%d k=%d,%d", o.u.lossk.base.B, o.u.lossk.base.J, o.u.lossk.base.H, o.u.lossk.base.W, o.u.lossk.base.S, o.u.lossk.topk_pose, o.u.lossk.topk_kd); break;
+        case FPD_OP_LOSS_KL: snprintf(t, sizeof(t), "loss_kl B=%d J=%d H=%d W=%d S=%d kl=%d,%d T=%g,%g", o.u.losskl.base.B, o.u.losskl.base.J, o.u.losskl.base.H, o.u.losskl.base.W, o.u.losskl.base.S, o.u.losskl.kl_pose, o.u.losskl.kl_kd, (double)o.u.losskl.temp_pose, (double)o.u.losskl.temp_kd); break;
         case FPD_OP_ADAM: snprintf(t, sizeof(t), "adam n=%lld", (long long)o.u.adam.n); break;
         case FPD_OP_SGD: snprintf(t, sizeof(t), "sgd n=%lld momentum=%g wd=%g%s", (long long)o.u.sgd.n, (double)o.u.sgd.momentum, (double)o.u.sgd.weight_decay, o.u.sgd.nesterov ? " nesterov" : ""); break;
         case FPD_OP_WREDUCE: snprintf(t, sizeof(t), "wreduce entries=%d", o.u.table.n); break;
@@ -886,6 +915,7 @@ static int run_op(const fpd_op& o, fpd_stream_t s) {
         case FPD_OP_EW_MERGE: return fpd_ew_merge(&o.u.ewm, s);
         case FPD_OP_LOSS: return fpd_loss(&o.u.loss, s);
         case FPD_OP_LOSS_OHKM: return fpd_loss_ohkm(&o.u.lossk, s);
+        case FPD_OP_LOSS_KL: return fpd_loss_kl(&o.u.losskl, s);
         case FPD_OP_ADAM: return fpd_adam(&o.u.adam, s);
         case FPD_OP_SGD: return fpd_sgd(&o.u.sgd, s);
         case FPD_OP_MEMSET: {

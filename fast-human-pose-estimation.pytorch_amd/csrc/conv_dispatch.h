@@ -160,6 +160,8 @@ int fpd_ew_blocks_option(int value);      // >= 1: grid cap of fpd_elementwise_l
 int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
 int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& a, hipStream_t st);      // csrc/loss_ohkm.hip: two launches
 int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a);
+int fpd_loss_kl_launch(const fpd_loss_kl_t& a, hipStream_t st);          // csrc/loss_kl.hip: two launches
+int64_t fpd_loss_kl_scratch_size(const fpd_loss_t& a);
 int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st);
 int fpd_sgd_launch(const fpd_sgd_t& a, hipStream_t st);
 int fpd_weight_prep_launch(const fpd_wprep_entry_t* table, int n, int64_t max_elems, int dtype, hipStream_t st);

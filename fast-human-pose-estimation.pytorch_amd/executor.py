@@ -20,7 +20,8 @@ _EW = {'bnrelu_fwd': R.EW_BNRELU_FWD, 'bnrelu_bwd_r': R.EW_BNRELU_BWD_R, 'bn_bwd
 _ARENA_DTYPE = {'param': torch.float32, 'grad': torch.float32, 'rstat': torch.float32, 'nbt': torch.int64,
                 'stats': torch.int64, 'losses': torch.float64, 'image': torch.float32, 'target': torch.float32,
                 'weight': torch.float32, 'adam_m': torch.float32, 'adam_v': torch.float32, 'fold': torch.float32,
-                'w8': torch.uint8, 'w8s': torch.float32, 'ohkm_scratch': torch.float64, 'ohkm_masks': torch.int32}
+                'w8': torch.uint8, 'w8s': torch.float32, 'ohkm_scratch': torch.float64, 'ohkm_masks': torch.int32,
+                'kl_scratch': torch.float64}
 
 
 def act_torch_dtype(dtype):
@@ -848,7 +849,7 @@ class FusedFPDStep:
 
     def __init__(self, student_state, student_cfg, teacher_state, teacher_cfg, batch, height, width, alpha,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, world_size=1, adam=None, teacher_chunks=None,
-                 use_target_weight=(True, True), ohkm=None, sgd=None):
+                 use_target_weight=(True, True), ohkm=None, sgd=None, kl=None):
         dev = student_state.device
         if adam is not None and sgd is not None:
             raise R.FpdError('FusedFPDStep: adam= and sgd= are mutually exclusive')
@@ -865,6 +866,17 @@ class FusedFPDStep:
             self.ohkm = tuple(self.J if k is None else int(k) for k in ohkm)
             if len(self.ohkm) != 2 or not all(1 <= k <= self.J for k in self.ohkm):
                 raise R.FpdError('FusedFPDStep: ohkm=%r: topk must lie in [1, J=%d]' % (ohkm, self.J))
+        # JointsKLDLoss(temperature) of the pose / distillation criterion: (T_pose or None, T_kd or None); None (the default) is
+        # the plan of before; a None inside the pair is a JointsMSELoss term
+        self.kl = None
+        if kl is not None:
+            if ohkm is not None:
+                raise R.FpdError('FusedFPDStep: kl= and ohkm= are mutually exclusive (no kernel pairs a KL term with hard-keypoint mining)')
+            self.kl = tuple(None if t is None else float(t) for t in kl)
+            if len(self.kl) != 2 or self.kl == (None, None):
+                raise R.FpdError('FusedFPDStep: kl=%r: a pair of temperatures, at least one of them not None' % (kl,))
+            if not all(t is None or (0.0 < t < float('inf')) for t in self.kl):
+                raise R.FpdError('FusedFPDStep: kl=%r: a temperature must be positive' % (kl,))
         # teacher first: it owns the image buffer; its last-stack map is read in place by the loss kernel
         self.teacher = None
         self.teachers = []
@@ -914,8 +926,15 @@ class FusedFPDStep:
                 R.check(int(nbytes), 'fpd_loss_ohkm_scratch_bytes')
             A.alloc('ohkm_scratch', nbytes // 8)
             A.alloc('ohkm_masks', len(g.outputs) * 2 * self.B)
+        if self.kl is not None:
+            d = R.LossT()
+            d.B, d.J, d.H, d.W, d.S = self.B, self.J, self.hh, self.hw, len(g.outputs)
+            nbytes = R.lib().fpd_loss_kl_scratch_bytes(d)
+            if nbytes < 0:
+                R.check(int(nbytes), 'fpd_loss_kl_scratch_bytes')
+            A.alloc('kl_scratch', nbytes // 8)
         self.student.mid_ops = [G.Op('loss', extra_in=list(g.outputs), extra_out=list(g.out_grads))]
-        add_loss = self._add_loss if self.ohkm is None else self._add_loss_ohkm
+        add_loss = self._add_loss_kl if self.kl is not None else self._add_loss if self.ohkm is None else self._add_loss_ohkm
         self.student.mid_native = [lambda plan: add_loss(plan, 0)]
         self.student.finalize()
         b = len(self.student.plan)                 # second loss op reading the other staged teacher map
@@ -1020,6 +1039,18 @@ class FusedFPDStep:
         k.scratch, k.scratch_bytes = sc.data_ptr(), sc.numel() * sc.element_size()
         k.masks = A.tensor('ohkm_masks').data_ptr()
         plan.add(R.OP_LOSS_OHKM, k)
+
+    def _add_loss_kl(self, plan, slot):
+        """_add_loss with a spatial-softmax KL term (csrc/loss_kl.hip): the same arguments + flags, temperatures and scratch."""
+        plan.add(*self.student.low.memset('losses'))
+        k = R.LossKlT()
+        self._fill_loss(k.base, slot)
+        tp, tk = self.kl
+        k.kl_pose, k.kl_kd = int(tp is not None), int(tk is not None)
+        k.temp_pose, k.temp_kd = tp or 1.0, tk or 1.0
+        sc = self.student.A.tensor('kl_scratch')
+        k.scratch, k.scratch_bytes = sc.data_ptr(), sc.numel() * sc.element_size()
+        plan.add(R.OP_LOSS_KL, k)
 
     def ohkm_masks(self):
         """[S][2][B] int32 of the last step: bit j = joint j of (stack, {pose, kd}, sample) was kept -- synchronises."""

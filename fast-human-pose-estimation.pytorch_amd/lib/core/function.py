@@ -7,7 +7,7 @@ device appends {avg_acc, cnt, pose, kd} of each iteration to a ring (csrc/pck.hi
 synchronisation of the loop -- when a log line is due (PRINT_FREQ) and at the end of the epoch.
 
 Not silently substituted: the fused step implements Adam and SGD (lib.utils.utils.FusedAdam / FusedSGD) and JointsMSELoss /
-JointsOHKMMSELoss criteria; any other optimizer / criterion object raises instead of being ignored."""
+JointsOHKMMSELoss / JointsKLDLoss criteria; any other optimizer / criterion object raises instead of being ignored."""
 import logging
 import os
 import time
@@ -18,7 +18,7 @@ from ... import executor as E
 from ... import runtime as R
 from ..utils.utils import FusedAdam, FusedSGD
 from .evaluate import accuracy  # noqa: F401  (re-exported like the reference's core.function namespace)
-from .loss import JointsMSELoss, JointsOHKMMSELoss
+from .loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss
 
 logger = logging.getLogger(__name__)
 
@@ -44,23 +44,34 @@ def _unwrap(m):
 def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
     """The fused step runs ITS Adam or SGD and ITS JointsMSELoss / JointsOHKMMSELoss: refuse objects it would otherwise
     silently ignore.  Returns the use_target_weight pair and the topk pair (None for a JointsMSELoss criterion; None instead
-    of the pair when neither criterion mines)."""
+    of the pair when neither criterion mines).  With a JointsKLDLoss in either slot a third element follows: the temperature
+    pair (None for a JointsMSELoss criterion); a KL criterion beside a mining one is refused."""
     if not isinstance(optimizer, (FusedAdam, FusedSGD)):
         raise R.FpdError('fpd_train: the fused MI355X step implements Adam and SGD only (utils.get_optimizer with '
                          "TRAIN.OPTIMIZER 'adam' -> FusedAdam, 'sgd' -> FusedSGD); got %s -- its update rule and state "
                          'would be ignored' % type(optimizer).__name__)
     for name, c in (('pose_criterion', pose_criterion), ('kd_pose_criterion', kd_pose_criterion)):
-        if not isinstance(c, (JointsMSELoss, JointsOHKMMSELoss)):
-            raise R.FpdError('fpd_train: %s must be a core.loss.JointsMSELoss or core.loss.JointsOHKMMSELoss (the fused loss '
-                             'kernels evaluate exactly those criteria), got %s' % (name, type(c).__name__))
+        if not isinstance(c, (JointsMSELoss, JointsOHKMMSELoss, JointsKLDLoss)):
+            raise R.FpdError('fpd_train: %s must be a core.loss.JointsMSELoss, core.loss.JointsOHKMMSELoss or core.loss.JointsKLDLoss '
+                             '(the fused loss kernels evaluate exactly those criteria), got %s' % (name, type(c).__name__))
     topk = tuple(int(c.topk) if isinstance(c, JointsOHKMMSELoss) else None for c in (pose_criterion, kd_pose_criterion))
-    return ((bool(pose_criterion.use_target_weight), bool(kd_pose_criterion.use_target_weight)),
-            None if topk == (None, None) else topk)
+    kl = tuple(float(c.temperature) if isinstance(c, JointsKLDLoss) else None for c in (pose_criterion, kd_pose_criterion))
+    use_w = (bool(pose_criterion.use_target_weight), bool(kd_pose_criterion.use_target_weight))
+    if kl != (None, None):
+        if topk != (None, None):
+            raise R.FpdError('fpd_train: a JointsKLDLoss criterion cannot be paired with a JointsOHKMMSELoss (no fused kernel '
+                             'evaluates that pair); use JointsMSELoss for the other criterion')
+        if not all(t is None or 0.0 < t < float('inf') for t in kl):
+            raise R.FpdError('fpd_train: JointsKLDLoss temperature must be positive, got %r' % (kl,))
+        return use_w, None, kl
+    return use_w, None if topk == (None, None) else topk
 
 
-def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True), ohkm=None):
+def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True), ohkm=None,
+                   kl=None):
     """One FusedFPDStep per (student, teacher, batch shape); shares the optimizer state with the FusedAdam / FusedSGD object.
-    tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair.
+    tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair;
+    kl: its temperature pair.
     A FusedSGD's (momentum, weight_decay, nesterov) live in the recorded plan op, so they are part of the key."""
     s, t = _unwrap(model), (_unwrap(tmodel) if tmodel is not None else None)
     # The cache lives ON the student module (not in a module-level dict keyed by id(): ids are recycled once an object
@@ -68,6 +79,8 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     # and optimizer are compared by identity through the references the entry holds, so they cannot be recycled either.
     cache = s.__dict__.setdefault('_fused_steps', {})
     key = (tuple(batch_shape), float(alpha), world_size, tuple(use_target_weight)) + ((tuple(ohkm),) if ohkm is not None else ())
+    if kl is not None:
+        key += (('kl',) + tuple(kl),)
     is_sgd = isinstance(optimizer, FusedSGD)
     if is_sgd:
         g = optimizer.param_groups[0]
@@ -80,7 +93,7 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     step = E.FusedFPDStep(s.device_state(), s.cfg_hg, t.device_state() if t is not None else None,
                           t.cfg_hg if t is not None else None, n, h, w, alpha,
                           lr=float(optimizer.param_groups[0]['lr']), world_size=world_size,
-                          use_target_weight=use_target_weight, ohkm=ohkm, **{'sgd' if is_sgd else 'adam': optimizer})
+                          use_target_weight=use_target_weight, ohkm=ohkm, kl=kl, **{'sgd' if is_sgd else 'adam': optimizer})
     cache[key] = (t, optimizer, step)
     return step
 
@@ -125,7 +138,7 @@ def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writ
 def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
                     output_dir, vis, img_writer):
     kd_mode = tmodel is not None
-    use_w, ohkm = crit
+    use_w, ohkm, kl = crit if len(crit) == 3 else tuple(crit) + (None,)
     batch_time, data_time = AverageMeter(), AverageMeter()
     losses, pose_losses, kd_pose_losses, acc = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     model.train()          # function.py:110-111
@@ -153,7 +166,7 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
             if step is not None:                       # batch shape changed (last, smaller batch): finish the old step
                 step.flush()
                 drain()
-            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm)
+            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm, kl)
             metric = step.enable_metric(min_slots=config.PRINT_FREQ + 1)   # PCK + losses of every iteration, logged on the device
             metric.drain()
             n_img = inp.size(0)

@@ -17,7 +17,7 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
  EW_ADD, EW_RELU_MASK, EW_DILATE2) = range(10)
 (OP_CONV, OP_WGRAD, OP_STEM_FWD, OP_STEM_WGRAD, OP_EW, OP_LOSS, OP_ADAM, OP_MEMSET, OP_WPREP, OP_BNUPD,
  OP_WREDUCE, OP_BNECK, OP_BNECK_FOLD, OP_CONV_PAIR, OP_BNECK_PAIR, OP_EW_PAIR, OP_PCK, OP_HEAD, OP_HEAD_FOLD,
- OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE) = range(27)
+ OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE, OP_LOSS_KL) = range(28)
 EWM_MAXPOOL_BWD, EWM_SUMPOOL = 0, 1
 AFFSUM_MAX = 4
 MAX_STACKS = 8
@@ -229,6 +229,11 @@ class LossOhkmT(C.Structure):
                 ('masks', _vp)]
 
 
+class LossKlT(C.Structure):
+    _fields_ = [('base', LossT), ('kl_pose', _i32), ('kl_kd', _i32), ('temp_pose', _f32), ('temp_kd', _f32),
+                ('scratch', _vp), ('scratch_bytes', _i64)]
+
+
 class AdamT(C.Structure):
     _fields_ = [('n', _i64), ('param', _vp), ('grad', _vp), ('m', _vp), ('v', _vp), ('param_lp', _vp),
                 ('lr', _f32), ('beta1', _f32), ('beta2', _f32), ('eps', _f32), ('bias_corr1', _f32),
@@ -272,7 +277,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
             'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT,
             'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
-            'fpd_vis_heatmap_grid_t': VisHeatmapGridT}
+            'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -326,6 +331,8 @@ SYMBOLS = {
     'fpd_loss': (C.c_int, [C.POINTER(LossT), _vp]),
     'fpd_loss_ohkm': (C.c_int, [C.POINTER(LossOhkmT), _vp]),
     'fpd_loss_ohkm_scratch_bytes': (C.c_int64, [C.POINTER(LossT)]),
+    'fpd_loss_kl': (C.c_int, [C.POINTER(LossKlT), _vp]),
+    'fpd_loss_kl_scratch_bytes': (C.c_int64, [C.POINTER(LossT)]),
     'fpd_adam': (C.c_int, [C.POINTER(AdamT), _vp]),
     'fpd_sgd': (C.c_int, [C.POINTER(SgdT), _vp]),
     'fpd_weight_prep': (C.c_int, [_vp, _i32, _i64, _i32, _vp]),

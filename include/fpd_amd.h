@@ -356,6 +356,23 @@ typedef struct {
     uint32_t* masks;       /* optional [S][2][B]: bit j = joint j of that (stack, term, sample) was kept */
 } fpd_loss_ohkm_t;
 
+/* JointsKLDLoss (soft-label KL over the spatial softmax of a heat map) for either term of fpd_loss_t, the other staying
+ * JointsMSELoss; all stacks, forward and backward in two launches.  Per criterion call (stack map s against r = target / teacher
+ * map, weight w, temperature T > 0), with p = softmax(s/T), q = softmax(r/T) over the hw pixels of that one map:
+ *   L[n,j] = w[n,j] T^2 sum_x q_x ((r_x - s_x)/T - lse(r/T) + lse(s/T)) ;  loss = 1/(B J) sum_{n,j} L[n,j] ;
+ *   d loss / d s_x = w[n,j] T (p_x - q_x) / (B J).
+ * The weight enters ONCE (not squared as in the MSE terms).  Both softmaxes subtract the row maximum; q_x == 0 contributes an
+ * exact 0 and no logarithm of a probability is taken.  dout_s = grad_scale [(1-alpha) dpose_s + alpha dkd_s] with each term MSE
+ * (fpd_loss_t's) or KL.  base.losses keeps {pose, kd} (caller zeroes); no other buffer needs zeroing, every sum is formed in a
+ * fixed order (bit-repeatable).  J <= 32.  Refused: both flags 0 (that is fpd_loss), a temperature <= 0 of a KL term. */
+typedef struct {
+    fpd_loss_t base;
+    int32_t kl_pose, kl_kd;       /* 1: that term is KL, 0: MSE */
+    float temp_pose, temp_kd;     /* temperature of a KL term (ignored for an MSE term) */
+    void* scratch;         /* fpd_loss_kl_scratch_bytes(&base) bytes, 8-byte aligned: per-block row statistics */
+    int64_t scratch_bytes;
+} fpd_loss_kl_t;
+
 /* torch.optim.Adam(lr) step over one flat fp32 arena (lib/utils/utils.py:69-73), optionally
  * emitting the bf16 working copy of the parameters. */
 typedef struct {
@@ -450,6 +467,9 @@ int fpd_loss(const fpd_loss_t* a, fpd_stream_t stream);
 int fpd_loss_ohkm(const fpd_loss_ohkm_t* a, fpd_stream_t stream);
 /* bytes of fpd_loss_ohkm_t.scratch for these dimensions (B, J, H, W, S are looked at); negative on bad dimensions */
 int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a);
+int fpd_loss_kl(const fpd_loss_kl_t* a, fpd_stream_t stream);
+/* bytes of fpd_loss_kl_t.scratch for these dimensions (B, J, H, W, S are looked at); negative on bad dimensions */
+int64_t fpd_loss_kl_scratch_bytes(const fpd_loss_t* a);
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream);
 /* refuses (before any launch) null param / grad, n < 0, momentum < 0, weight_decay < 0, momentum != 0 without buf, nesterov without momentum */
 int fpd_sgd(const fpd_sgd_t* a, fpd_stream_t stream);
@@ -863,7 +883,8 @@ enum {
     FPD_OP_WQUANT = 23,         /* args: fpd_table_t over fpd_wquant_entry_t */
     FPD_OP_LOSS_OHKM = 24,      /* args: fpd_loss_ohkm_t */
     FPD_OP_SGD = 25,            /* args: fpd_sgd_t */
-    FPD_OP_EW_MERGE = 26        /* args: fpd_ew_merge_t */
+    FPD_OP_EW_MERGE = 26,       /* args: fpd_ew_merge_t */
+    FPD_OP_LOSS_KL = 27         /* args: fpd_loss_kl_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;

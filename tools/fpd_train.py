@@ -15,7 +15,8 @@ scenes that are augmented, cropped and labelled on the device per batch (DATASET
 PROB_HALF_BODY / NUM_JOINTS_HALF_BODY, LOSS.USE_DIFFERENT_JOINTS_WEIGHT; lib/dataset/device_dataset.py), and KD.TEACHER 'synthetic' builds a
 random teacher with calibrated BN statistics instead of loading a checkpoint.  LOSS.USE_OHKM of the student config makes
 the pose criterion a JointsOHKMMSELoss(topk=LOSS.TOPK), LOSS.USE_OHKM of the teacher config the distillation criterion
-(make_criterion below); the reference declares both keys and its tools never read them (its class is never instantiated).
+(make_criterion below); KD.LOSS 'kl' makes the distillation criterion a JointsKLDLoss(KD.TEMPERATURE) (make_kd_criterion);
+the reference declares both keys and its tools never read them (its class is never instantiated).
 """
 import argparse
 import logging
@@ -36,7 +37,7 @@ from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import fpd_train, train, validate  # noqa: E402
 from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa: E402
 from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
-from fpd_amd.lib.core.loss import JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
+from fpd_amd.lib.core.loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
 from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
                                      save_checkpoint)
 
@@ -71,6 +72,24 @@ def make_criterion(c):
     if c.LOSS.USE_OHKM:
         return JointsOHKMMSELoss(use_target_weight=c.LOSS.USE_TARGET_WEIGHT, topk=c.LOSS.TOPK)
     return JointsMSELoss(use_target_weight=c.LOSS.USE_TARGET_WEIGHT)
+
+
+def make_kd_criterion(c, tc):
+    """The distillation criterion: KD.LOSS 'mse' (the default) -> make_criterion(teacher config) as before; 'kl' ->
+    JointsKLDLoss(teacher config's LOSS.USE_TARGET_WEIGHT, KD.TEMPERATURE), the soft-label KL over the spatial softmax of
+    the teacher's heat maps (:175 "you can choose or replace pose_loss and kd_pose_loss type").  No fused kernel pairs a
+    KL term with hard-keypoint mining, so 'kl' beside LOSS.USE_OHKM of either config ends the run here."""
+    kind = str(c.KD.LOSS).lower()
+    if kind == 'mse':
+        return make_criterion(tc)
+    if kind != 'kl':
+        sys.exit("ERROR: KD.LOSS %r: choose 'mse' or 'kl'." % (c.KD.LOSS,))
+    if tc.LOSS.USE_OHKM or c.LOSS.USE_OHKM:
+        sys.exit("ERROR: KD.LOSS 'kl' cannot be combined with LOSS.USE_OHKM (%s config): the fused loss pairs a KL term "
+                 'with a plain MSE term only.' % ('teacher' if tc.LOSS.USE_OHKM else 'student'))
+    if not float(c.KD.TEMPERATURE) > 0.0:
+        sys.exit('ERROR: KD.TEMPERATURE must be positive, got %r.' % (c.KD.TEMPERATURE,))
+    return JointsKLDLoss(use_target_weight=tc.LOSS.USE_TARGET_WEIGHT, temperature=float(c.KD.TEMPERATURE))
 
 
 def run(args, normal=False):
@@ -118,6 +137,10 @@ def run(args, normal=False):
 
     pose_criterion = make_criterion(cfg).to(dev)                                             # :145-147,177-179
     kd_pose_criterion = make_criterion(tcfg).to(dev)
+    if not normal:                                                                           # KD.LOSS: 'mse' leaves it as it is
+        kd_pose_criterion = make_kd_criterion(cfg, tcfg).to(dev)
+    if isinstance(kd_pose_criterion, JointsKLDLoss):
+        logger.info('=> distillation criterion: spatial-softmax KL, temperature %g', kd_pose_criterion.temperature)
     val_criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)      # the validation loss stays plain MSE
     if cfg.LOSS.USE_OHKM or tcfg.LOSS.USE_OHKM:
         logger.info('=> hard keypoint mining: pose criterion %s, distillation criterion %s',
