@@ -94,7 +94,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t); SZ(fpd_loss_kl_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
-    SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t);
+    SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t); SZ(fpd_dark_t);
     SZ(fpd_vis_minmax_t); SZ(fpd_vis_max_preds_t); SZ(fpd_vis_joints_grid_t); SZ(fpd_vis_heatmap_grid_t);
 #undef SZ
     return -1;
@@ -488,6 +488,29 @@ int fpd_val_post(const fpd_val_post_t* a, fpd_stream_t stream) {
     if (a->b != nullptr)
         for (int j = 0; j < a->J; ++j) FPD_REQUIRE(a->src[j] >= 0 && a->src[j] < a->J, "val_post: src[%d] = %d out of range", j, a->src[j]);
     int rc = fpd_val_post_launch(*a, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
+int fpd_dark_refine(const fpd_dark_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->hm && a->taps, "dark_refine: null pointer (map or taps)");
+    FPD_REQUIRE(a->ksize >= FPD_DARK_MIN_KSIZE && a->ksize <= FPD_DARK_MAX_KSIZE && (a->ksize & 1), "dark_refine: ksize = %d (odd, %d..%d)",
+                a->ksize, FPD_DARK_MIN_KSIZE, FPD_DARK_MAX_KSIZE);
+    FPD_REQUIRE(a->layout == FPD_DARK_NCHW || a->layout == FPD_DARK_NHWC, "dark_refine: bad layout %d", a->layout);
+    FPD_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->J > 0 && a->J <= FPD_MAX_JOINTS, "dark_refine: bad dims (J <= %d)", FPD_MAX_JOINTS);
+    FPD_REQUIRE((int64_t)a->H * a->W <= FPD_DARK_MAX_HW, "dark_refine: a %dx%d map does not fit LDS (H * W <= %d)", a->H, a->W, FPD_DARK_MAX_HW);
+    FPD_REQUIRE((int64_t)a->N * a->H * a->W * a->J < ((int64_t)1 << 31), "dark_refine: map too large");
+    FPD_REQUIRE((a->trans == nullptr) == (a->preds == nullptr), "dark_refine: trans and preds go together");
+    const bool form_a = a->trans != nullptr;
+    const bool form_b = a->center || a->scale || a->all_preds;
+    FPD_REQUIRE(!(form_a && form_b), "dark_refine: both output forms given (trans/preds and center/scale/all_preds)");
+    FPD_REQUIRE(form_a || form_b || a->coords, "dark_refine: no output (neither form, no coords)");
+    if (form_b) {
+        FPD_REQUIRE(a->center && a->scale && a->all_preds, "dark_refine: null pointer (center, scale and all_preds go together)");
+        FPD_REQUIRE(a->row0 >= 0, "dark_refine: row0 = %lld is negative", (long long)a->row0);
+        FPD_REQUIRE(a->row0 + a->N <= a->rows, "dark_refine: rows %lld..%lld outside the %lld result rows", (long long)a->row0,
+                    (long long)(a->row0 + a->N - 1), (long long)a->rows);
+    }
+    int rc = fpd_dark_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 

@@ -135,6 +135,7 @@ int fpd_flip_w_launch(const float* x, float* y, int64_t rows, int W, hipStream_t
 int fpd_flip_merge_launch(const fpd_flipmerge_t& p, hipStream_t st);
 int fpd_final_preds_launch(const fpd_finalpreds_t& p, hipStream_t st);
 int fpd_val_post_launch(const fpd_val_post_t& p, hipStream_t st);
+int fpd_dark_launch(const fpd_dark_t& p, hipStream_t st);                         // csrc/dark.hip
 int fpd_vis_minmax_launch(const fpd_vis_minmax_t& p, hipStream_t st);             // csrc/vis.hip
 int fpd_vis_max_preds_launch(const fpd_vis_max_preds_t& p, hipStream_t st);
 int fpd_vis_joints_grid_launch(const fpd_vis_joints_grid_t& p, hipStream_t st);

@@ -15,6 +15,7 @@
 // bit-identical to the reference functions (tests/golden/infer_ref.npz).
 #include "argmax.h"
 #include "common.h"
+#include "map_coords.h"
 #include "val_post_math.h"
 
 namespace {
@@ -34,17 +35,6 @@ __device__ __forceinline__ void peak_coords(ArgMax m, int H, int W, int post_pro
             cy += (dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f));
         }
     }
-}
-
-// transform_preds (transforms.py:50-55,99-102) in float64, stored as float32: trans[n] . [x, y, 1].  The two rows are written
-// out with the fused multiply-adds final_preds_kernel has always been compiled to (x: t0*X first, y: t4*Y first), with
-// contraction off, so that every kernel that maps coordinates rounds alike whatever the compiler would choose per call site:
-// for float32 boxes the float64 sums sit on float32 rounding ties often enough for the order to show.
-__device__ __forceinline__ void map_coords(const double* t, float cx, float cy, float& ox, float& oy) {
-#pragma clang fp contract(off)
-    const double X = (double)cx, Y = (double)cy;
-    ox = (float)(t[2] + fma(t[1], Y, t[0] * X));
-    oy = (float)(t[5] + fma(t[3], X, t[4] * Y));
 }
 
 __global__ __launch_bounds__(256) void flip_w_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int W) {

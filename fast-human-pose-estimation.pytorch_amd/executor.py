@@ -1208,7 +1208,10 @@ class ValidateStep:
     returns.  'prep' (working weight copies, folded BN tables) runs once per validation in begin(): the weights do not
     change while it lasts.  For the flip test the last map of the first forward is kept as a copy of that one map
     (N*h*w*J elements) rather than in a second instance, which would hold a second activation arena to save one small
-    device-to-device copy."""
+    device-to-device copy.
+
+    With `dark` (TEST.DARK: the blur size) fpd_val_post runs without the quarter-pixel shift and one fpd_dark_refine launch
+    on the merged map overwrites x and y of the batch's rows of all_preds with the DARK decode (csrc/dark.hip)."""
 
     def __init__(self, inst):
         from .lib.core.evaluate import DeviceAccuracy
@@ -1233,16 +1236,22 @@ class ValidateStep:
         a.N, a.J, a.H, a.W, a.dtype = n, j, h, w, self.dtype
         a.center, a.scale, a.score = self.meta.data_ptr(), self.meta.data_ptr() + 16 * n, self.meta.data_ptr() + 32 * n
         a.merged = self.merged.data_ptr()
+        self.dark, self._taps = 0, {}                  # blur size (0: off); device taps per blur size
+        d = self.dark_args = R.DarkT()
+        d.N, d.J, d.H, d.W, d.layout = n, j, h, w, R.DARK_NHWC
+        d.hm, d.center, d.scale = a.merged, a.center, a.scale
         s = self.loss = R.LossT()
         s.B, s.J, s.H, s.W, s.S, s.dtype, s.target_nchw, s.alpha = n, j, h, w, 1, R.F32, 1, 0.0
         s.out[0] = s.teacher = self.merged.data_ptr()
         s.losses, s.grad_scale = self.losses.data_ptr(), 1.0
 
     def begin(self, all_preds, all_boxes, flip_pairs=None, shift=False, post_process=False, use_target_weight=True,
-              min_slots=1):
+              min_slots=1, dark=0):
         """Start a validation: all_preds [rows,J,3] float32 and all_boxes [rows,6] float64 device tensors the batches write
         into; flip_pairs None = no flip test.  Refreshes the working weights (the model may have trained since).  The ring
-        holds at least `min_slots` batches between two drains."""
+        holds at least `min_slots` batches between two drains.  dark: blur size of the DARK decoding, which replaces the
+        quarter-pixel shift (0: off)."""
+        from .lib.core.inference import dark_ksize, dark_taps_device
         from .lib.utils.transforms import channel_sources
         assert all_preds.dtype == torch.float32 and all_preds.is_contiguous() and tuple(all_preds.shape[1:]) == (self.J, 3)
         assert all_boxes.dtype == torch.float64 and all_boxes.is_contiguous() and tuple(all_boxes.shape[1:]) == (6,)
@@ -1256,7 +1265,15 @@ class ValidateStep:
         a = self.args
         a.rows, a.all_preds, a.all_boxes = all_preds.shape[0], all_preds.data_ptr(), all_boxes.data_ptr()
         self.flip = flip_pairs is not None
-        a.shift, a.post_process = int(bool(shift) and self.flip), int(bool(post_process))
+        self.dark = dark_ksize(dark)
+        a.shift, a.post_process = int(bool(shift) and self.flip), int(bool(post_process) and not self.dark)
+        if self.dark:
+            if self.H * self.W > R.DARK_MAX_HW:
+                raise R.FpdError('ValidateStep: DARK decoding holds the map in LDS, H * W <= %d, got %dx%d' % (R.DARK_MAX_HW, self.H, self.W))
+            if self.dark not in self._taps:
+                self._taps[self.dark] = dark_taps_device(self.dark, self.device)
+            d = self.dark_args
+            d.ksize, d.taps, d.rows, d.all_preds = self.dark, self._taps[self.dark].data_ptr(), a.rows, a.all_preds
         for k, s in enumerate(channel_sources(self.J, flip_pairs or [])):
             a.src[k] = s
         self.use_w = bool(use_target_weight)
@@ -1298,6 +1315,10 @@ class ValidateStep:
         else:
             a.a, a.b = self.out_ptr, None
         R.check(l.fpd_val_post(a, st), 'fpd_val_post')
+        if self.dark:
+            d = self.dark_args
+            d.box_f32, d.row0 = a.box_f32, a.row0
+            R.check(l.fpd_dark_refine(d, st), 'fpd_dark_refine')
         tgt = target.to(self.device, non_blocking=True).float().contiguous()
         wt = (target_weight.to(self.device, non_blocking=True).float().reshape(n, self.J).contiguous() if self.use_w else self.ones)
         self._keep = (inp, tgt, wt)

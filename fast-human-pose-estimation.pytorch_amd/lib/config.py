@@ -90,7 +90,10 @@ def _defaults():
         'TEST': {'BATCH_SIZE_PER_GPU': 32, 'FLIP_TEST': False, 'POST_PROCESS': False, 'SHIFT_HEATMAP': False, 'MODEL_FILE': '',
                  # read by DATASET.DATASET coco (default.py:110-119); NMS_THRE and BBOX_THRE are accepted and unused, as there
                  'USE_GT_BBOX': False, 'IMAGE_THRE': 0.1, 'NMS_THRE': 0.6, 'SOFT_NMS': False, 'OKS_THRE': 0.5, 'IN_VIS_THRE': 0.0,
-                 'COCO_BBOX_FILE': '', 'BBOX_THRE': 1.0},
+                 'COCO_BBOX_FILE': '', 'BBOX_THRE': 1.0,
+                 # not in the reference: DARK sub-pixel decoding (core.inference) in place of the POST_PROCESS quarter-pixel
+                 # shift; BLUR_KERNEL: its Gaussian blur size, odd, 9..31 (DarkPose YAMLs carry 11)
+                 'DARK': False, 'BLUR_KERNEL': 11},
         'KD': {'TRAIN_TYPE': 'NORMAL', 'TEACHER': '', 'ALPHA': 0.5,        # default.py:122-126
                'LOSS': 'mse', 'TEMPERATURE': 1.0},   # not in the reference: distillation criterion 'mse' | 'kl' (core.loss.JointsKLDLoss)
         'DEBUG': {'DEBUG': False, 'SAVE_BATCH_IMAGES_GT': False, 'SAVE_BATCH_IMAGES_PRED': False,

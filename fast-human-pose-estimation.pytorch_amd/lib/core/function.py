@@ -275,7 +275,8 @@ def _validate_body(config, val_loader, val_dataset, model, criterion, output_dir
     Every batch is enqueued work only (executor.ValidateStep): the eval-mode forward, TEST.FLIP_TEST's second forward on
     the width-flipped batch, and one launch that merges the two maps, takes the arg-max with the TEST.POST_PROCESS
     quarter-pixel shift, computes every sample's inverse affine map and writes the batch's rows of the device-resident
-    all_preds [num,J,3] / all_boxes [num,6]; JointsMSELoss and the PCK accuracy read the merged map and append to a device
+    all_preds [num,J,3] / all_boxes [num,6] (with TEST.DARK one more launch, the DARK decode of the merged map, overwrites
+    their x and y, and the quarter-pixel shift is off); JointsMSELoss and the PCK accuracy read the merged map and append to a device
     ring.  The host waits for the device when a `Test:` line is due (PRINT_FREQ) and once after the last batch, when the
     result arrays are downloaded.  A smaller last batch gets a step of its own shape.
 
@@ -285,6 +286,8 @@ def _validate_body(config, val_loader, val_dataset, model, criterion, output_dir
     image paths of the other ranks' rows from the dataset's own records and calls val_dataset.evaluate; the other ranks
     return the indicator rank 0 broadcasts (gather.broadcast, where the callable has one)."""
     import numpy as np
+
+    from .inference import dark_config
     if type(criterion) is not JointsMSELoss:
         raise R.FpdError('validate: the fused validation step evaluates core.loss.JointsMSELoss, got %s' % type(criterion).__name__)
     net = _unwrap(model)
@@ -320,7 +323,7 @@ def _validate_body(config, val_loader, val_dataset, model, criterion, output_dir
                     drain()
                 if id(step) not in n_img:
                     step.begin(all_preds, all_boxes, flip_pairs, config.TEST.SHIFT_HEATMAP, config.TEST.POST_PROCESS,
-                               criterion.use_target_weight, min_slots=config.PRINT_FREQ + 1)
+                               criterion.use_target_weight, min_slots=config.PRINT_FREQ + 1, dark=dark_config(config))
                     n_img[id(step)] = shape[0]
             if idx + shape[0] > num_samples:
                 raise R.FpdError('validate: the loader yields more than the %d samples of the dataset' % num_samples)
@@ -395,7 +398,7 @@ def _validate_per_batch(config, val_loader, val_dataset, model, criterion, outpu
 
     from ..utils.transforms import flip_input, flip_merge, get_affine_transform
     from .evaluate import DeviceAccuracy
-    from .inference import final_preds_device
+    from .inference import dark_config, final_preds_device
     batch_time, losses, acc = AverageMeter(), AverageMeter(), AverageMeter()
     model.eval()
     net = _unwrap(model)
@@ -431,7 +434,8 @@ def _validate_per_batch(config, val_loader, val_dataset, model, criterion, outpu
             c, s = _to_numpy(meta['center']), _to_numpy(meta['scale'])
             score = _to_numpy(meta['score'])
             trans = np.stack([get_affine_transform(c[k], s[k], 0, [w, h], inv=1) for k in range(n)])
-            _, preds, maxvals = final_preds_device(output, torch.from_numpy(trans).to(dev), config.TEST.POST_PROCESS)
+            _, preds, maxvals = final_preds_device(output, torch.from_numpy(trans).to(dev), config.TEST.POST_PROCESS,
+                                                   dark_config(config))
             # the one synchronisation of the iteration: results + the two scalars
             preds, maxvals = preds.cpu().numpy(), maxvals.cpu().numpy()
             losses.update(loss.item(), num_images)

@@ -131,6 +131,16 @@ class ValPostT(C.Structure):
                 ('score', _vp), ('merged', _vp), ('all_preds', _vp), ('all_boxes', _vp), ('src', _i32 * MAX_JOINTS)]
 
 
+DARK_NCHW, DARK_NHWC = 0, 1   # include/fpd_amd.h FPD_DARK_*
+DARK_MIN_KSIZE, DARK_MAX_KSIZE, DARK_MAX_HW = 9, 31, 16384
+
+
+class DarkT(C.Structure):
+    _fields_ = [('N', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('layout', _i32), ('ksize', _i32), ('box_f32', _i32),
+                ('_pad', _i32), ('row0', _i64), ('rows', _i64), ('hm', _vp), ('taps', _vp), ('coords', _vp), ('maxvals', _vp),
+                ('refined', _vp), ('trans', _vp), ('preds', _vp), ('center', _vp), ('scale', _vp), ('all_preds', _vp)]
+
+
 VIS_NCHW, VIS_NHWC = 0, 1     # include/fpd_amd.h FPD_VIS_*
 
 
@@ -275,7 +285,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
             'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
-            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT,
+            'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT, 'fpd_dark_t': DarkT,
             'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
             'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT}
 
@@ -314,6 +324,7 @@ SYMBOLS = {
     'fpd_flip_merge': (C.c_int, [C.POINTER(FlipMergeT), _vp]),
     'fpd_final_preds': (C.c_int, [C.POINTER(FinalPredsT), _vp]),
     'fpd_val_post': (C.c_int, [C.POINTER(ValPostT), _vp]),
+    'fpd_dark_refine': (C.c_int, [C.POINTER(DarkT), _vp]),
     'fpd_vis_minmax': (C.c_int, [C.POINTER(VisMinmaxT), _vp]),
     'fpd_vis_max_preds': (C.c_int, [C.POINTER(VisMaxPredsT), _vp]),
     'fpd_vis_joints_grid': (C.c_int, [C.POINTER(VisJointsGridT), _vp]),

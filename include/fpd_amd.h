@@ -595,6 +595,44 @@ typedef struct {
 } fpd_val_post_t;
 int fpd_val_post(const fpd_val_post_t* a, fpd_stream_t stream);
 
+/* Distribution-aware coordinate decoding (DARK, Zhang et al., CVPR 2020) in place of the quarter-pixel shift, one launch,
+ * per (sample, joint) with m the fp32 map (csrc/dark.hip, the Newton step in csrc/dark_math.h):
+ *   arg-max as in fpd_final_preds (first maximum wins, (0, 0) where the maximum is not positive); maxval from the raw map
+ *   B  = the separable blur of m with taps[ksize], rows then columns, zeros outside the map
+ *   L  = log(max(B * (maxval / max(B)), 1e-10)); nothing is refined where maxval <= 0 or max(B) <= 0
+ *   where 1 < px < W - 2 and 1 < py < H - 2: (x, y) += -Hess(L)^-1 grad(L) by central differences, if det(Hess) != 0,
+ *   in float64, rounded once into the float32 coordinate
+ * then the map to image coordinates in one of two forms:
+ *   (a) trans / preds as in fpd_finalpreds_t (both NULL: heat-map coordinates only)
+ *   (b) center / scale / box_f32 / row0 / rows / all_preds as in fpd_val_post_t: ONLY x and y of rows row0 .. row0+N-1 of
+ *       all_preds are written; maxval and all_boxes stay what fpd_val_post (post_process = 0) wrote
+ * taps: the normalised Gaussian of OpenCV's getGaussianKernel(ksize, 0), ksize odd in [9, 31], computed by the caller in
+ * float64.  Refused before any launch: null hm or taps, bad ksize or layout, J > FPD_MAX_JOINTS, H * W > FPD_DARK_MAX_HW
+ * (two fp32 images of the map live in LDS), both or neither of (a) and (b) other than the coordinates-only form,
+ * row0 < 0, row0 + N > rows. */
+#define FPD_DARK_NCHW 0
+#define FPD_DARK_NHWC 1
+#define FPD_DARK_MIN_KSIZE 9
+#define FPD_DARK_MAX_KSIZE 31
+#define FPD_DARK_MAX_HW 16384
+typedef struct {
+    int32_t N, J, H, W;
+    int32_t layout, ksize;         /* FPD_DARK_NCHW: [N,J,H,W] (the module API's output); FPD_DARK_NHWC: [N,H,W,J] (`merged`) */
+    int32_t box_f32, _pad;         /* form (b), as in fpd_val_post_t */
+    int64_t row0, rows;            /* form (b) */
+    const float* hm;               /* fp32 map in `layout` */
+    const double* taps;            /* [ksize] device */
+    float* coords;                 /* [N,J,2] heat-map coordinates (x, y), or NULL */
+    float* maxvals;                /* [N,J], or NULL */
+    int32_t* refined;              /* [N,J] 1 where the Newton step was taken (a zero step included), or NULL */
+    const double* trans;           /* (a) [N][2][3] */
+    float* preds;                  /* (a) [N,J,2] image coordinates */
+    const double* center;          /* (b) [N,2] device */
+    const double* scale;           /* (b) [N,2] device */
+    float* all_preds;              /* (b) [rows,J,3] float32: x and y of the batch's rows are overwritten */
+} fpd_dark_t;
+int fpd_dark_refine(const fpd_dark_t* a, fpd_stream_t stream);
+
 /* ---- debug images (lib/utils/vis.py of the reference: save_batch_image_with_joints, save_batch_heatmaps) ---- */
 /* The canvases the reference composes on the host with torchvision, cv2 and numpy, rendered on the device from the tensors
  * of the iteration; per-pixel arithmetic in csrc/vis_math.h.  The caller owns every buffer, downloads the uint8 canvases
