@@ -93,7 +93,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
     SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t); SZ(fpd_loss_kl_t);
-    SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t);
+    SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t); SZ(fpd_targets_unbiased_t);
     SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t); SZ(fpd_dark_t);
     SZ(fpd_vis_minmax_t); SZ(fpd_vis_max_preds_t); SZ(fpd_vis_joints_grid_t); SZ(fpd_vis_heatmap_grid_t);
 #undef SZ
@@ -650,6 +650,17 @@ int fpd_render_targets_w(const fpd_targets_w_t* w, fpd_stream_t stream) {
     FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0 && a->patch > 0 && (a->patch & 1), "render_targets_w: bad dims");
     FPD_REQUIRE(a->stride_x > 0 && a->stride_y > 0, "render_targets_w: bad stride");
     int rc = fpd_render_targets_w_launch(*w, (hipStream_t)stream);
+    return rc ? rc : check_launch();
+}
+
+int fpd_render_targets_unbiased(const fpd_targets_unbiased_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a && a->joints && a->vis && a->target && a->weight, "render_targets_unbiased: null pointer");
+    FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0, "render_targets_unbiased: bad dims (B=%d, J=%d, H=%d, W=%d)", a->B, a->J, a->H, a->W);
+    FPD_REQUIRE(a->sigma >= 1 && a->sigma <= 4096, "render_targets_unbiased: sigma=%d outside 1..4096", a->sigma);
+    FPD_REQUIRE(a->stride_x > 0 && a->stride_y > 0, "render_targets_unbiased: bad stride");
+    FPD_REQUIRE((int64_t)a->B * a->J < ((int64_t)1 << 31) && (int64_t)a->H * a->W < ((int64_t)1 << 31), "render_targets_unbiased: map too large");
+    FPD_REQUIRE(a->H + a->W <= 8192, "render_targets_unbiased: H + W = %d row and column factors exceed the 64 KB of LDS (8192)", a->H + a->W);
+    int rc = fpd_render_targets_unbiased_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 

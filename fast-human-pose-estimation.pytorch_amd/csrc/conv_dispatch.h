@@ -144,6 +144,7 @@ int64_t fpd_vis_joints_canvas_bytes(const fpd_vis_joints_grid_t& p);
 int fpd_render_targets_launch(const fpd_targets_t& a, hipStream_t st);
 int fpd_warp_affine_launch(const fpd_warp_t& a, hipStream_t st);
 int fpd_render_targets_w_launch(const fpd_targets_w_t& a, hipStream_t st);
+int fpd_render_targets_unbiased_launch(const fpd_targets_unbiased_t& a, hipStream_t st);
 int fpd_warp_affine_aug_launch(const fpd_warp_aug_t& a, hipStream_t st);
 int fpd_augment_params_launch(const fpd_augment_t& a, hipStream_t st);
 int fpd_oks_nms_launch(const fpd_oks_nms_t& a, hipStream_t st);

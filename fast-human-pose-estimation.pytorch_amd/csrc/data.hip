@@ -9,10 +9,14 @@
 //                          get_affine_transform, joint transform) from a device-resident database and a table of draws;
 //                          its output drives warp_affine_aug_kernel and render_targets_kernel, so a batch needs three
 //                          launches and no host work per sample
+//   render_targets_unbiased_kernel  DARK's unbiased encoding (include/fpd_amd.h fpd_targets_unbiased_t): the Gaussian at the
+//                          real-valued centre over the whole map, float64 values rounded once; the third launch of a batch
+//                          when MODEL.TARGET_TYPE is gaussian_unbiased
 #include <algorithm>
 
 #include "augment_math.h"
 #include "common.h"
+#include "encode_math.h"
 
 namespace {
 
@@ -45,6 +49,47 @@ __device__ __forceinline__ void render_targets_body(const fpd_targets_t& a, cons
 
 __global__ __launch_bounds__(256) void render_targets_kernel(const fpd_targets_t a) { render_targets_body(a, nullptr); }
 __global__ __launch_bounds__(256) void render_targets_w_kernel(const fpd_targets_w_t a) { render_targets_body(a.t, a.joints_weight); }
+
+// One workgroup per (sample, joint).  The decisions come from encode_math.h; the value of pixel (x, y) is the float64 product
+// of a column factor ex[x] and a row factor ey[y] (W + H exponentials per map instead of H * W), both in LDS: s_factor holds
+// ex[0..W) then ey[0..H).  Rows whose length is a multiple of four are written 16 bytes at a time when the buffer allows it.
+__global__ __launch_bounds__(256) void render_targets_unbiased_kernel(const fpd_targets_unbiased_t a) {
+    extern __shared__ double s_factor[];
+    const int bj = blockIdx.x, HW = a.H * a.W;
+    const double* jt = a.joints + (size_t)bj * 3;
+    float* tg = a.target + (size_t)bj * HW;
+    const bool has_jw = a.joints_weight != nullptr;
+    fpd_encode_place_t pl;
+    fpd_encode_place(jt[0], jt[1], a.stride_x, a.stride_y, a.sigma, a.W, a.H, a.vis[bj], has_jw, has_jw ? a.joints_weight[bj % a.J] : 0.f, &pl);
+    if (threadIdx.x == 0) a.weight[bj] = pl.weight;
+    const bool wide = (a.W & 3) == 0 && ((uintptr_t)a.target & 15) == 0;      // then every map starts on 16 bytes as well
+    if (!pl.drawn) {                                                        // the same for the whole block
+        if (wide) {
+            for (int q = threadIdx.x; q < HW / 4; q += blockDim.x) reinterpret_cast<float4*>(tg)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (int p = threadIdx.x; p < HW; p += blockDim.x) tg[p] = 0.f;
+        }
+        return;
+    }
+    double* ex = s_factor;
+    double* ey = s_factor + a.W;
+    for (int i = threadIdx.x; i < a.W + a.H; i += blockDim.x)
+        s_factor[i] = i < a.W ? fpd_encode_factor(i, pl.mu_x, a.sigma) : fpd_encode_factor(i - a.W, pl.mu_y, a.sigma);
+    __syncthreads();
+    if (wide) {
+        for (int q = threadIdx.x; q < HW / 4; q += blockDim.x) {
+            const int p = 4 * q, y = p / a.W, x = p - y * a.W;               // W % 4 == 0: the four pixels share the row
+            const double r = ey[y];
+            reinterpret_cast<float4*>(tg)[q] = make_float4(fpd_encode_value(ex[x], r), fpd_encode_value(ex[x + 1], r),
+                                                           fpd_encode_value(ex[x + 2], r), fpd_encode_value(ex[x + 3], r));
+        }
+    } else {
+        for (int p = threadIdx.x; p < HW; p += blockDim.x) {
+            const int y = p / a.W, x = p - y * a.W;
+            tg[p] = fpd_encode_value(ex[x], ey[y]);
+        }
+    }
+}
 
 // cv::saturate_cast<int>(double) = cvRound = round half to even
 __device__ __forceinline__ int cv_round(double v) { return __double2int_rn(v); }
@@ -162,6 +207,12 @@ __global__ __launch_bounds__(64) void augment_params_kernel(const fpd_augment_t 
 
 int fpd_render_targets_w_launch(const fpd_targets_w_t& a, hipStream_t st) {
     FPD_LAUNCH(render_targets_w_kernel, dim3(a.t.B * a.t.J), dim3(256), 0, st, a);
+    return 0;
+}
+
+// api.hip has checked (H + W) * 8 bytes against the LDS a kernel gets without asking
+int fpd_render_targets_unbiased_launch(const fpd_targets_unbiased_t& a, hipStream_t st) {
+    FPD_LAUNCH(render_targets_unbiased_kernel, dim3(a.B * a.J), dim3(256), (size_t)(a.H + a.W) * sizeof(double), st, a);
     return 0;
 }
 

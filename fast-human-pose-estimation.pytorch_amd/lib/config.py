@@ -72,6 +72,8 @@ def _defaults():
         'OUTPUT_DIR': 'output', 'LOG_DIR': 'log', 'DATA_DIR': '', 'GPUS': (0,), 'WORKERS': 4, 'PRINT_FREQ': 20,
         'AUTO_RESUME': False, 'PIN_MEMORY': True, 'RANK': 0,
         'CUDNN': {'BENCHMARK': True, 'DETERMINISTIC': False, 'ENABLED': True},
+        # TARGET_TYPE 'gaussian' (the reference's) or, not in the reference, 'gaussian_unbiased': DARK's encoding at the real-valued
+        # joint position (lib/dataset/device_dataset.py; the counterpart of TEST.DARK); any other value is read as 'gaussian'
         'MODEL': {'NAME': 'hourglass', 'INIT_WEIGHTS': False, 'PRETRAINED': '', 'NUM_JOINTS': 16, 'TAG_PER_JOINT': True,
                   'TARGET_TYPE': 'gaussian', 'IMAGE_SIZE': [256, 256], 'HEATMAP_SIZE': [64, 64], 'SIGMA': 2, 'DTYPE': 'fp32',
                   'EXTRA': {'NUM_FEATURES': 256, 'NUM_STACKS': 8, 'NUM_BLOCKS': 1}},

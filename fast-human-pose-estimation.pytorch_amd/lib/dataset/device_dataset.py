@@ -7,7 +7,8 @@ get_affine_transform, the crop (cv2.warpAffine + ToTensor + Normalize), the join
                         share an image (image_index), and the images may be streamed in from a loader (load)
   DeviceAugmentLoader   an iterable over batches.  Per batch the host draws the random numbers of the whole batch in one
                         vectorised call into a pinned staging buffer, copies it to the device and enqueues three kernels
-                        (csrc/data.hip: augment_params, warp_affine_aug, render_targets_w).  There is no loop over samples
+                        (csrc/data.hip: augment_params, warp_affine_aug, render_targets_w; with MODEL.TARGET_TYPE
+                        gaussian_unbiased the third is render_targets_unbiased).  There is no loop over samples
                         and nothing waits for the device.  With world_size > 1 it yields this rank's share of
                         the epoch: partition 'strided' (epoch_order, training and the default) or 'block' (block_range:
                         validation, every row exactly once across the ranks)
@@ -23,7 +24,7 @@ import torch
 from ... import runtime as R
 from ... import synth
 from ..utils.transforms import channel_sources
-from .device_pipeline import gaussian_patch
+from .device_pipeline import gaussian_patch, render_targets_unbiased, unbiased_targets
 
 DRAW_COLUMNS = ('u_half', 'n_half', 'n_scale', 'n_rot', 'u_rot', 'u_flip')
 DEFAULT_CHUNK_BYTES = 256 << 20          # the pinned staging block of a streamed upload
@@ -229,7 +230,8 @@ class DeviceAugmentLoader:
         ds = cfg.DATASET
         self.sf, self.rf, self.flip = float(ds.SCALE_FACTOR), float(ds.ROT_FACTOR), bool(ds.FLIP)
         self.prob_half_body, self.num_joints_half_body = float(ds.PROB_HALF_BODY), int(ds.NUM_JOINTS_HALF_BODY)
-        self.g = torch.from_numpy(np.ascontiguousarray(gaussian_patch(int(cfg.MODEL.SIGMA)), np.float32)).to(db.device)
+        self.sigma, self.unbiased = int(cfg.MODEL.SIGMA), unbiased_targets(cfg)
+        self.g = torch.from_numpy(np.ascontiguousarray(gaussian_patch(self.sigma), np.float32)).to(db.device)
         # a database without a weight table behaves like the reference's joints_weight = 1 (JointsDataset.py:54)
         self.joints_weight = db.joints_weight if cfg.LOSS.USE_DIFFERENT_JOINTS_WEIGHT else None
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
@@ -320,6 +322,9 @@ class DeviceAugmentLoader:
         for k in range(3):
             c.mean[k], c.std[k] = self.mean[k], self.std[k]
         R.check(R.lib().fpd_warp_affine_aug(c, st), 'fpd_warp_affine_aug')
+        if self.unbiased:
+            target, weight = render_targets_unbiased(p['joints'], p['vis'], (hw, hh), (w, h), self.sigma, self.joints_weight)
+            return inp, target, weight, p
         target = torch.empty((b, j, hh, hw), dtype=torch.float32, device=dev)
         weight = torch.empty((b, j, 1), dtype=torch.float32, device=dev)
         t = R.TargetsWT()

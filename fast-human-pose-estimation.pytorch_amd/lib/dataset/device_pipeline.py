@@ -23,10 +23,45 @@ def gaussian_patch(sigma):
     return np.exp(-((x - x0) ** 2 + (y - y0) ** 2) / (2 * sigma ** 2))
 
 
+UNBIASED = 'gaussian_unbiased'
+
+
+def unbiased_targets(cfg):
+    """True when cfg.MODEL.TARGET_TYPE asks for DARK's unbiased encoding; every other value, and a config without the key,
+    keeps the reference's integer-centred patch."""
+    model = cfg.get('MODEL') if hasattr(cfg, 'get') else getattr(cfg, 'MODEL', None)
+    if model is None:
+        return False
+    return (model.get('TARGET_TYPE') if hasattr(model, 'get') else getattr(model, 'TARGET_TYPE', None)) == UNBIASED
+
+
+def render_targets_unbiased(joints, vis, heatmap_size, image_size, sigma, joints_weight=None):
+    """fpd_render_targets_unbiased on device tensors joints [B,J,3] float64 and vis [B,J] float32 (joints_weight [J] float32
+    or None) -> (target [B,J,h,w] fp32, target_weight [B,J,1] fp32)."""
+    b, j = vis.shape
+    w, h = heatmap_size
+    target = torch.empty((b, j, h, w), dtype=torch.float32, device=vis.device)
+    weight = torch.empty((b, j, 1), dtype=torch.float32, device=vis.device)
+    a = R.TargetsUnbiasedT()
+    a.B, a.J, a.H, a.W, a.sigma = b, j, h, w, int(sigma)
+    a.stride_x, a.stride_y = image_size[0] / w, image_size[1] / h
+    a.joints, a.vis, a.target, a.weight = joints.data_ptr(), vis.data_ptr(), target.data_ptr(), weight.data_ptr()
+    if joints_weight is not None:
+        a.joints_weight = joints_weight.data_ptr()
+    R.check(R.lib().fpd_render_targets_unbiased(a, R.current_stream()), 'fpd_render_targets_unbiased')
+    return target, weight
+
+
 class DevicePipeline:
-    def __init__(self, image_size, heatmap_size, sigma, device, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    def __init__(self, image_size, heatmap_size, sigma, device, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                 target_type='gaussian'):
         """image_size / heatmap_size are (w, h) like cfg.MODEL.IMAGE_SIZE / HEATMAP_SIZE; mean/std are the Normalize
-        constants of tools/fpd_train.py:182-184, in the channel order of the images handed to crop()."""
+        constants of tools/fpd_train.py:182-184, in the channel order of the images handed to crop().  target_type
+        'gaussian' (the reference's integer-centred patch) or 'gaussian_unbiased' (DARK's encoding at the real-valued
+        centre, include/fpd_amd.h fpd_targets_unbiased_t)."""
+        if target_type not in ('gaussian', UNBIASED):
+            raise R.FpdError("DevicePipeline: target_type must be 'gaussian' or '%s', got %r" % (UNBIASED, target_type))
+        self.target_type = target_type
         self.image_size, self.heatmap_size, self.sigma = tuple(int(v) for v in image_size), tuple(int(v) for v in heatmap_size), int(sigma)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -40,6 +75,8 @@ class DevicePipeline:
         jt = torch.as_tensor(joints, dtype=torch.float64).to(self.device).contiguous()
         vis = torch.as_tensor(joints_vis, dtype=torch.float32)
         vis = (vis[..., 0] if vis.dim() == 3 else vis).to(self.device).contiguous()
+        if self.target_type == UNBIASED:
+            return render_targets_unbiased(jt, vis, self.heatmap_size, self.image_size, self.sigma)
         b, j = vis.shape
         w, h = self.heatmap_size
         target = torch.empty((b, j, h, w), dtype=torch.float32, device=self.device)

@@ -7,7 +7,9 @@ import numpy as np
 import torch
 import torch.utils.data
 
+from ... import runtime as R
 from ... import synth
+from .device_pipeline import unbiased_targets
 
 MPII_FLIP_PAIRS = [[0, 5], [1, 4], [2, 3], [10, 15], [11, 14], [12, 13]]                                   # mpii.py:27
 COCO_FLIP_PAIRS = [[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]]                  # coco.py:73-74
@@ -17,6 +19,9 @@ class SyntheticPose(torch.utils.data.Dataset):
     POOL = 256          # distinct samples generated up front (one vectorised call); indices wrap around the pool
 
     def __init__(self, cfg, n, seed):
+        if unbiased_targets(cfg):
+            raise R.FpdError("MODEL.TARGET_TYPE gaussian_unbiased needs a loader that renders its targets from joints on the "
+                             'device; the plain `synthetic` set draws finished maps (use DATASET.DATASET synthetic_aug, mpii or coco)')
         self.n, self.seed = n, seed
         self.num_joints = cfg.MODEL.NUM_JOINTS
         self.image_size, self.heatmap_size = tuple(cfg.MODEL.IMAGE_SIZE), tuple(cfg.MODEL.HEATMAP_SIZE)

@@ -208,6 +208,11 @@ class TargetsWT(C.Structure):
     _fields_ = [('t', TargetsT), ('joints_weight', _vp)]
 
 
+class TargetsUnbiasedT(C.Structure):
+    _fields_ = [('B', _i32), ('J', _i32), ('H', _i32), ('W', _i32), ('sigma', _i32), ('_pad', _i32), ('stride_x', _f64),
+                ('stride_y', _f64), ('joints', _vp), ('vis', _vp), ('joints_weight', _vp), ('target', _vp), ('weight', _vp)]
+
+
 class OksNmsT(C.Structure):
     _fields_ = [('P_total', _i32), ('n_img', _i32), ('J', _i32), ('soft', _i32), ('rescore', _i32), ('grid', _i32),
                 ('in_vis_thre', _f64), ('oks_thre', _f64), ('kpts', _vp), ('area', _vp), ('box_score', _vp), ('offsets', _vp),
@@ -284,7 +289,8 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_conv_f8_t': ConvF8T, 'fpd_wquant_entry_t': WquantEntryT, 'fpd_flipmerge_t': FlipMergeT, 'fpd_finalpreds_t': FinalPredsT, 'fpd_targets_t': TargetsT,
             'fpd_warp_src_t': WarpSrcT, 'fpd_warp_t': WarpT, 'fpd_loss_ohkm_t': LossOhkmT, 'fpd_sgd_t': SgdT,
             'fpd_aug_img_t': AugImgT, 'fpd_aug_db_t': AugDbT, 'fpd_aug_crop_t': AugCropT, 'fpd_augment_t': AugmentT,
-            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
+            'fpd_warp_aug_t': WarpAugT, 'fpd_targets_w_t': TargetsWT, 'fpd_targets_unbiased_t': TargetsUnbiasedT,
+            'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
             'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT, 'fpd_dark_t': DarkT,
             'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
             'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT}
@@ -334,6 +340,7 @@ SYMBOLS = {
     'fpd_augment_params': (C.c_int, [C.POINTER(AugmentT), _vp]),
     'fpd_warp_affine_aug': (C.c_int, [C.POINTER(WarpAugT), _vp]),
     'fpd_render_targets_w': (C.c_int, [C.POINTER(TargetsWT), _vp]),
+    'fpd_render_targets_unbiased': (C.c_int, [C.POINTER(TargetsUnbiasedT), _vp]),
     'fpd_oks_nms': (C.c_int, [C.POINTER(OksNmsT), _vp]),
     'fpd_coco_match': (C.c_int, [C.POINTER(CocoMatchT), _vp]),
     'fpd_coco_accumulate': (C.c_int, [C.POINTER(CocoAccumT), _vp]),

@@ -723,6 +723,42 @@ typedef struct {
 } fpd_targets_t;
 int fpd_render_targets(const fpd_targets_t* a, fpd_stream_t stream);
 
+/* DARK's unbiased target encoding (Zhang et al., CVPR 2020: generate_target / adjust_target_weight of the published code):
+ * the Gaussian is evaluated at the real-valued joint position over the whole map, so that a network trained on these
+ * targets predicts sub-pixel peaks, which fpd_dark_refine then recovers.  fpd_render_targets rounds the centre to a pixel
+ * first, and the best decode of such a map is that pixel.
+ *
+ * UNPINNED: the DarkPose source is not available to this project.  The text below is the definition; it restates the
+ * published rule in this project's terms and has not been compared with a run of the authors' code.
+ *
+ * For every (sample b, joint j), tmp = 3 * sigma, all arithmetic in float64 unless noted:
+ *   mu_x = joints[b,j,0] / stride_x, mu_y = joints[b,j,1] / stride_y        one division each, no + 0.5, no rounding
+ *   ulx = (int)(mu_x - tmp), brx = (int)(mu_x + tmp + 1); uly, bry likewise from mu_y.  The cast truncates toward zero like
+ *         Python's int() (so it is not a floor below zero)
+ *   outside = ulx >= W || uly >= H || brx < 0 || bry < 0; a centre that is not finite is outside as well (Python's int()
+ *         raises there)
+ *   w = outside ? 0 : vis[b,j]
+ *   weight[b,j] = w * joints_weight[j] as a float32 product; joints_weight NULL: w (as in fpd_render_targets_w)
+ *   !outside && w > 0.5f: EVERY pixel (x, y) of the H x W map is (float)exp(-((x - mu_x)^2 + (y - mu_y)^2) / (2 sigma^2)),
+ *         evaluated in float64 and rounded once to float32.  There is no patch window.
+ *   otherwise the whole map is +0.0f.
+ * Tolerance of a written value against numpy's float32(exp(float64 expression)), derived, not measured: a float64
+ * evaluation with a relative error below 2^-30 lands within 1 float32 ulp, which covers a direct exp and the separable
+ * product ex[x] * ey[y] of two float64 factors that the kernel forms; where the exact value is below float32's smallest
+ * normal (2^-126) an absolute 2^-126 is allowed (the factors may underflow to zero).  Weights and all-zero maps are exact.
+ * H + W <= 8192 (the row and column factors live in LDS). */
+typedef struct {
+    int32_t B, J, H, W;            /* heat-map shape */
+    int32_t sigma, _pad;           /* >= 1 */
+    double stride_x, stride_y;     /* image_size / heatmap_size */
+    const double* joints;          /* [B,J,3] (x, y, -) in network-input pixels */
+    const float* vis;              /* [B,J] */
+    const float* joints_weight;    /* [J] or NULL */
+    float* target;                 /* [B,J,H,W] */
+    float* weight;                 /* [B,J] */
+} fpd_targets_unbiased_t;
+int fpd_render_targets_unbiased(const fpd_targets_unbiased_t* a, fpd_stream_t stream);
+
 /* The crop of JointsDataset.__getitem__ (:160-168) for a batch: cv2.warpAffine(img, trans, (W,H), INTER_LINEAR)
  * (constant zero border) -> ToTensor (/255, HWC->CHW) -> Normalize(mean, std) (tools/fpd_train.py:182-193), one pass,
  * reading interleaved 8-bit source images that differ in size.  The bilinear sample follows OpenCV's fixed-point scheme

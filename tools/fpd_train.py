@@ -36,6 +36,7 @@ from fpd_amd.lib import models  # noqa: E402,F401
 from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import fpd_train, train, validate  # noqa: E402
 from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa: E402
+from fpd_amd.lib.dataset.device_pipeline import unbiased_targets  # noqa: E402
 from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
 from fpd_amd.lib.core.loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
 from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
@@ -149,6 +150,8 @@ def run(args, normal=False):
     if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii', 'coco'):
         sys.exit('dataset %r is not available here; use DATASET.DATASET synthetic, synthetic_aug, mpii or coco' % cfg.DATASET.DATASET)
     bs = cfg.TRAIN.BATCH_SIZE_PER_GPU
+    if unbiased_targets(cfg):                            # read by the device loaders below, train and validation; `synthetic` raises
+        logger.info('=> targets: MODEL.TARGET_TYPE gaussian_unbiased (Gaussians at the real-valued joint positions)')
     if cfg.DATASET.DATASET == 'mpii':
         # DATASET.ROOT decoded once and resident on every rank's device; each rank augments its rank::world share of the
         # epoch's permutation (lib/dataset/mpii.py); every rank holds and validates its block of the validation set

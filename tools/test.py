@@ -29,6 +29,7 @@ from fpd_amd.lib.config import cfg, update_config  # noqa: E402
 from fpd_amd.lib.core.function import validate  # noqa: E402
 from fpd_amd.lib.core.loss import JointsMSELoss  # noqa: E402
 from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa: E402
+from fpd_amd.lib.dataset.device_pipeline import unbiased_targets  # noqa: E402
 from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
 from fpd_amd.lib.utils.utils import load_checkpoint  # noqa: E402
 
@@ -71,6 +72,8 @@ def main():
 
     if cfg.DATASET.DATASET not in ('synthetic', 'synthetic_aug', 'mpii', 'coco'):
         sys.exit('dataset %r is not available here; use DATASET.DATASET synthetic, synthetic_aug, mpii or coco' % cfg.DATASET.DATASET)
+    if unbiased_targets(cfg):                            # the validation loss is then taken against the unbiased targets; `synthetic` raises
+        logger.info('=> targets: MODEL.TARGET_TYPE gaussian_unbiased (Gaussians at the real-valued joint positions)')
     if cfg.DATASET.DATASET == 'mpii':                    # DATASET.ROOT / TEST_SET, resident on the device; PCKh
         _, valid_loader, valid_set = mpii(cfg, dev, rank, world, train=False)
     elif cfg.DATASET.DATASET == 'coco':                  # DATASET.ROOT / TEST_SET; OKS NMS on the device, keypoint AP
