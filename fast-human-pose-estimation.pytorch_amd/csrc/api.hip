@@ -74,6 +74,9 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c1_launches")) return fpd_conv_c1_option(2, value);      // (read-only: launches served so far)
     if (!strcmp(name, "conv_skip")) return fpd_conv_c1_option(3, value);             // second 1x1 source (fpd_conv_t.x2) offered at all
     if (!strcmp(name, "stem_act")) return fpd_stem_s2d_option(0, value);             // eval-mode BN + ReLU in the stem's epilogue (fpd_stem_t.act)
+    if (!strcmp(name, "stem_blocks")) return fpd_stem_s2d_option(1, value);          // grid / slab cap of the persistent stem kernels (tests: several tiles per block), 0 = none
+    if (!strcmp(name, "stem_s2d_launches")) return fpd_stem_s2d_option(2, value);    // (read-only: forward + weight-gradient launches stem_s2d.hip has served)
+    if (!strcmp(name, "stem_mfma_launches")) return fpd_stem_mfma_launches();        // (read-only: ... stem_mfma.hip has served; neither moved: the direct kernels)
     if (!strcmp(name, "ew_merge")) return fpd_ew_merge_option(value < 0 ? 0 : value);      // BN-backward applies inside the pool backward (fpd_ew_merge_t) offered at all
     if (!strcmp(name, "ew_merge_blocks")) return fpd_ew_merge_blocks_option(value);      // their grid cap (tests: several windows per thread on small tensors)
     if (!strcmp(name, "ew_blocks")) return fpd_ew_blocks_option(value);      // grid cap of the plain elementwise, pair and affsum launches (tests: several trips per thread), 0 = none

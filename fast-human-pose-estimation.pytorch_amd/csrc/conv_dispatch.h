@@ -109,7 +109,9 @@ int fpd_wreduce_launch(const fpd_wreduce_entry_t* table, int n, int64_t max_elem
 // ---- stem ----
 int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st);
 bool fpd_stem_forward_s2d_takes_act(const fpd_stem_t& a);
-int fpd_stem_s2d_option(int which, int value);
+int fpd_stem_s2d_option(int which, int value);      // which: 0 = "stem_act", 1 = "stem_blocks" (return the previous value), 2 = "stem_s2d_launches"
+int fpd_stem_blocks(int dflt);                      // the grid / slab cap of a persistent stem launch whose own cap is dflt ("stem_blocks")
+int fpd_stem_mfma_launches();                       // "stem_mfma_launches"
 int fpd_stem_wgrad_s2d_partials(const fpd_stem_t& a);
 int fpd_stem_wgrad_s2d_launch(const fpd_stem_t& a, hipStream_t st);
 int fpd_stem_forward_mfma_launch(const fpd_stem_t& a, hipStream_t st);

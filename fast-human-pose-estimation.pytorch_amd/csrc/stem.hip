@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -160,15 +161,18 @@ int fpd_stem_forward_launch(const fpd_stem_t& a, hipStream_t st) {
     return 0;
 }
 
+// slabs of the weight gradient = its grid when it writes slabs: the query and the launch both ask here
+static int stem_wgrad_blocks(const fpd_stem_t& a) { return std::max(1, std::min(a.N * cdiv(a.P, TH) * cdiv(a.Q, TW), fpd_stem_blocks(1024))); }
+
 int fpd_stem_wgrad_partials(const fpd_stem_t& a) {
     if (a.K > KMAX || 256 % a.K != 0) return 0;
-    return std::min(a.N * cdiv(a.P, TH) * cdiv(a.Q, TW), 1024);
+    return stem_wgrad_blocks(a);
 }
 
 int fpd_stem_wgrad_launch(const fpd_stem_t& a, hipStream_t st) {
     if (a.K > KMAX || 256 % a.K != 0) return fpd_fail(-3, "stem wgrad: K=%d must divide 256 and be <= %d", a.K, KMAX);
     const int tiles = a.N * cdiv(a.P, TH) * cdiv(a.Q, TW);
-    const int grid = a.partial != nullptr ? std::min(tiles, 1024) : 1;
+    const int grid = a.partial != nullptr ? stem_wgrad_blocks(a) : 1;
     if (a.dtype == FPD_BF16)
         FPD_LAUNCH((stem_wgrad_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, a, tiles);
     else

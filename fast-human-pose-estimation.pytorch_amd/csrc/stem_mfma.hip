@@ -6,8 +6,10 @@
 //   wgrad   : dW[k][tap]  += dy[pixel][k]^T A[pixel][tap]   both operands through the transposing LDS read
 // fp32 builds keep the direct kernels of stem.hip.
 #include <algorithm>
+#include <atomic>
 
 #include "common.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "mfma_frag.h"
 
@@ -266,6 +268,12 @@ static bool stem_mfma_ok(const fpd_stem_t& a, int& logQ) {
     return true;
 }
 
+static std::atomic<int> g_mfma_launches{0};              // forward + weight-gradient launches these kernels have served ("stem_mfma_launches")
+int fpd_stem_mfma_launches() { return g_mfma_launches.load(std::memory_order_relaxed); }
+
+// slabs of the weight gradient = its grid when it writes slabs: the query and the launch both ask here
+static int mfma_wgrad_blocks(const fpd_stem_t& a) { return std::max(1, std::min(a.N * a.P * a.Q / 128, fpd_stem_blocks(512))); }
+
 // return 1 = not applicable (caller uses the direct kernels)
 int fpd_stem_forward_mfma_launch(const fpd_stem_t& a, hipStream_t st) {
     int logQ;
@@ -282,13 +290,14 @@ int fpd_stem_forward_mfma_launch(const fpd_stem_t& a, hipStream_t st) {
         if (int rc_ = cfg2.ensure(reinterpret_cast<const void*>(&stem_fwd_mfma_kernel<2>), lds)) return rc_;
         FPD_LAUNCH((stem_fwd_mfma_kernel<2>), dim3(tiles), dim3(256), lds, st, a, logQ);
     }
+    g_mfma_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
 
 int fpd_stem_wgrad_mfma_partials(const fpd_stem_t& a) {
     int logQ;
     if (!stem_mfma_ok(a, logQ)) return 0;
-    return std::min(a.N * a.P * a.Q / 128, 512);
+    return mfma_wgrad_blocks(a);
 }
 
 int fpd_stem_wgrad_mfma_launch(const fpd_stem_t& a, hipStream_t st) {
@@ -297,7 +306,7 @@ int fpd_stem_wgrad_mfma_launch(const fpd_stem_t& a, hipStream_t st) {
     const int kmax = a.K <= 32 ? 32 : 64;
     const size_t lds = (size_t)128 * LDA * sizeof(bf16_t) + (size_t)128 * (kmax + 8) * sizeof(bf16_t) + patch_bytes(logQ);
     const int tiles = a.N * a.P * a.Q / 128;
-    const dim3 grid(a.partial != nullptr ? std::min(tiles, 512) : 1);
+    const dim3 grid(a.partial != nullptr ? mfma_wgrad_blocks(a) : 1);
     static LdsAttr cfg32, cfg64;        // per device, set once (thread-safe: common.h)
     if (kmax == 32) {
         if (int rc_ = cfg32.ensure(reinterpret_cast<const void*>(&stem_wgrad_mfma_kernel<32>), lds)) return rc_;
@@ -306,5 +315,6 @@ int fpd_stem_wgrad_mfma_launch(const fpd_stem_t& a, hipStream_t st) {
         if (int rc_ = cfg64.ensure(reinterpret_cast<const void*>(&stem_wgrad_mfma_kernel<64>), lds)) return rc_;
         FPD_LAUNCH((stem_wgrad_mfma_kernel<64>), grid, dim3(256), lds, st, a, logQ, tiles);
     }
+    g_mfma_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }

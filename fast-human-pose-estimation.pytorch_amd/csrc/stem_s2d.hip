@@ -19,6 +19,7 @@
 // (r05 stamps of the first version, which went through the shared LDS-staged epilogue with a statistics flush per tile: 6 k of
 // a tile's 10 k cycles were epilogue, and the block's 30 k-cycle prologue was a chain of dependent weight loads).
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "common.h"
@@ -489,8 +490,19 @@ static int stem_act_mode() {
     if (g_stem_act < 0) { const char* e = getenv("FPD_STEM_ACT"); g_stem_act = e ? atoi(e) : 1; }
     return g_stem_act;
 }
-int fpd_stem_s2d_option(int which, int value) {
-    (void)which;
+// "stem_blocks" (tests): n >= 1: no persistent stem launch -- the forward here, the three weight gradients here, in stem_mfma.hip and
+// in stem.hip -- gets more than n blocks (and writes more than n slabs), so that a block owns several tiles on a small tensor;
+// 0 = the per-kernel defaults alone.  fpd_stem_blocks(dflt) is the one place that applies it: queries and launches both call it.
+static int g_stem_blocks = 0;
+static std::atomic<int> g_s2d_launches{0};               // forward + weight-gradient launches these kernels have served ("stem_s2d_launches")
+int fpd_stem_blocks(int dflt) { return g_stem_blocks > 0 ? std::min(g_stem_blocks, dflt) : dflt; }
+int fpd_stem_s2d_option(int which, int value) {          // which: 0 = act offered, 1 = blocks (returns the previous value), 2 = launches served so far
+    if (which == 2) return g_s2d_launches.load(std::memory_order_relaxed);
+    if (which == 1) {
+        const int prev = g_stem_blocks;
+        if (value >= 0) g_stem_blocks = value;
+        return prev;
+    }
     const int prev = stem_act_mode();
     g_stem_act = value;
     return prev;
@@ -521,9 +533,8 @@ int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st) {
     const size_t lds = std::max((size_t)ring * (a.Q + 3) * S2_PIXB + (size_t)32 * TN * S2_WROW + (act ? (size_t)2 * 32 * TN * sizeof(float) : 0),
                                 (size_t)4 * 32 * TN * 2 * (33 * sizeof(float) + sizeof(double)));      // tiles (+ scale / shift) | block-end statistics transposition
     const int tiles = a.N * a.P * a.Q / 128;
-    static const int cap = 0;        // (0 = the per-K defaults below; the FPD_STEM_BLOCKS knob of round 5 is gone)
     // K = 32: two blocks per CU (35.6 us at 512 blocks, 47.6 at 256, 44.1 at 1024); K = 64: 62.2 us at 256, 71.8 at 512 (r05, one box)
-    const int blocks = std::max(1, std::min(tiles, cap > 0 ? cap : (TN == 1 ? 512 : 256)));
+    const int blocks = std::max(1, std::min(tiles, fpd_stem_blocks(TN == 1 ? 512 : 256)));
     static LdsAttr cfg1, cfg2, cfg1a, cfg2a;
     if (TN == 1 && !act) {
         if (int rc_ = cfg1.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<1, false>), lds)) return rc_;
@@ -538,6 +549,7 @@ int fpd_stem_forward_s2d_launch(const fpd_stem_t& a, hipStream_t st) {
         if (int rc_ = cfg2a.ensure(reinterpret_cast<const void*>(&stem_s2d_fwd_kernel<2, true>), lds)) return rc_;
         FPD_LAUNCH((stem_s2d_fwd_kernel<2, true>), dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
     }
+    g_s2d_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
 
@@ -548,8 +560,7 @@ static bool s2d_wgrad_ok(const fpd_stem_t& a, int& logQ, int& blocks) {
     while ((1 << logQ) < a.Q) ++logQ;
     if (a.P % (128 >> logQ) != 0) return false;
     const int tiles = a.N * a.P * a.Q / 128;
-    static const int cap = 256;      // (= its slab count: 41.6 us; 128 / 512 blocks 67.4 / 52.5 us, round 5)
-    blocks = std::max(1, std::min(tiles, cap));
+    blocks = std::max(1, std::min(tiles, fpd_stem_blocks(256)));      // (256 = its slab count: 41.6 us; 128 / 512 blocks 67.4 / 52.5 us, round 5)
     return true;
 }
 
@@ -569,5 +580,6 @@ int fpd_stem_wgrad_s2d_launch(const fpd_stem_t& a, hipStream_t st) {
     static LdsAttr cfg;
     if (int rc_ = cfg.ensure(reinterpret_cast<const void*>(&stem_s2d_wgrad_kernel), lds)) return rc_;
     FPD_LAUNCH(stem_s2d_wgrad_kernel, dim3(blocks), dim3(256), lds, st, a, logQ, tiles);
+    g_s2d_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }

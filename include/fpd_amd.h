@@ -1004,7 +1004,13 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * the same for fpd_ew_merge_supported() / fpd_ew_merge() (default 1, or what FPD_EW_MERGE says); "ew_merge_blocks" = grid cap of those launches (default 2048, any
  * n >= 1); "ew_blocks" = n >= 1: no fpd_elementwise() launch, neither half of an fpd_elementwise_pair() launch and no fpd_affsum() launch
  * gets more than n blocks, so that a thread walks several pixels on a small tensor (tests); 0 = the library's own grid rule alone
- * (default); a negative value changes nothing.  Returns the
+ * (default); a negative value changes nothing; "stem_blocks" = n >= 1: no persistent stem launch -- the space-to-depth forward
+ * and the three weight gradients of fpd_stem_wgrad() -- gets more than n blocks, and fpd_stem_wgrad_num_partials() answers
+ * accordingly, so that a block owns several tiles on a small image (tests); 0 = the kernels' own grids alone (default), a negative
+ * value changes nothing; a launch without slabs (partial == NULL) keeps its single block; "stem_s2d_launches" /
+ * "stem_mfma_launches" = read-only (the value is ignored): fpd_stem_forward() + fpd_stem_wgrad() launches served so far by the
+ * space-to-depth kernels (csrc/stem_s2d.hip) / the im2col kernels (csrc/stem_mfma.hip); a stem launch that moves neither was
+ * served by the direct kernels (csrc/stem.hip).  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */
 int fpd_set_option(const char* name, int32_t value);
 int fpd_abi_sizeof(const char* struct_name);  /* sizeof of a struct above, -1 if unknown */

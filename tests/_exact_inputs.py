@@ -1,5 +1,5 @@
-"""Input constructions, op lists and case lists of the bit-exact tests of the streaming kernels (tests/test_exact_stream_gpu.py
-on the device, tests/test_exact_inputs_cpu.py for the preconditions).  No device is needed to import or use this module.
+"""Input constructions, op lists and case lists of the bit-exact tests of the streaming kernels and of the stem
+(tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py on the device, tests/test_exact_inputs_cpu.py for the preconditions).  No device is needed to import or use this module.
 
 Everything here is a small dyadic rational, chosen so that the specification (oracle/plan_interp.py) is EXACT: a kernel that
 groups its partial sums differently, folds its coefficients in another order or rounds an fp32 accumulator to bf16 once must
@@ -28,7 +28,17 @@ free draw), not by the large dense forward cases, which are there for the tiles,
 check_reference() asserts, ON THE INTERPRETER'S RESULT, the headroom that makes every fp32 sum exact in any grouping (sum of
 |addend| in units of the common power of two below 2^24, per channel / element over the whole tensor), that no output is
 degenerate, that every ReLU mask keeps 10-90 % and that more than 1 % of every normalised tensor sits exactly ON the mask
-boundary (x*scale + shift == 0: `>` against `>=` is visible)."""
+boundary (x*scale + shift == 0: `>` against `>=` is visible).
+
+The stem (Conv2d(3, K, 7, stride 2, pad 3) on the fp32 NCHW image; tests/test_exact_stem_gpu.py): image, weights, bias and dy are
+drawn from the same sets, so EVERY value is bf16-representable -- on purpose.  In a bf16 build the direct kernels (csrc/stem.hip)
+multiply the unrounded fp32 image and weights, while the space-to-depth and im2col kernels (csrc/stem_s2d.hip,
+csrc/stem_mfma.hip) and the interpreter round both to bf16 first; on these inputs the rounding changes nothing and all three
+back ends share ONE specification.  (That difference is not touched here.)  The frozen stem's bn1 + ReLU ('act') is an
+eval-mode BN with running_var = 1 - 1e-5 -- invstd == 1.0f, scale == gamma, shift == beta - mean*gamma, the cancellation rule
+of exact_bn() -- and one channel in 16 has all-zero weights, zero bias and zero shift: every pixel of it sits ON the ReLU
+boundary.  The s2d forward keeps its statistics per lane in fp32, SHIFTED by the channel's bias: check_reference() asserts the
+headroom of those sums (|y - bias|, (y - bias)^2) beside the plain ones."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -293,6 +303,63 @@ def pair(bt, gen, dims, wmode, use_bn, epi):
     return b
 
 
+def stem_dims(N, H, W, K):
+    return N, H, W, K, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def exact_eval_bn(bt, gen, C, name='bn1'):
+    """-> (graph.BN in eval mode with ReLU, dict of the exact per-channel fp64 values, `on`: the channels with shift == 0).
+    running_var = 1 - 1e-5 (in fp32: 1 - 168 * 2^-24): invstd rounds to 1.0f.  The draw and the cancellation rule of exact_bn()."""
+    mu, gamma, beta = pick(gen, MU, C), pick(gen, GAMMA, C), pick(gen, BETA, C)
+    on = torch.randperm(C, generator=gen)[:max(1, C // 16)]
+    mu[on], beta[on] = 0.0, 0.0
+    cancel = (mu != 0) & (beta == mu * gamma)
+    beta = torch.where(cancel, -beta, beta)
+    bn = G.BN(name, 'eval', C, bt.buf('param', (C,), gamma.float()), bt.buf('param', (C,), beta.float()),
+              bt.buf('rstat', (C,), mu.float()), bt.buf('rstat', (C,), torch.full((C,), 1.0 - 1e-5)), bt.buf('nbt', ()), relu=True)
+    return bn, dict(mu=mu, gamma=gamma, beta=beta, shift=beta - mu * gamma), on
+
+
+def stem(bt, gen, dims, wmode, stats, act=False):
+    """The stem's forward on the fp32 NCHW image: y (+ output statistics), or -- act -- behind it the eval-mode bn1 + ReLU that
+    the frozen network's launch applies in its epilogue (graph: stem_fwd.act_ew); compared is then the activation alone."""
+    N, H, W, K, P, Q = dims
+    b = Built()
+    wv, bv = weights(gen, wmode, K, 7, 3), small(gen, K)
+    img = bt.buf('image', (N, 3, H, W), small(gen, N, 3, H, W))
+    y = bt.act((N, P, Q, K), None, 'stem')
+    st = bt.buf('stats', (RS, 2, K), torch.zeros(RS, 2, K, dtype=torch.float64)) if stats else None
+    if act:
+        bn, ex, on = exact_eval_bn(bt, gen, K)
+        wv[on], bv[on] = 0.0, 0.0                         # y == 0 and shift == 0: the whole channel sits on the ReLU boundary
+        bn.count = N * P * Q
+        b.h['act'] = ex
+    op = G.Op('stem_fwd', image=img, w=bt.buf('param', (K, 7, 7, 3), wv), bias=bt.buf('param', (K,), bv), y=y, out_stats=st, dims=dims)
+    b.ops.append(op)
+    if act:
+        a = bt.act((N, P, Q, K), None, 'stem_act')
+        op.act_ew = G.Op('ew', op='bnrelu_fwd', dims=(N, P, Q, K), y=a, out_stats=None, x=y, x2=None, dy=None, add=None, bstats=None,
+                         dgamma=None, dbeta=None, bn=bn)
+        b.ops.append(op.act_ew)
+        b.compare += [('stem act', a)]
+    else:
+        b.compare += [('y', y)] + ([('out_stats', st)] if stats else [])
+    b.h['stem'] = op
+    return b
+
+
+def stem_weight_gradient(bt, gen, dims):
+    N, H, W, K, P, Q = dims
+    b = Built()
+    img = bt.buf('image', (N, 3, H, W), small(gen, N, 3, H, W))
+    dy = bt.act((N, P, Q, K), small(gen, N, P, Q, K, density=0.3), 'dy')
+    dw, db = bt.buf('grad', (K, 7, 7, 3), torch.zeros(K, 7, 7, 3)), bt.buf('grad', (K,), torch.zeros(K))
+    b.ops.append(G.Op('stem_wgrad', image=img, dy=dy, dw=dw, dbias=db, dims=dims))
+    b.compare += [('dw', dw), ('dbias', db)]
+    b.h['stem'] = b.ops[0]
+    return b
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the checks on the reference
 def quantum(t):
@@ -378,6 +445,62 @@ def _check_apply(A, b, op, label):
     assert not bool(((ex['mu'] * m2 - m1 == 0) & (m1 != 0)).any()), label + ': mu*m2 - m1 cancels'
 
 
+def _stem_operands(A, op, label):
+    img, wt = A.view(op.image), (A.view(op.w) if op.kind == 'stem_fwd' else None)
+    for t in (img, wt):                                   # one specification for the rounding and the non-rounding back ends
+        assert t is None or torch.equal(t.bfloat16().float(), t), label + ': an operand is not bf16-representable'
+    return img.double(), (wt.permute(0, 3, 1, 2).double() if wt is not None else None)
+
+
+def _check_stem(A, b, op, label):
+    N, H, W, K, P, Q = op.dims
+    img, wt = _stem_operands(A, op, label)
+    bias = A.view(op.bias).double()
+    acc = F.conv2d(img.abs(), wt.abs(), None, stride=2, padding=3) + bias.abs().view(1, K, 1, 1)
+    _headroom(acc, min(quantum(img) * quantum(wt), quantum(bias)), label + ' accumulator')
+    y = PI._act(A, op.y).double()
+    assert float(y.abs().max()) > 0, label + ': all-zero output'
+    if op.out_stats is not None:
+        d = y - bias                                      # what the space-to-depth kernel adds up per lane, in fp32
+        qy, qd = quantum(y), min(quantum(y), quantum(bias))
+        _headroom(y.abs().sum((0, 1, 2)), qy, label + ' sum y')
+        _headroom((y * y).sum((0, 1, 2)), qy * qy, label + ' sum y*y')
+        _headroom(d.abs().sum((0, 1, 2)), qd, label + ' sum (y - bias)')
+        _headroom((d * d).sum((0, 1, 2)), qd * qd, label + ' sum (y - bias)^2')
+        st = A.view(op.out_stats).sum(0)
+        assert float(st[0].abs().max()) > 0 and float(st[1].abs().max()) > 0, label + ': all-zero statistics'
+    ae = op.act_ew
+    if ae is None:
+        return
+    ex, bn = b.h['act'], ae.bn
+    assert not bool(((ex['shift'] == 0) & (ex['mu'] != 0)).any()), label + ': beta - mean*gamma cancels'
+    scale, shift, mean, invstd = PI._bn_coef(A, bn)
+    assert torch.equal(scale.double(), ex['gamma']) and torch.equal(shift.double(), ex['shift']), label + ': scale / shift not exact'
+    assert torch.equal(mean.double(), ex['mu']) and bool((invstd == 1.0).all()), label + ': mean / invstd not exact'
+    # the device's arithmetic (csrc/common.h bn_resolve, eval mode): fp32 running estimates, eps = (double)(float)1e-5
+    inv = 1.0 / torch.sqrt(A.view(bn.rvar).double() + EPS_DEVICE)
+    g = A.view(bn.gamma).double()
+    assert torch.equal((g * inv).float().double(), ex['gamma']), label + ': device scale not exact'
+    assert torch.equal((A.view(bn.beta).double() - A.view(bn.rmean).double() * g * inv).float().double(), ex['shift']), label + ': device shift not exact'
+    z = torch.addcmul(shift, PI._act(A, op.y), scale)
+    on, keep = float((z == 0).float().mean()), float((z > 0).float().mean())
+    assert on > 0.01, '%s: only %.2f %% of the elements sit on the mask boundary' % (label, 100 * on)
+    assert 0.1 <= keep <= 0.9, '%s: the ReLU mask keeps %.1f %%' % (label, 100 * keep)
+    dead = (ex['shift'] == 0) & (A.view(op.w).abs().sum((1, 2, 3)) == 0) & (A.view(op.bias) == 0)
+    assert bool(dead.any()) and bool((z[..., dead] == 0).all()), label + ': no channel lies on the boundary as a whole'
+    assert float(PI._act(A, ae.y).abs().max()) > 0, label + ': all-zero activation'
+
+
+def _check_stem_wgrad(A, b, op, label):
+    N, H, W, K, P, Q = op.dims
+    img, _ = _stem_operands(A, op, label)
+    dy = _nchw(PI._act(A, op.dy).double())
+    tot = torch.nn.grad.conv2d_weight(img.abs(), (K, 3, 7, 7), dy.abs(), stride=2, padding=3)
+    _headroom(tot, quantum(img) * quantum(dy), label + ' dw')
+    _headroom(dy.abs().sum((0, 2, 3)), quantum(dy), label + ' dbias')
+    assert float(A.view(op.dw).abs().max()) > 0 and float(A.view(op.dbias).abs().max()) > 0, label + ': all-zero gradient'
+
+
 def check_reference(A, b, label=''):
     """The preconditions of a bit-exact comparison, asserted on the arenas the interpreter has run `b.ops` over."""
     for ex in b.bns.values():
@@ -388,7 +511,11 @@ def check_reference(A, b, label=''):
                 _check_conv(A, b, o, label + ' conv')
             elif o.kind == 'wgrad':
                 _check_wgrad(A, b, o, label + ' wgrad')
-            elif o.kind == 'ew':
+            elif o.kind == 'stem_fwd':                    # (with its act_ew, the 'ew' op behind it)
+                _check_stem(A, b, o, label + ' stem')
+            elif o.kind == 'stem_wgrad':
+                _check_stem_wgrad(A, b, o, label + ' stem wgrad')
+            elif o.kind == 'ew' and o.op == 'bn_bwd_apply':
                 _check_apply(A, b, o, label + ' apply')
 
 
@@ -429,6 +556,44 @@ PP_FWD = [_cap(c[0], c[1], c[2], max(c[3], c[4])) + (c[3], c[4], c[5], c[6] is n
 # ... data gradient with fold and fused weight gradient: two 1x1 rows of FOLD_CASES.  (N, H, W, C, K, blocks)
 PP_BWD = [c[:5] + (c[6],) for c in _tk.FOLD_CASES if c in ((3, 20, 48, 64, 32, 1, 3, True), (2, 32, 32, 128, 64, 1, 4, True))]
 assert (len(PP_BWD), len(C1_PAIR), len(C3_FWD), len(C3_BWD), len(PP_FWD)) == (2, 4, 8, 5, 12), 'a case list this module derives from has changed'
+
+
+# the stem: (N, H, W, K, blocks) with P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1; at most 4096 output pixels.  blocks = the
+# "stem_blocks" option of the launch (0: the kernels' defaults); tiles are 128 output pixels = 128 / Q whole rows
+def _even(N, P, Q, K, blocks):
+    return N, 2 * P, 2 * Q, K, blocks
+
+
+# space-to-depth kernels (bf16, H = 2P, W = 2Q, Q a power of two in 16..128):
+STEM_S2D = [
+    _even(2, 8, 16, 8, 1),         # two images, one tile each, one block: full reload at the image change; smallest K
+    _even(1, 24, 16, 24, 1),       # three continuing tiles: the 19-row ring wraps; weight rows beyond K zeroed
+    _even(3, 16, 16, 32, 2),       # 6 tiles split 3 / 3: the second block starts in the middle of an image (its halo above is real rows)
+    _even(2, 8, 32, 32, 3),        # 4 tiles over 3 blocks (uneven fpd_cut)
+    _even(1, 12, 32, 40, 1),       # two channel tiles, the second half-live
+    _even(2, 6, 64, 64, 2),        # 6 tiles over 2 blocks, Q = 64
+    _even(2, 3, 128, 64, 1),       # one row per tile: a ring of 5 that wraps every tile
+    _even(1, 5, 128, 16, 7),       # cap above the tile count
+    _even(2, 8, 16, 32, 0),        # the default grid
+]
+STEM_ACT = [c for c in STEM_S2D if c[3] in (8, 32, 40, 64)]
+# the same (P, Q) with an odd size: the space-to-depth form declines, the im2col kernels (csrc/stem_mfma.hip) serve
+STEM_MFMA = [(2, 15, 32, 8, 0), (1, 32, 63, 32, 0), (2, 7, 127, 40, 0), (1, 5, 255, 64, 0), (2, 15, 63, 64, 0)]
+# direct kernels (csrc/stem.hip; 8 x 16 tiles): (N, H, W, K, dtype, backend) -- tiles ragged in both directions with an odd K;
+# Q = 24; Q = 96 with P = 9; each in both storage types; a space-to-depth shape in fp32 and under the direct back end
+STEM_DIRECT = [c + (dt, 0) for c in ((2, 21, 37, 5), (1, 16, 48, 16), (1, 18, 192, 64)) for dt in (1, 0)] + [
+    (2, 16, 32, 32, 0, 0), (2, 16, 32, 32, 1, 1)]
+# weight gradient: (N, H, W, K, blocks, dtype); blocks = the cap of the third mode of the device test (an uneven split of the
+# tiles wherever there are more than two).  space-to-depth: K <= 32; im2col <32>: the odd shapes with K <= 32; im2col <64>:
+# K = 40 and 64, even and odd sizes; direct (K divides 256): Q in {24, 96} and fp32
+STEM_WGRAD_S2D = [_even(2, 8, 16, 8, 1), _even(1, 24, 16, 24, 2), _even(3, 16, 16, 32, 4), _even(2, 8, 32, 32, 3), _even(1, 5, 128, 16, 2),
+                  _even(2, 8, 16, 32, 1)]
+STEM_WGRAD_MFMA = [(2, 15, 32, 8, 1), (1, 32, 63, 32, 3), _even(1, 12, 32, 40, 2), _even(2, 6, 64, 64, 4), _even(2, 3, 128, 64, 4),
+                   (2, 7, 127, 40, 3)]
+STEM_WGRAD_DIRECT = [(1, 16, 48, 16, 1, 1), (1, 16, 48, 16, 1, 0), (3, 16, 48, 16, 4, 1), (1, 18, 192, 64, 5, 1), (1, 18, 192, 64, 5, 0),
+                     (2, 16, 32, 8, 1, 0)]
+STEM_WGRAD = [c + (1,) for c in STEM_WGRAD_S2D + STEM_WGRAD_MFMA] + STEM_WGRAD_DIRECT
+assert all(c[0] * stem_dims(*c[:4])[4] * stem_dims(*c[:4])[5] <= 4096 for c in STEM_S2D + STEM_MFMA + STEM_DIRECT + STEM_WGRAD)
 
 
 def seed(*parts):
@@ -479,6 +644,20 @@ def pp_dgrad(bt, case, wmode):
     return dgrad(bt, seed('ppb', case, wmode), case[:5] + (1,), wmode, True, True)
 
 
+def stem_forward(bt, case, wmode, stats):
+    return stem(bt, seed('stf', case[:4], wmode, stats), stem_dims(*case[:4]), wmode, stats)
+
+
+def stem_act(bt, case, wmode):
+    return stem(bt, seed('sta', case[:4], wmode), stem_dims(*case[:4]), wmode, False, act=True)
+
+
+def stem_wgrad(bt, case):
+    return stem_weight_gradient(bt, seed('stw', case[:4]), stem_dims(*case[:4]))
+
+
+_STEM_FWD = STEM_S2D + STEM_MFMA + sorted({c[:4] + (0,) for c in STEM_DIRECT} - set(STEM_S2D))
+_STEM_WG = sorted({c[:4] for c in STEM_WGRAD})
 FAMILIES = [
     (c1_forward, [(c, m, v) for c in C1_FWD for m in WMODES for v in C1_FWD_VARIANTS]),
     (c1_dgrad, [(c, m, fo, fu) for c in C1_BWD for m in WMODES for fo in (False, True) for fu in (False, True)]),
@@ -489,4 +668,7 @@ FAMILIES = [
     (c3_pair, [(c, m) for c in C3_PAIR for m in WMODES]),
     (pp_forward, [(c, m) for c in PP_FWD for m in WMODES]),
     (pp_dgrad, [(c, m) for c in PP_BWD for m in WMODES]),
+    (stem_forward, [(c, m, s) for c in _STEM_FWD for m in WMODES for s in (True, False)]),
+    (stem_act, [(c, m) for c in STEM_ACT for m in WMODES]),
+    (stem_wgrad, [(c,) for c in _STEM_WG]),
 ]

@@ -189,6 +189,38 @@ def test_host_side_dispatch_predicates_of_round_3_without_a_device(runtime):
         assert lib.fpd_set_option(name, prev) == default
 
 
+def test_stem_blocks_option_and_slab_queries_without_a_device(runtime):
+    """fpd_set_option("stem_blocks"): 0 (the default) leaves every slab count of the stem's weight gradient as it was -- 256
+    space-to-depth, 512 im2col, 1024 direct at most, one per tile below that --, n >= 1 caps all three; the launch counters are
+    read-only."""
+    import ctypes
+    R, lib = runtime, runtime.lib()
+
+    def slabs(N, H, W, K, dtype=R.BF16):
+        s = R.StemT()
+        s.N, s.H, s.W, s.K, s.P, s.Q, s.dtype = N, H, W, K, (H - 1) // 2 + 1, (W - 1) // 2 + 1, dtype
+        return lib.fpd_stem_wgrad_num_partials(ctypes.byref(s))
+    # (the student's stem, an odd width of it, a K the space-to-depth form declines, a non-power-of-two width, fp32, few tiles)
+    shapes = [((32, 256, 256, 32), 256), ((32, 256, 255, 32), 512), ((32, 256, 256, 64), 512), ((32, 256, 192, 64), 1024),
+              ((32, 256, 256, 32, R.F32), 1024), ((1, 48, 32, 24), 3), ((1, 32, 63, 32), 4), ((1, 18, 192, 64), 12)]
+    for name in (b'stem_s2d_launches', b'stem_mfma_launches'):
+        n = lib.fpd_set_option(name, 0)
+        assert n >= 0 and lib.fpd_set_option(name, n + 5) == n and lib.fpd_set_option(name, 0) == n
+    for args, want in shapes:
+        assert slabs(*args) == want, (args, slabs(*args))
+    assert lib.fpd_set_option(b'stem_blocks', 2) == 0
+    try:
+        for args, want in shapes:
+            assert slabs(*args) == 2, (args, slabs(*args))
+        assert lib.fpd_set_option(b'stem_blocks', 7) == 2 and lib.fpd_set_option(b'stem_blocks', -1) == 7      # negative: unchanged
+        for args, want in shapes:
+            assert slabs(*args) == min(want, 7), (args, slabs(*args))
+    finally:
+        lib.fpd_set_option(b'stem_blocks', 0)
+    for args, want in shapes:
+        assert slabs(*args) == want
+
+
 def test_exact_statistics_encoding_round_trip_and_order_independence():
     """include/fpd_amd.h fpd_stat_t as the host sees it (executor.Arenas.stats_write / stats_read on CPU tensors): a value
     travels as two 64-bit integer limbs, hi = rint(v * 2^20) and lo = rint((v - hi * 2^-20) * 2^60); the split is exact to
