@@ -683,6 +683,16 @@ int fpd_loss(const fpd_loss_t* a, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+int fpd_loss_geometry(const fpd_loss_t* a, int32_t* vectorised, int32_t* blocks, int32_t* tiles_per_block) {
+    FPD_REQUIRE(a && vectorised && blocks && tiles_per_block, "loss_geometry: null pointer");
+    FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0, "loss_geometry: non-positive dimension");
+    int v = 0, b = 0, t = 0;
+    const int rc = fpd_loss_geometry_of(*a, &v, &b, &t);
+    if (rc) return rc;
+    *vectorised = v; *blocks = b; *tiles_per_block = t;
+    return 0;
+}
+
 static int validate_loss_dims(const fpd_loss_t* a, const char* what) {
     FPD_REQUIRE(a, "%s: null pointer", what);
     FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0, "%s: non-positive dimension", what);

@@ -162,6 +162,7 @@ int fpd_ew_merge_option(int value);      // >= 0: set; returns the previous valu
 int fpd_ew_merge_blocks_option(int value);      // >= 1: set the grid cap of the merged launches; returns the previous value
 int fpd_ew_blocks_option(int value);      // >= 1: grid cap of fpd_elementwise_launch (each half of a pair launch) and fpd_affsum_launch, 0: none (default); returns the previous value
 int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st);
+int fpd_loss_geometry_of(const fpd_loss_t& a, int* vectorised, int* blocks, int* tiles_per_block);      // the kernel and grid of that launch
 int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& a, hipStream_t st);      // csrc/loss_ohkm.hip: two launches
 int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a);
 int fpd_loss_kl_launch(const fpd_loss_kl_t& a, hipStream_t st);          // csrc/loss_kl.hip: two launches

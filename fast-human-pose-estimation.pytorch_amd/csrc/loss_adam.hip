@@ -300,28 +300,43 @@ inline int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64
 
 }  // namespace
 
-int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st) {
+// Which kernel fpd_loss_launch() runs for `a` as it stands (dimensions, dtype, pointer alignments), and its grid: the launch
+// below and the query fpd_loss_geometry() both come through here.
+int fpd_loss_geometry_of(const fpd_loss_t& a, int* vectorised, int* blocks, int* tiles_per_block) {
     if (a.J > 32 || a.S > FPD_MAX_STACKS || a.S < 1) return fpd_fail(-3, "loss: J=%d (<=32), S=%d (1..%d)", a.J, a.S, FPD_MAX_STACKS);
     const int vec = a.dtype == FPD_BF16 ? 8 : 4;
     bool aligned = a.J % vec == 0 && ((uintptr_t)a.teacher & 15) == 0;
     for (int s = 0; s < a.S; ++s) aligned = aligned && ((uintptr_t)a.out[s] & 15) == 0 && ((uintptr_t)a.dout[s] & 15) == 0;
+    *vectorised = aligned ? 1 : 0;
     if (aligned) {                               // 16-byte vectors of joints (the benchmark's J = 16)
         // <= 256 blocks (= 512 same-address atomics), tiles of one image per block
         const int tpi = cdiv(a.H * a.W, 128);
         int tpb = 1;
         while (a.B * cdiv(tpi, tpb) > 256 && tpb < tpi) ++tpb;
-        const int vt = a.B * cdiv(tpi, tpb);
-        if (a.dtype == FPD_BF16)
-            FPD_LAUNCH((loss_vec_kernel<bf16_t>), dim3(vt), dim3(256), 0, st, a, tpb);
-        else
-            FPD_LAUNCH((loss_vec_kernel<float>), dim3(vt), dim3(256), 0, st, a, tpb);
+        *tiles_per_block = tpb;
+        *blocks = a.B * cdiv(tpi, tpb);
         return 0;
     }
-    const int tiles = a.B * cdiv(a.H * a.W, 64);
+    *tiles_per_block = 1;                        // a block per 64-pixel tile
+    *blocks = a.B * cdiv(a.H * a.W, 64);
+    return 0;
+}
+
+int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st) {
+    int vectorised = 0, blocks = 0, tpb = 0;
+    const int rc = fpd_loss_geometry_of(a, &vectorised, &blocks, &tpb);
+    if (rc) return rc;
+    if (vectorised) {
+        if (a.dtype == FPD_BF16)
+            FPD_LAUNCH((loss_vec_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, a, tpb);
+        else
+            FPD_LAUNCH((loss_vec_kernel<float>), dim3(blocks), dim3(256), 0, st, a, tpb);
+        return 0;
+    }
     if (a.dtype == FPD_BF16)
-        FPD_LAUNCH((loss_kernel<bf16_t>), dim3(tiles), dim3(256), 0, st, a);
+        FPD_LAUNCH((loss_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, a);
     else
-        FPD_LAUNCH((loss_kernel<float>), dim3(tiles), dim3(256), 0, st, a);
+        FPD_LAUNCH((loss_kernel<float>), dim3(blocks), dim3(256), 0, st, a);
     return 0;
 }
 

@@ -347,6 +347,7 @@ SYMBOLS = {
     'fpd_head_forward': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_head_fold': (C.c_int, [C.POINTER(HeadT), _vp]),
     'fpd_loss': (C.c_int, [C.POINTER(LossT), _vp]),
+    'fpd_loss_geometry': (C.c_int, [C.POINTER(LossT), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'fpd_loss_ohkm': (C.c_int, [C.POINTER(LossOhkmT), _vp]),
     'fpd_loss_ohkm_scratch_bytes': (C.c_int64, [C.POINTER(LossT)]),
     'fpd_loss_kl': (C.c_int, [C.POINTER(LossKlT), _vp]),

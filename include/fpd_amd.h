@@ -464,6 +464,12 @@ int fpd_elementwise(const fpd_ew_t* a, fpd_stream_t stream);
 typedef struct { fpd_ew_t a, b; } fpd_ew_pair_t;
 int fpd_elementwise_pair(const fpd_ew_pair_t* p, fpd_stream_t stream);
 int fpd_loss(const fpd_loss_t* a, fpd_stream_t stream);
+/* The launch fpd_loss() makes for `a` as it stands (pure host code: dimensions, dtype and the alignment of teacher, out[s] and
+ * dout[s] are looked at, nothing is dereferenced).  vectorised: 1 = 16-byte vectors of joints, tiles of 128 pixels (J a multiple
+ * of 8 in bf16, 4 in fp32, and every map 16-byte aligned), 0 = the element-per-thread kernel, tiles of 64 pixels.  blocks: the
+ * grid = the number of terms added to each of losses[0..1].  tiles_per_block: tiles of one image a block walks (the last block
+ * of an image may own fewer).  Returns 0, or the error code fpd_loss() would give for these dimensions. */
+int fpd_loss_geometry(const fpd_loss_t* a, int32_t* vectorised, int32_t* blocks, int32_t* tiles_per_block);
 int fpd_loss_ohkm(const fpd_loss_ohkm_t* a, fpd_stream_t stream);
 /* bytes of fpd_loss_ohkm_t.scratch for these dimensions (B, J, H, W, S are looked at); negative on bad dimensions */
 int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a);
