@@ -301,6 +301,8 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// grid of a grid-stride launch over n work items at 256 threads a block: at most 4096 blocks (loss_adam.hip, ema.hip)
+static inline int grid_for(int64_t n) { const int64_t b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
 // Probe build only (tools/probes/tile_timing.sh, -DFPD_TILE_TIMING): cycle stamps of block (0, 0) at the phase boundaries of
 // conv_tile_body and its epilogue, printed by the kernel.

@@ -296,8 +296,6 @@ __global__ void nhwc_to_nchw_kernel(const T* src, float* dst, int N, int C, int 
     }
 }
 
-inline int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096)); }
-
 }  // namespace
 
 // Which kernel fpd_loss_launch() runs for `a` as it stands (dimensions, dtype, pointer alignments), and its grid: the launch

@@ -844,12 +844,13 @@ class GraphInstance:
 class FusedFPDStep:
     """The fused FPD iteration (lib/core/function.py:119-147 of the reference) on one GPU:
          teacher forward (eval BN) -> student forward (train BN) -> fused pose+KD loss fwd/bwd
-         -> student backward -> [RCCL all-reduce of the flat gradient] -> flat Adam (sgd=: flat SGD instead).
+         -> student backward -> [RCCL all-reduce of the flat gradient] -> flat Adam (sgd=: flat SGD instead)
+         [-> ema=: the weight average of a lib.utils.utils.ModelEma, one more launch in the optimizer's range].
     No host synchronisation inside; losses are read back only when asked for."""
 
     def __init__(self, student_state, student_cfg, teacher_state, teacher_cfg, batch, height, width, alpha,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, world_size=1, adam=None, teacher_chunks=None,
-                 use_target_weight=(True, True), ohkm=None, sgd=None, kl=None):
+                 use_target_weight=(True, True), ohkm=None, sgd=None, kl=None, ema=None):
         dev = student_state.device
         if adam is not None and sgd is not None:
             raise R.FpdError('FusedFPDStep: adam= and sgd= are mutually exclusive')
@@ -945,7 +946,7 @@ class FusedFPDStep:
         self.n_param = n
         self._dist_work = None
         if sgd is not None:         # share the momentum buffer / step / lr with a lib.utils.utils.FusedSGD; no Adam moments
-            self._add_sgd(sgd, student_state, n)
+            self._add_sgd(sgd, student_state, n, ema)
             return
         if adam is not None:        # share moments / step / lr with a lib.utils.utils.FusedAdam (checkpointable state)
             self.m, self.v, self.lr_dev, self.step_dev = adam.m, adam.v, adam.lr_dev, adam.step_dev
@@ -969,9 +970,24 @@ class FusedFPDStep:
         self._adam_args = a
         b = len(self.student.plan)
         self.student.plan.add(R.OP_ADAM, a)
+        self._add_ema(ema, student_state)
         self.student.rng['adam'] = (b, len(self.student.plan))
 
-    def _add_sgd(self, sgd, student_state, n):
+    def _add_ema(self, ema, student_state):
+        """ema=: one OP_EMA behind the optimizer op, INSIDE its range -- whatever replays that range (student_step, the deferred
+        run behind the overlapped all-reduce, a captured graph) averages exactly once per update, and nothing else needs to know.
+        It reads the arenas the optimizer and the BN update of this step have just written and writes only the ModelEma's own."""
+        self.ema = ema
+        if ema is None:
+            return
+        a = ema.ema_args()
+        pa = student_state.A
+        if a.seg[0].src != pa.tensor('param').data_ptr() or a.seg[1].src != pa.tensor('rstat').data_ptr():
+            raise R.FpdError('FusedFPDStep: ema= averages another model than the student of this step')
+        self._ema_args = a
+        self.student.plan.add(R.OP_EMA, a)
+
+    def _add_sgd(self, sgd, student_state, n, ema=None):
         """The optimizer range ('adam' by name, so that run / capture / phase timing need not know) = one OP_SGD with the
         hyperparameters of the FusedSGD's param group as they are NOW (core.function keys its step cache on them)."""
         g = sgd.param_groups[0]
@@ -989,6 +1005,7 @@ class FusedFPDStep:
         self._sgd_args = a
         b = len(self.student.plan)
         self.student.plan.add(R.OP_SGD, a)
+        self._add_ema(ema, student_state)
         self.student.rng['adam'] = (b, len(self.student.plan))
 
     def enable_metric(self, min_slots=0):

@@ -88,14 +88,19 @@ def _defaults():
                     'DATA_FORMAT': 'jpg', 'COLOR_RGB': False, 'SELECT_DATA': False, 'CACHE_ROOT': '', 'HYBRID_JOINTS_TYPE': ''},
         'TRAIN': {'LR_FACTOR': 0.1, 'LR_STEP': [90, 120], 'LR': 0.00025, 'OPTIMIZER': 'adam', 'MOMENTUM': 0.9, 'WD': 0.0001,
                   'NESTEROV': False, 'GAMMA1': 0.99, 'GAMMA2': 0.0, 'BEGIN_EPOCH': 0, 'END_EPOCH': 140, 'RESUME': False,
-                  'CHECKPOINT': '', 'BATCH_SIZE_PER_GPU': 32, 'SHUFFLE': True},
+                  'CHECKPOINT': '', 'BATCH_SIZE_PER_GPU': 32, 'SHUFFLE': True,
+                  # not in the reference: exponential moving average of the student's weights (utils.ModelEma), updated inside the
+                  # fused step; validation and the best / final checkpoints then use the average
+                  'EMA': False, 'EMA_DECAY': 0.9998, 'EMA_WARMUP': True},
         'TEST': {'BATCH_SIZE_PER_GPU': 32, 'FLIP_TEST': False, 'POST_PROCESS': False, 'SHIFT_HEATMAP': False, 'MODEL_FILE': '',
                  # read by DATASET.DATASET coco (default.py:110-119); NMS_THRE and BBOX_THRE are accepted and unused, as there
                  'USE_GT_BBOX': False, 'IMAGE_THRE': 0.1, 'NMS_THRE': 0.6, 'SOFT_NMS': False, 'OKS_THRE': 0.5, 'IN_VIS_THRE': 0.0,
                  'COCO_BBOX_FILE': '', 'BBOX_THRE': 1.0,
                  # not in the reference: DARK sub-pixel decoding (core.inference) in place of the POST_PROCESS quarter-pixel
                  # shift; BLUR_KERNEL: its Gaussian blur size, odd, 9..31 (DarkPose YAMLs carry 11)
-                 'DARK': False, 'BLUR_KERNEL': 11},
+                 'DARK': False, 'BLUR_KERNEL': 11,
+                 # not in the reference: tools/test.py evaluates the ema_state_dict of the full checkpoint given as MODEL_FILE
+                 'USE_EMA': False},
         'KD': {'TRAIN_TYPE': 'NORMAL', 'TEACHER': '', 'ALPHA': 0.5,        # default.py:122-126
                'LOSS': 'mse', 'TEMPERATURE': 1.0},   # not in the reference: distillation criterion 'mse' | 'kl' (core.loss.JointsKLDLoss)
         'DEBUG': {'DEBUG': False, 'SAVE_BATCH_IMAGES_GT': False, 'SAVE_BATCH_IMAGES_PRED': False,

@@ -71,7 +71,14 @@ class _NetFn(torch.autograd.Function):
 
 class FlatArenaNet(nn.Module):
     """Base of the HIP-backed networks.  Subclasses set self.cfg_hg (the dict executor.GraphInstance builds the op graph
-    from), self.fpd_dtype, call _init_flat(table), build their module tree and call _bind_tree()."""
+    from), self.fpd_dtype and self._ctor (their constructor's arguments), call _init_flat(table), build their module tree
+    and call _bind_tree()."""
+
+    def clone_structure(self, cls=None):
+        """A second instance built from the same configuration (of `cls`, a subclass, when given), on the CPU with its own
+        freshly initialised arenas: utils.ModelEma points it at the EMA arenas."""
+        cfg, kwargs = self._ctor
+        return (cls or type(self))(cfg, **kwargs)
 
     def _init_flat(self, table):
         self.table = table

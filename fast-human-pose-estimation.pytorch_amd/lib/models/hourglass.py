@@ -112,6 +112,7 @@ class HourglassNet(FlatArenaNet):
 
     def __init__(self, cfg, **kwargs):
         super().__init__()
+        self._ctor = (cfg, dict(kwargs))
         extra = cfg.MODEL.EXTRA
         self.cfg_hg = {'F': int(extra.NUM_FEATURES), 'S': int(extra.NUM_STACKS), 'J': int(cfg.MODEL.NUM_JOINTS),
                        'num_blocks': int(extra.NUM_BLOCKS)}

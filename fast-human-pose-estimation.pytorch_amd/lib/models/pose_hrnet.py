@@ -115,6 +115,7 @@ class PoseHighResolutionNet(FlatArenaNet):
 
     def __init__(self, cfg, **kwargs):
         super().__init__()
+        self._ctor = (cfg, dict(kwargs))
         extra = _plain(cfg['MODEL']['EXTRA'])
         self.extra = {k: extra[k] for k in ('STAGE2', 'STAGE3', 'STAGE4')}
         self.extra['FINAL_CONV_KERNEL'] = int(extra.get('FINAL_CONV_KERNEL', 1))

@@ -193,6 +193,107 @@ class FusedSGD(_FlatOptimizer):
         self.sync_lr()
 
 
+class _EmaOutputs(torch.autograd.Function):
+    """Identity on the averaged model's outputs whose backward is the refusal: nothing trains through an average."""
+
+    @staticmethod
+    def forward(ctx, anchor, *outs):
+        return tuple(o.view_as(o) for o in outs)
+
+    @staticmethod
+    def backward(ctx, *g):
+        raise R.FpdError('ModelEma.module holds averaged weights: it is evaluated, never trained (backward through it refused)')
+
+
+class _EmaModule:
+    """Mixed in front of the model's class for ModelEma.module: always in eval mode, no backward."""
+
+    def train(self, mode=True):
+        if mode:
+            raise R.FpdError('ModelEma.module holds averaged weights and stays in eval mode (train() refused)')
+        return super().train(False)
+
+    def forward(self, x):
+        outs = super().forward(x)
+        if not torch.is_grad_enabled():
+            return outs
+        wrapped = _EmaOutputs.apply(next(self.parameters()), *(outs if isinstance(outs, list) else [outs]))
+        return list(wrapped) if isinstance(outs, list) else wrapped[0]
+
+
+class ModelEma:
+    """Exponential moving average of a HIP-backed model's state (timm ModelEmaV3 / the ExpMomentumEMA hook of RTMPose):
+    EMA copies of the model's three flat arenas and a device update counter, advanced by ONE fpd_ema launch (csrc/ema.hip) --
+    by update() on the module-API path, or as a plan op inside the fused step's optimizer range (FusedFPDStep(ema=)).
+    Parameters and BN running statistics are averaged, e += w (x - e) with w = 1 - min(decay, (1 + u) / (10 + u)) under
+    warm-up (csrc/ema_math.h); num_batches_tracked is copied.  `.module` is a second instance of the model's class whose
+    tensors are views of the EMA arenas: validate, tools/test.py and load_checkpoint take it like the model.  Create it after
+    .to(device), like the optimizer."""
+
+    def __init__(self, model, decay=0.9998, warmup=True):
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError('Invalid EMA decay: %r (expected 0 <= decay < 1)' % (decay,))
+        self.model = model.module if hasattr(model, 'module') else model
+        if not hasattr(self.model, '_flat') or not hasattr(self.model, 'clone_structure'):
+            raise R.FpdError('ModelEma: %s is not a HIP-backed model (lib.models)' % type(self.model).__name__)
+        self.decay, self.warmup = float(decay), bool(warmup)
+        self.flat = {n: t.clone() for n, t in self.model._flat.items()}
+        self.updates_dev = torch.zeros(1, dtype=torch.int64, device=self.flat['param'].device)
+        cls = type(self.model)
+        with torch.random.fork_rng(devices=[]):            # the second instance's own initialisation draws nothing from the run
+            self.module = self.model.clone_structure(type('Ema' + cls.__name__, (_EmaModule, cls), {}))
+        self.module._flat = self.flat
+        self.module._flat_grad = self.module._state = None
+        self.module._instances = {}
+        self.module._relink()
+        self.module.eval()
+
+    def ema_args(self):
+        """The filled fpd_ema_t: parameter arena, running-statistics arena, num_batches_tracked as the plain copy."""
+        t, src = self.model.table, self.model._flat
+        a = R.EmaT()
+        a.nseg = 2
+        for s, n in enumerate(('param', 'rstat')):
+            a.seg[s].src, a.seg[s].dst, a.seg[s].n = src[n].data_ptr(), self.flat[n].data_ptr(), t.sizes[n]
+        a.warmup, a.decay = int(self.warmup), self.decay
+        a.copy_src, a.copy_dst, a.copy_n = src['nbt'].data_ptr(), self.flat['nbt'].data_ptr(), t.sizes['nbt']
+        a.updates_dev = self.updates_dev.data_ptr()
+        return a
+
+    @torch.no_grad()
+    def update(self):
+        if not self.flat['param'].is_cuda:
+            raise R.FpdError('ModelEma.update needs the model on a CUDA (ROCm) device; there is no CPU path')
+        R.check(R.lib().fpd_ema(self.ema_args(), R.current_stream()), 'fpd_ema')
+
+    @torch.no_grad()
+    def set(self, model=None):
+        """Start the average again from the model's current state: arenas copied, counter zero."""
+        m = self.model if model is None else (model.module if hasattr(model, 'module') else model)
+        for n in self.flat:
+            self.flat[n].copy_(m._flat[n])
+        self.updates_dev.zero_()
+
+    @property
+    def updates(self):
+        return int(self.updates_dev.item())
+
+    def state_dict(self):
+        return {'state_dict': {k: v.clone() for k, v in self.module.state_dict().items()}, 'updates': self.updates,
+                'decay': self.decay, 'warmup': self.warmup}
+
+    def load_state_dict(self, sd):
+        inner = {(k[7:] if k.startswith('module.') else k): v for k, v in sd['state_dict'].items()}
+        self.module.load_state_dict(inner)
+        self.updates_dev.fill_(int(sd.get('updates', 0)))
+        if 'decay' in sd:
+            if not 0.0 <= float(sd['decay']) < 1.0:
+                raise ValueError('Invalid EMA decay in the state: %r' % (sd['decay'],))
+            self.decay = float(sd['decay'])
+        if 'warmup' in sd:
+            self.warmup = bool(sd['warmup'])
+
+
 def multistep_lr(base_lr, milestones, gamma, epoch):
     """Learning rate the reference trains epoch `epoch` with (tools/fpd_train.py:236-239,253: MultiStepLR built with
     last_epoch = -1 and stepped at the START of every epoch, so epoch e runs at the scheduler's value for e + 1, i.e.

@@ -17,7 +17,7 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
  EW_ADD, EW_RELU_MASK, EW_DILATE2) = range(10)
 (OP_CONV, OP_WGRAD, OP_STEM_FWD, OP_STEM_WGRAD, OP_EW, OP_LOSS, OP_ADAM, OP_MEMSET, OP_WPREP, OP_BNUPD,
  OP_WREDUCE, OP_BNECK, OP_BNECK_FOLD, OP_CONV_PAIR, OP_BNECK_PAIR, OP_EW_PAIR, OP_PCK, OP_HEAD, OP_HEAD_FOLD,
- OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE, OP_LOSS_KL) = range(28)
+ OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE, OP_LOSS_KL, OP_EMA) = range(29)
 EWM_MAXPOOL_BWD, EWM_SUMPOOL = 0, 1
 AFFSUM_MAX = 4
 MAX_STACKS = 8
@@ -261,6 +261,18 @@ class SgdT(C.Structure):
                 ('lr_dev', _vp), ('step_dev', _vp)]
 
 
+EMA_MAX_SEG = 4     # include/fpd_amd.h FPD_EMA_MAX_SEG
+
+
+class EmaSegT(C.Structure):
+    _fields_ = [('src', _vp), ('dst', _vp), ('n', _i64)]
+
+
+class EmaT(C.Structure):
+    _fields_ = [('seg', EmaSegT * EMA_MAX_SEG), ('nseg', _i32), ('warmup', _i32), ('decay', _f64), ('copy_src', _vp),
+                ('copy_dst', _vp), ('copy_n', _i64), ('updates_dev', _vp)]
+
+
 class WprepEntryT(C.Structure):
     _fields_ = [('w', _vp), ('w_fwd', _vp), ('w_bwd', _vp), ('K', _i32), ('R', _i32), ('S', _i32), ('C', _i32)]
 
@@ -293,7 +305,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_ew_merge_t': EwMergeT, 'fpd_oks_nms_t': OksNmsT,
             'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT, 'fpd_dark_t': DarkT,
             'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
-            'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT}
+            'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT, 'fpd_ema_t': EmaT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -354,6 +366,8 @@ SYMBOLS = {
     'fpd_loss_kl_scratch_bytes': (C.c_int64, [C.POINTER(LossT)]),
     'fpd_adam': (C.c_int, [C.POINTER(AdamT), _vp]),
     'fpd_sgd': (C.c_int, [C.POINTER(SgdT), _vp]),
+    'fpd_ema': (C.c_int, [C.POINTER(EmaT), _vp]),
+    'fpd_ema_geometry': (C.c_int, [C.POINTER(EmaT), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'fpd_weight_prep': (C.c_int, [_vp, _i32, _i64, _i32, _vp]),
     'fpd_bn_update_running': (C.c_int, [_vp, _i32, _vp]),
     'fpd_cast': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),

@@ -405,6 +405,27 @@ typedef struct {
     int64_t* step_dev;     /* optional: device step counter, incremented once per step */
 } fpd_sgd_t;
 
+/* Exponential moving average of a model's state (timm ModelEmaV3 / the ExpMomentumEMA hook), one launch over up to
+ * FPD_EMA_MAX_SEG flat fp32 segments (in practice the parameter arena and the BN running-statistics arena), arithmetic in
+ * csrc/ema_math.h:
+ *   u = *updates_dev + 1;  d = warmup ? min(decay, (1 + u) / (10 + u)) : decay  (float64);  w = (float)(1 - d)
+ *   dst[i] = dst[i] + w * (src[i] - dst[i])          three float32 roundings, never fused
+ *   copy_dst[i] = copy_src[i]                         (num_batches_tracked: integers are copied, not averaged)
+ * A one-thread launch behind the kernel adds 1 to *updates_dev, so no block reads a counter that has moved.  A segment whose
+ * src and dst are both 16-byte aligned moves 16-byte vectors (and up to 3 elements one by one), any other segment goes
+ * element by element.  Refused before any launch: nseg outside 1..FPD_EMA_MAX_SEG, a negative n or copy_n, a null pointer
+ * with a positive count, a null updates_dev, decay outside [0, 1), any written range (a dst, copy_dst, the counter)
+ * overlapping any read or other written range (src == dst included). */
+#define FPD_EMA_MAX_SEG 4
+typedef struct { const float* src; float* dst; int64_t n; } fpd_ema_seg_t;
+typedef struct {
+    fpd_ema_seg_t seg[FPD_EMA_MAX_SEG];
+    int32_t nseg, warmup;
+    double decay;
+    const int64_t* copy_src; int64_t* copy_dst; int64_t copy_n;   /* plain copy, may be NULL / 0 */
+    int64_t* updates_dev;  /* updates done so far; read by every thread, incremented behind the kernel */
+} fpd_ema_t;
+
 /* Per-conv working copies of the weights: cast to `dtype` in K,R,S,C order (forward operand)
  * and the flipped, IO-swapped C,R,S,K copy (data-gradient operand).  One launch for a table. */
 typedef struct {
@@ -479,6 +500,12 @@ int64_t fpd_loss_kl_scratch_bytes(const fpd_loss_t* a);
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream);
 /* refuses (before any launch) null param / grad, n < 0, momentum < 0, weight_decay < 0, momentum != 0 without buf, nesterov without momentum */
 int fpd_sgd(const fpd_sgd_t* a, fpd_stream_t stream);
+int fpd_ema(const fpd_ema_t* a, fpd_stream_t stream);
+/* The launch fpd_ema() makes for `a` as it stands (pure host code: counts and pointer alignments are looked at, nothing is
+ * dereferenced).  blocks: the grid of the one kernel (256 threads a block; a thread walks a segment's vectors, then its
+ * single elements, with a stride of 256 * blocks).  vec_elems[s], s < nseg: the leading elements of segment s moved as
+ * 16-byte vectors (a multiple of 4; 0 = the element-by-element path).  Returns 0, or the error code fpd_ema() would give. */
+int fpd_ema_geometry(const fpd_ema_t* a, int32_t* blocks, int64_t* vec_elems);
 int fpd_weight_prep(const fpd_wprep_entry_t* table_dev, int32_t n_entries, int64_t max_elems, int32_t dtype,
                     fpd_stream_t stream);
 int fpd_bn_update_running(const fpd_bnupd_entry_t* table_dev, int32_t n_entries, fpd_stream_t stream);
@@ -964,7 +991,8 @@ enum {
     FPD_OP_LOSS_OHKM = 24,      /* args: fpd_loss_ohkm_t */
     FPD_OP_SGD = 25,            /* args: fpd_sgd_t */
     FPD_OP_EW_MERGE = 26,       /* args: fpd_ew_merge_t */
-    FPD_OP_LOSS_KL = 27         /* args: fpd_loss_kl_t */
+    FPD_OP_LOSS_KL = 27,        /* args: fpd_loss_kl_t */
+    FPD_OP_EMA = 28             /* args: fpd_ema_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;

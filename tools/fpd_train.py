@@ -16,7 +16,10 @@ PROB_HALF_BODY / NUM_JOINTS_HALF_BODY, LOSS.USE_DIFFERENT_JOINTS_WEIGHT; lib/dat
 random teacher with calibrated BN statistics instead of loading a checkpoint.  LOSS.USE_OHKM of the student config makes
 the pose criterion a JointsOHKMMSELoss(topk=LOSS.TOPK), LOSS.USE_OHKM of the teacher config the distillation criterion
 (make_criterion below); KD.LOSS 'kl' makes the distillation criterion a JointsKLDLoss(KD.TEMPERATURE) (make_kd_criterion);
-the reference declares both keys and its tools never read them (its class is never instantiated).
+the reference declares both keys and its tools never read them (its class is never instantiated).  TRAIN.EMA keeps an
+exponential moving average of the student (utils.ModelEma, TRAIN.EMA_DECAY / EMA_WARMUP), updated inside the fused step:
+the per-epoch validation, model_best.pth and final_state.pth then hold the average; checkpoint.pth keeps the raw weights
+(what a resume continues from) and gains ema_state_dict / ema_updates.
 """
 import argparse
 import logging
@@ -39,7 +42,7 @@ from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa
 from fpd_amd.lib.dataset.device_pipeline import unbiased_targets  # noqa: E402
 from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
 from fpd_amd.lib.core.loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
-from fpd_amd.lib.utils.utils import (get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
+from fpd_amd.lib.utils.utils import (ModelEma, get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
                                      save_checkpoint)
 
 
@@ -191,6 +194,7 @@ def run(args, normal=False):
         del cal
 
     optimizer = get_optimizer(cfg, model)                                                     # :218
+    ema = ModelEma(model, decay=float(cfg.TRAIN.EMA_DECAY), warmup=bool(cfg.TRAIN.EMA_WARMUP)) if cfg.TRAIN.EMA else None
     begin_epoch, best_perf = cfg.TRAIN.BEGIN_EPOCH, 0.0
     ckpt = os.path.join(out_dir, 'checkpoint.pth')
     if cfg.AUTO_RESUME and os.path.exists(ckpt):                                              # :224-234
@@ -199,6 +203,11 @@ def run(args, normal=False):
         model.load_state_dict(state['state_dict'])
         optimizer.load_state_dict(state['optimizer'])
         logger.info("=> loaded checkpoint '%s' (epoch %d)", ckpt, state['epoch'])
+        if ema is not None and 'ema_state_dict' in state:
+            ema.load_state_dict({'state_dict': state['ema_state_dict'], 'updates': state.get('ema_updates', 0)})
+        elif ema is not None:
+            logger.warning('=> checkpoint %s has no ema_state_dict: the average restarts from the resumed weights', ckpt)
+            ema.set(model)
     base_lr = float(optimizer.param_groups[0].get('initial_lr', cfg.TRAIN.LR))               # :236-239 MultiStepLR
     optimizer.param_groups[0]['initial_lr'] = base_lr
     allreduce = fdist.make_allreduce(dist) if world > 1 else None
@@ -215,28 +224,34 @@ def run(args, normal=False):
         optimizer.param_groups[0]['lr'] = multistep_lr(base_lr, cfg.TRAIN.LR_STEP, cfg.TRAIN.LR_FACTOR, epoch)   # :253
         if train_type == 'FPD':                                                               # :255-264
             loss = fpd_train(cfg, loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch, out_dir,
-                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank)
+                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank, ema=ema)
         else:
             loss = train(cfg, loader, model, pose_criterion, optimizer, epoch, out_dir, cfg.LOG_DIR, writer_dict,
-                         allreduce=allreduce, world_size=world, rank=rank)
+                         allreduce=allreduce, world_size=world, rank=rank, ema=ema)
         torch.cuda.synchronize()
         logger.info('=> epoch %d done in %.1fs, %.1f samples/s, last logged loss %.5f', epoch, time.time() - t0,
                     len(loader) * bs * world / max(time.time() - t0, 1e-9), loss)
         # :266-285: evaluate on the validation set (flip test etc. per cfg.TEST) on every rank, keep the best model on rank 0
         # float(): MPII's indicator is a numpy scalar, which a weights-only torch.load of the checkpoint refuses
-        perf_indicator = float(validate(cfg, valid_loader, valid_set, model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict,
+        # TRAIN.EMA: the averaged weights are what is evaluated and kept as the best model
+        eval_model = ema.module if ema is not None else model
+        perf_indicator = float(validate(cfg, valid_loader, valid_set, eval_model, val_criterion, out_dir, cfg.LOG_DIR, writer_dict,
                                         gather=gather, rank=rank))
         if rank == 0:
             best_model = perf_indicator >= best_perf
             best_perf = max(best_perf, perf_indicator)
-            save_checkpoint({'epoch': epoch + 1, 'model': cfg.MODEL.NAME, 'state_dict': model.state_dict(),
-                             'best_state_dict': model.module.state_dict(), 'perf': perf_indicator,
-                             'optimizer': optimizer.state_dict()}, best_model, out_dir)
+            states = {'epoch': epoch + 1, 'model': cfg.MODEL.NAME, 'state_dict': model.state_dict(),
+                      'best_state_dict': model.module.state_dict(), 'perf': perf_indicator,
+                      'optimizer': optimizer.state_dict()}
+            if ema is not None:
+                e = ema.state_dict()
+                states.update(best_state_dict=e['state_dict'], ema_state_dict=e['state_dict'], ema_updates=e['updates'])
+            save_checkpoint(states, best_model, out_dir)
         if world > 1:
             dist.barrier()       # ranks != 0 wait for rank 0's checkpoint HERE, explicitly, rather than inside the first
                                  # gradient all-reduce of the next epoch
     if rank == 0:
-        torch.save(model.module.state_dict(), os.path.join(out_dir, 'final_state.pth'))      # :288-294
+        torch.save((ema.module if ema is not None else model.module).state_dict(), os.path.join(out_dir, 'final_state.pth'))      # :288-294
     if world > 1:
         dist.destroy_process_group()
 

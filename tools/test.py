@@ -10,7 +10,8 @@ model runs on the HIP path, on one GPU or, under `python -m torch.distributed.ru
 (every rank validates its block of the set, rank 0 gathers and evaluates); DATASET.DATASET 'synthetic' feeds the seeded synthetic validation set of
 tools/fpd_train.py ('synthetic_aug': its validation scenes, cropped on the device), 'mpii' DATASET.ROOT / TEST_SET with the
 PCKh table, 'coco' DATASET.ROOT / TEST_SET from ground-truth or detection boxes (TEST.USE_GT_BBOX, TEST.COCO_BBOX_FILE) with the
-keypoint AP table."""
+keypoint AP table.  TEST.USE_EMA true evaluates the averaged weights (ema_state_dict) of a full checkpoint.pth written by a
+TRAIN.EMA run and given as TEST.MODEL_FILE; a file without them is an error."""
 import argparse
 import logging
 import os
@@ -66,7 +67,15 @@ def main():
     model = eval('models.' + cfg.MODEL.NAME + '.get_pose_net')(cfg, is_train=False)          # :84-86
     model_file = cfg.TEST.MODEL_FILE or os.path.join(out_dir, 'final_state.pth')              # :88-96
     logger.info('=> loading model from %s', model_file)
-    load_checkpoint(model_file, model, strict=not cfg.TEST.MODEL_FILE, model_info=cfg.MODEL.NAME)
+    if cfg.TEST.USE_EMA:
+        state = torch.load(model_file, map_location='cpu')
+        if not isinstance(state, dict) or not isinstance(state.get('ema_state_dict'), dict):
+            raise ValueError('TEST.USE_EMA: %s holds no ema_state_dict (give the checkpoint.pth of a TRAIN.EMA run as '
+                             'TEST.MODEL_FILE)' % model_file)
+        logger.info('=> evaluating the averaged weights (%d updates)', int(state.get('ema_updates', 0)))
+        load_checkpoint(state['ema_state_dict'], model, strict=True, model_info=cfg.MODEL.NAME)
+    else:
+        load_checkpoint(model_file, model, strict=not cfg.TEST.MODEL_FILE, model_info=cfg.MODEL.NAME)
     model = fdist.DataParallelReplica(model.to(dev))
     criterion = JointsMSELoss(use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT).to(dev)          # :101-103
 
