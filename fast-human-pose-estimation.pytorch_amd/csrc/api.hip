@@ -83,6 +83,8 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c3")) return fpd_conv_c3_option(0, value);
     if (!strcmp(name, "conv_c3_blocks")) return fpd_conv_c3_option(1, value);
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);
+    if (!strcmp(name, "conv_tile_launches")) return fpd_conv_tile_launches();        // (read-only: launches conv_tile.hip has served)
+    if (!strcmp(name, "wgrad_tile_launches")) return fpd_wgrad_tile_launches();      // (read-only: launches of wgrad_tile_kernel; those handed to wgrad3 are not counted)
     if (!strcmp(name, "bneck_blocks")) return fpd_bneck_blocks_option(value);
     if (!strcmp(name, "bneck_upadd")) return fpd_bneck_upadd_option(value);          // up-add formed on load (fpd_bneck_t.x2) offered at all
     if (!strcmp(name, "head_blocks")) return fpd_head_blocks_option(value);
@@ -189,6 +191,17 @@ int fpd_conv_pair_fold_supported(const fpd_conv_pair_t* p) {
     if (!p || validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return 0;
     if (route_conv(p->a, &p->b, ConvAsk{true, fpd_conv_ask(p->a, &p->b).wg, fpd_conv_ask(p->a, &p->b).skip}, r) != nullptr) return r.folds ? 1 : 0;
     return (fpd_conv_fold_supported(&p->a) && fpd_conv_fold_supported(&p->b)) ? 1 : 0;      // two single launches
+}
+
+// Which instantiation of the halo-tile kernel would run this launch (pair), asked of the kernel unit alone -- whether the dispatch
+// gets as far as conv_tile is the business of the options and of the units in front of it.  The fold is asked for where fold_x is set.
+int fpd_conv_tile_variant(const fpd_conv_t* a) {
+    if (!a || validate_conv(a) != 0) return -1;
+    return fpd_conv_tile_variant_of(*a, nullptr, fpd_conv_ask(*a, nullptr));
+}
+int fpd_conv_tile_pair_variant(const fpd_conv_pair_t* p) {
+    if (!p || validate_conv(&p->a) != 0 || validate_conv(&p->b) != 0) return -1;
+    return fpd_conv_tile_variant_of(p->a, &p->b, fpd_conv_ask(p->a, &p->b));
 }
 
 // (the second source is read from the fields: x2, w2, bias2, C2 as they will be launched)
@@ -330,6 +343,11 @@ int fpd_conv_wgrad(const fpd_wgrad_t* a, fpd_stream_t stream) {
         if (rc != 1) break;
     }
     return rc ? rc : check_launch();
+}
+
+int fpd_wgrad_tile_variant(const fpd_wgrad_t* a) {
+    if (!a || validate_conv_dims(a->N, a->H, a->W, a->C, a->K, a->R, a->S, a->stride, a->pad, a->P, a->Q) != 0) return -1;
+    return fpd_wgrad_tile_variant_of(*a);
 }
 
 /* slabs the kernel fpd_conv_wgrad() dispatches these dimensions to will write */

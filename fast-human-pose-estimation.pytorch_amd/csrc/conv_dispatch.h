@@ -84,6 +84,8 @@ int fpd_conv_pp_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, Con
 int fpd_conv_pp_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
 int fpd_conv_tile_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, ConvRoute& r);
 int fpd_conv_tile_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st);
+int fpd_conv_tile_variant_of(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask);      // the instantiation that launch runs (packed, see conv_tile.hip), -1: declined
+int fpd_conv_tile_launches();                      // "conv_tile_launches"
 int fpd_conv_c1_option(int which, int value);
 int fpd_conv_c3_option(int which, int value);
 int fpd_conv_pp_option(int which, int value);
@@ -98,6 +100,8 @@ int fpd_weight_quant_f8_launch(const fpd_wquant_entry_t* table, int n, hipStream
 // ---- weight gradients: *_partials = slabs the launch of the same unit writes (0: it declines) ----
 int fpd_wgrad_tile_partials(const fpd_wgrad_t& a);
 int fpd_wgrad_tile_launch(const fpd_wgrad_t& a, hipStream_t st);
+int fpd_wgrad_tile_variant_of(const fpd_wgrad_t& a);      // the wgrad_tile_kernel instantiation that launch runs (packed, see wgrad_tile.hip), -1: declined or handed to wgrad3
+int fpd_wgrad_tile_launches();                     // "wgrad_tile_launches"
 int fpd_wgrad_mfma_partials(const fpd_wgrad_t& a);
 int fpd_wgrad_mfma_launch(const fpd_wgrad_t& a, hipStream_t st);
 int fpd_wgrad_smallc_partials(const fpd_wgrad_t& a);

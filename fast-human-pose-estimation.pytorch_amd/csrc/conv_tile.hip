@@ -520,6 +520,9 @@ int launch_tile_v(const fpd_conv_t& a, const fpd_conv_t* bp, const TilePlan& pl,
     return 0;
 }
 // the plan's (TN, ALLW) as template arguments
+// (ALLW with TN == 4 is compiled and never launched: nine staged weight tiles of 128 channels are 165888 B in either storage type,
+// above LDS_MAX, so tile_route() never plans it -- a sweep of fpd_conv_tile_variant() over N 1..32, the networks' map sizes and
+// C, K in 16..384 finds every other (T, BK, TN, ALLW, FOLD) and not this one: tests/test_exact_variants_cpu.py)
 template <typename T, int BK>
 int launch_tile(const fpd_conv_t& a, const fpd_conv_t* b, const TilePlan& pl, hipStream_t st) {
     if constexpr (BK == 64 || (BK == 32 && sizeof(T) == 4)) {
@@ -540,15 +543,23 @@ int fpd_conv_tile_route(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask, C
     TilePlan pl;
     return tile_route(a, b, ask, r, pl) ? 0 : 1;
 }
+// The instantiation the launch carrying `ask` runs (tests: every compiled variant is reached by an exact case), from the plan of the
+// same tile_route() the launch walks: element size | BK << 4 | TN << 12 | ALLW << 16 | FOLD << 17; -1: the kernel declines.
+int fpd_conv_tile_variant_of(const fpd_conv_t& a, const fpd_conv_t* b, ConvAsk ask) {
+    ConvRoute r;
+    TilePlan pl;
+    if (!tile_route(a, b, ask, r, pl)) return -1;
+    return pl.esz | pl.bk << 4 | pl.tn << 12 | (pl.allw ? 1 : 0) << 16 | (pl.fold ? 1 : 0) << 17;
+}
+static std::atomic<int> g_tile_launches{0};      // launches this unit has served (tests: "conv_tile_launches")
+int fpd_conv_tile_launches() { return g_tile_launches.load(std::memory_order_relaxed); }
 int fpd_conv_tile_launch(const fpd_conv_t& a, const fpd_conv_t* b, hipStream_t st) {
     ConvRoute r;
     TilePlan pl;
     if (!tile_route(a, b, fpd_conv_ask(a, b), r, pl)) return 1;
-    if (pl.esz == 2) {
-        if (pl.bk == 64) return launch_tile<bf16_t, 64>(a, b, pl, st);
-        if (pl.bk == 32) return launch_tile<bf16_t, 32>(a, b, pl, st);
-        return launch_tile<bf16_t, 16>(a, b, pl, st);
-    }
-    if (pl.bk == 32) return launch_tile<float, 32>(a, b, pl, st);
-    return launch_tile<float, 16>(a, b, pl, st);
+    int rc;
+    if (pl.esz == 2) rc = pl.bk == 64 ? launch_tile<bf16_t, 64>(a, b, pl, st) : pl.bk == 32 ? launch_tile<bf16_t, 32>(a, b, pl, st) : launch_tile<bf16_t, 16>(a, b, pl, st);
+    else rc = pl.bk == 32 ? launch_tile<float, 32>(a, b, pl, st) : launch_tile<float, 16>(a, b, pl, st);
+    if (rc == 0) g_tile_launches.fetch_add(1, std::memory_order_relaxed);
+    return rc;
 }

@@ -710,9 +710,14 @@ static bool w3_grid(const fpd_wgrad_t& a, W3Grid& g) {
 }
 
 // returns 1 when the shape is outside this kernel's domain (or no slabs were given: the single-block flush stays with wgrad_tile)
+static bool w3_takes(const fpd_wgrad_t& a, W3Grid& g) { return a.partial != nullptr && w3_grid(a, g); }
+bool fpd_wgrad3_takes(const fpd_wgrad_t& a) {      // (the variant query of wgrad_tile.hip)
+    W3Grid g;
+    return w3_takes(a, g);
+}
 int fpd_wgrad3_launch(const fpd_wgrad_t& a, hipStream_t st) {
     W3Grid g;
-    if (a.partial == nullptr || !w3_grid(a, g)) return 1;
+    if (!w3_takes(a, g)) return 1;
     static const int spec = 1;      // specialised waves (wgrad3s); the uniform kernel stays for fpd_set_option-free A/B builds (-DW3_UNIFORM would select it)
     if (spec) {
         static LdsAttr configured_s;

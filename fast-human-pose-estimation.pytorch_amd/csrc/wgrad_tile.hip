@@ -12,6 +12,7 @@
 // fpd_wgrad_reduce() sums in a fixed order, or (no slabs given: one block per tile) straight into dw -- no atomics.
 // Replaces autograd of nn.Conv2d (weight/bias gradient) in /root/reference/lib/models/hourglass.py:20,23,27.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "common.h"
@@ -149,7 +150,10 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const fpd_wgrad_t a, co
         d_goff[i] = (v < nvd) ? px * K + k0 + cv : -1;
         d_loff[i] = px * LD + cv;
     }
-    // a thread always stages the same VEC channels (BLK % vpr_c == 0): keep their BN coefficients in registers
+    // where BLK % vpr_c == 0 a thread always stages the same VEC channels: their BN coefficients are kept in registers.  A channel
+    // tile of 48 (bf16: vpr_c == 6, HRNet-W48's first branch) does not divide the block: vector tid + i * BLK then belongs to
+    // channel group (tid + 2 i) % 6, and stores() reads the coefficients of every vector from the table instead
+    const bool same_cv = BLK % vpr_c == 0;
     float psc[VEC], psh[VEC];
     {
         const int cvh = ((tid % vpr_c) * VEC);
@@ -192,6 +196,11 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const fpd_wgrad_t a, co
                     float f[VEC];
                     DT<T>::unpack(val, f);
                     const bool ok = (hmask >> i) & 1u;
+                    if (!same_cv) {                               // this vector's channels: reload the coefficients from the table
+                        const int cv = h_loff[i] % LD;            // (the pixel part of h_loff is a multiple of LD, cv < CW < LD)
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) { psc[e] = s_scale[cv + e]; psh[e] = s_shift[cv + e]; }
+                    }
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         const float t = bn_act(f[e], psc[e], psh[e], a.bn.relu);
@@ -453,18 +462,51 @@ __global__ __launch_bounds__(256) void wreduce_kernel(const fpd_wreduce_entry_t*
 int fpd_wgrad3_launch(const fpd_wgrad_t& a, hipStream_t st);      // wgrad3.hip: the student's 3x3 64 -> 64 with slabs
 int fpd_wgrad3_partials(const fpd_wgrad_t& a);
 
+bool fpd_wgrad3_takes(const fpd_wgrad_t& a);
+
+namespace {
+// The instantiation of wgrad_tile_kernel a launch runs: the ONE if chain, for the launch and for the variant query.
+struct WtVariant { int r, tp; bool h4, small; };
+bool wt_variant(const fpd_wgrad_t& a, WtGrid& g, WtVariant& v) {
+    if (!wt_grid(a, g)) return false;
+    v = WtVariant{a.R, 128, false, false};
+    if (g.h4) v.h4 = true;
+    else if (a.R == 3 && a.dtype == FPD_BF16 && a.C <= 32 && a.K <= 32) v.small = true;
+    else if (a.R == 1) v.tp = g.tp;
+    return true;
+}
+std::atomic<int> g_wt_launches{0};      // launches of wgrad_tile_kernel (tests: "wgrad_tile_launches"; those handed to wgrad3 are not counted)
+}  // namespace
+
+int fpd_wgrad_tile_launches() { return g_wt_launches.load(std::memory_order_relaxed); }
+
+// dtype | R << 4 | TP << 8 | H4 << 20 | SMALL << 21 | KSPLIT << 22 of the wgrad_tile_kernel instantiation the launch of `a` runs
+// (a.partial set or not, as it will be launched); -1: this unit declines, or wgrad3 takes the launch.
+int fpd_wgrad_tile_variant_of(const fpd_wgrad_t& a) {
+    WtGrid g;
+    WtVariant v;
+    if (fpd_wgrad3_takes(a) || !wt_variant(a, g, v)) return -1;
+    const int nt = v.r * v.r * (v.small || a.dtype != FPD_BF16 ? 1 : 4);      // accumulator tiles against the 8 waves: the kernel's KSPLIT
+    return a.dtype | v.r << 4 | v.tp << 8 | (v.h4 ? 1 : 0) << 20 | (v.small ? 1 : 0) << 21 | (nt <= 4 ? 1 : 0) << 22;
+}
+
 int fpd_wgrad_tile_launch(const fpd_wgrad_t& a, hipStream_t st) {
     if (const int rc3 = fpd_wgrad3_launch(a, st); rc3 != 1) return rc3;
     WtGrid g;
-    if (!wt_grid(a, g)) return 1;
+    WtVariant v;
+    if (!wt_variant(a, g, v)) return 1;
     if (a.partial != nullptr && a.partial_stride < (int64_t)a.K * a.R * a.S * a.C + a.K)
         return fpd_fail(-2, "wgrad: partial_stride %lld smaller than weight + bias", (long long)a.partial_stride);
     if (a.partial == nullptr) g.gx = 1;      // no slabs: one block per (k, c) tile adds straight into dw (deterministic, slow)
-    if (g.h4) return launch_wt<bf16_t, 3, 128, true>(a, g, st);
-    if (a.R == 3 && a.dtype == FPD_BF16 && a.C <= 32 && a.K <= 32) return launch_wt<bf16_t, 3, 128, false, true>(a, g, st);
-    if (a.R == 3) return a.dtype == FPD_BF16 ? launch_wt<bf16_t, 3, 128>(a, g, st) : launch_wt<float, 3, 128>(a, g, st);
-    if (g.tp == 256) return a.dtype == FPD_BF16 ? launch_wt<bf16_t, 1, 256>(a, g, st) : launch_wt<float, 1, 256>(a, g, st);
-    return a.dtype == FPD_BF16 ? launch_wt<bf16_t, 1, 128>(a, g, st) : launch_wt<float, 1, 128>(a, g, st);
+    const bool lp = a.dtype == FPD_BF16;
+    int rc;
+    if (v.h4) rc = launch_wt<bf16_t, 3, 128, true>(a, g, st);
+    else if (v.small) rc = launch_wt<bf16_t, 3, 128, false, true>(a, g, st);
+    else if (v.r == 3) rc = lp ? launch_wt<bf16_t, 3, 128>(a, g, st) : launch_wt<float, 3, 128>(a, g, st);
+    else if (v.tp == 256) rc = lp ? launch_wt<bf16_t, 1, 256>(a, g, st) : launch_wt<float, 1, 256>(a, g, st);
+    else rc = lp ? launch_wt<bf16_t, 1, 128>(a, g, st) : launch_wt<float, 1, 128>(a, g, st);
+    if (rc == 0) g_wt_launches.fetch_add(1, std::memory_order_relaxed);
+    return rc;
 }
 
 int fpd_wgrad_tile_partials(const fpd_wgrad_t& a) {

@@ -323,6 +323,9 @@ SYMBOLS = {
     'fpd_conv_fused_wgrad_partials': (C.c_int, [C.POINTER(ConvT)]),
     'fpd_conv_fold_supported': (C.c_int, [_vp]),
     'fpd_conv_pair_fold_supported': (C.c_int, [_vp]),
+    'fpd_conv_tile_variant': (C.c_int, [_vp]),
+    'fpd_conv_tile_pair_variant': (C.c_int, [_vp]),
+    'fpd_wgrad_tile_variant': (C.c_int, [_vp]),
     'fpd_conv_skip_supported': (C.c_int, [_vp]),
     'fpd_stem_act_supported': (C.c_int, [_vp]),
     'fpd_conv_pair_fused_wgrad_partials': (C.c_int, [C.POINTER(ConvPairT), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -467,6 +467,15 @@ int fpd_conv_fused_wgrad_partials(const fpd_conv_t* a);
  * or not: only the dimensions, epilogue and prologue are looked at); 0 otherwise. */
 int fpd_conv_fold_supported(const fpd_conv_t* a);
 int fpd_conv_pair_fold_supported(const fpd_conv_pair_t* p);
+/* The instantiation of the halo-tile kernel (csrc/conv_tile.hip) that would run this launch / pair launch, decided by the route
+ * function the launch walks; the fold is asked for where fold_x is set.  Pure host code, nothing is dereferenced.
+ *   element size (2 / 4) | BK << 4 | TN << 12 | ALLW << 16 | FOLD << 17,   or -1 where that kernel declines.
+ * (Whether the dispatch reaches that kernel depends on the options "conv_c1" / "conv_c3" / "conv_pp" and the back end.) */
+int fpd_conv_tile_variant(const fpd_conv_t* a);
+int fpd_conv_tile_pair_variant(const fpd_conv_pair_t* p);
+/* ... of wgrad_tile_kernel (csrc/wgrad_tile.hip) for this weight gradient, a->partial set or not as it will be launched:
+ *   dtype | R << 4 | TP << 8 | H4 << 20 | SMALL << 21 | KSPLIT << 22,   or -1 where it declines or hands the launch to wgrad3. */
+int fpd_wgrad_tile_variant(const fpd_wgrad_t* a);
 /* 1 if fpd_conv_forward() would serve this launch WITH its second source (x2, w2, bias2, C2 filled in as they will be
  * launched); 0 otherwise.  Process-wide switch: FPD_FUSE_SKIP=0 / fpd_set_option("conv_skip", 0). */
 int fpd_conv_skip_supported(const fpd_conv_t* a);
@@ -1044,7 +1053,9 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * value changes nothing; a launch without slabs (partial == NULL) keeps its single block; "stem_s2d_launches" /
  * "stem_mfma_launches" = read-only (the value is ignored): fpd_stem_forward() + fpd_stem_wgrad() launches served so far by the
  * space-to-depth kernels (csrc/stem_s2d.hip) / the im2col kernels (csrc/stem_mfma.hip); a stem launch that moves neither was
- * served by the direct kernels (csrc/stem.hip).  Returns the
+ * served by the direct kernels (csrc/stem.hip); "conv_c1_launches" / "conv_c3_launches" / "conv_tile_launches" = read-only:
+ * convolution launches served so far by csrc/conv_c1.hip / conv_c3.hip / conv_tile.hip; "wgrad_tile_launches" = read-only:
+ * launches of wgrad_tile_kernel itself (csrc/wgrad_tile.hip; those its launch function hands to wgrad3 are not counted).  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */
 int fpd_set_option(const char* name, int32_t value);
 int fpd_abi_sizeof(const char* struct_name);  /* sizeof of a struct above, -1 if unknown */

@@ -1,5 +1,7 @@
-"""Input constructions, op lists and case lists of the bit-exact tests of the streaming kernels and of the stem
-(tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py on the device, tests/test_exact_inputs_cpu.py for the preconditions).  No device is needed to import or use this module.
+"""Input constructions, op lists and case lists of the bit-exact tests of the streaming kernels, of the stem, of the halo-tile
+kernels and of the stride-2 convolutions (tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py, tests/test_exact_tile_gpu.py
+on the device; tests/test_exact_inputs_cpu.py for the preconditions, tests/test_exact_variants_cpu.py for the kernel
+instantiations the halo-tile lists reach).  No device is needed to import or use this module.
 
 Everything here is a small dyadic rational, chosen so that the specification (oracle/plan_interp.py) is EXACT: a kernel that
 groups its partial sums differently, folds its coefficients in another order or rounds an fp32 accumulator to bf16 once must
@@ -209,26 +211,45 @@ def budget(n, terms, use_bn):
     return 0.6, max(0.0, min(1.0, (A - 0.09) / 4.0))
 
 
-def forward(bt, gen, dims, wmode, use_bn, use_res, b=None):
-    """conv (R x R, 'same') + bias (+ residual) + output statistics, behind an exact train-mode BN+ReLU prologue or none."""
+def forward(bt, gen, dims, wmode, use_bn, use_res, b=None, stride=1):
+    """conv (R x R, pad (R - 1) / 2, `stride`) + bias (+ residual) + output statistics, behind an exact train-mode BN+ReLU
+    prologue or none."""
     N, H, W, C, K, R = dims
     b = b or Built()
-    density, live = budget(N * H * W, C * R * R if wmode == 'dense' else 2, use_bn)
+    pad = (R - 1) // 2
+    P, Q = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    density, live = budget(N * P * Q, C * R * R if wmode == 'dense' else 2, use_bn)
     xv = small(gen, N, H, W, C, density=density)
     if live is not None:                                  # coarse draw: {-1, 0, 1}
         xv = torch.randint(-1, 2, (N, H, W, C), generator=gen).float() * (xv != 0)
     x = bt.act((N, H, W, C), xv, 'x')
     w = bt.buf('wlp', (K, R, R, C), weights(gen, wmode, K, R, C))
     bias = bt.buf('param', (K,), small(gen, K))
-    res = bt.act((N, H, W, K), small(gen, N, H, W, K), 'res') if use_res else None
-    y = bt.act((N, H, W, K), None, 'y')
+    res = bt.act((N, P, Q, K), small(gen, N, P, Q, K), 'res') if use_res else None
+    y = bt.act((N, P, Q, K), None, 'y')
     bn = b.bn(bt, gen, C, N * H * W, live=live) if use_bn else None
     ostats = bt.buf('stats', (RS, 2, K), torch.zeros(RS, 2, K, dtype=torch.float64))
     op = G.Op('conv', x=x, w=w, wkey='w', bias=bias, bkey='b', residual=res, y=y, out_stats=ostats, bn=bn, epi='plain',
-              epi_x=None, epi_bn=None, epi_stats=None, dims=(N, H, W, C, K, R, R, 1, (R - 1) // 2, H, W))
+              epi_x=None, epi_bn=None, epi_stats=None, dims=(N, H, W, C, K, R, R, stride, pad, P, Q))
     b.ops.append(op)
     b.compare += [('y', y), ('out_stats', ostats)]
     return b, op
+
+
+def wgrad_only(bt, gen, dims, use_bn, stride=1):
+    """A weight gradient as a launch of its own: dw, dbias of conv(relu(bn(x))) (exact per-channel train-mode prologue, or
+    none: the raw x) against dy.  dims = (N, H, W, C, K, R) of the forward convolution."""
+    N, H, W, C, K, R = dims
+    b = Built()
+    pad = (R - 1) // 2
+    P, Q = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    x = bt.act((N, H, W, C), small(gen, N, H, W, C, density=0.6 if use_bn else 0.3), 'x')
+    dy = bt.act((N, P, Q, K), small(gen, N, P, Q, K, density=0.3), 'dy')
+    bn = b.bn(bt, gen, C, N * H * W) if use_bn else None
+    dw, db = bt.buf('grad', (K, R, R, C), torch.zeros(K, R, R, C)), bt.buf('grad', (K,), torch.zeros(K))
+    b.ops.append(G.Op('wgrad', x=x, dy=dy, dw=dw, dbias=db, bn=bn, dims=(N, H, W, C, K, R, R, stride, pad, P, Q)))
+    b.compare += [('dw', dw), ('dbias', db)]
+    return b
 
 
 def dgrad(bt, gen, dims, wmode, fold, fuse, b=None):
@@ -403,7 +424,7 @@ def _check_conv(A, b, op, label):
         _check_bn(A, op.bn, b.bns[op.bn], x, label + ' prologue')
         x = PI._prologue(A, x, op.bn)
     wt = A.view(op.w).float()
-    acc = F.conv2d(_nchw(x.abs()).double(), _nchw(wt.abs()).double(), None, padding=pad)
+    acc = F.conv2d(_nchw(x.abs()).double(), _nchw(wt.abs()).double(), None, stride=stride, padding=pad)
     extra = [A.view(op.bias).double()] if op.bias is not None else []
     extra += [PI._act(A, op.residual).double()] if op.residual is not None else []
     q = min([quantum(x) * quantum(wt)] + [quantum(e) for e in extra])
@@ -425,9 +446,11 @@ def _check_conv(A, b, op, label):
 
 def _check_wgrad(A, b, op, label):
     n, h, w, C, K, R, S, stride, pad, P, Q = op.dims
+    if op.bn is not None:
+        _check_bn(A, op.bn, b.bns[op.bn], PI._act(A, op.x), label + ' prologue')
     a = PI._prologue(A, PI._act(A, op.x), op.bn).double()
     dy = PI._act(A, op.dy).double()
-    tot = torch.nn.grad.conv2d_weight(_nchw(a.abs()), (K, C, R, S), _nchw(dy.abs()), padding=pad)
+    tot = torch.nn.grad.conv2d_weight(_nchw(a.abs()), (K, C, R, S), _nchw(dy.abs()), stride=stride, padding=pad)
     _headroom(tot, quantum(a) * quantum(dy), label + ' dw')
     _headroom(dy.abs().sum((0, 1, 2)), quantum(dy), label + ' dbias')
     assert float(A.view(op.dw).abs().max()) > 0 and float(A.view(op.dbias).abs().max()) > 0, label + ': all-zero gradient'
@@ -558,6 +581,79 @@ PP_BWD = [c[:5] + (c[6],) for c in _tk.FOLD_CASES if c in ((3, 20, 48, 64, 32, 1
 assert (len(PP_BWD), len(C1_PAIR), len(C3_FWD), len(C3_BWD), len(PP_FWD)) == (2, 4, 8, 5, 12), 'a case list this module derives from has changed'
 
 
+# The halo-tile kernels (csrc/conv_tile.hip, csrc/wgrad_tile.hip; tests/test_exact_tile_gpu.py with conv_c1 / conv_c3 / conv_pp
+# off, both storage types).  conv_tile is compiled for T x BK {64, 32, 16} x TN {1, 2, 4} x ALLW x FOLD; which instantiation a
+# shape launches is the library's answer (fpd_conv_tile_variant), and tests/test_exact_variants_cpu.py asserts that these lists
+# reach every instantiation a launch can reach.  The comments name the bf16 variant; fp32 storage chunks by 32 or 16 channels.
+BOTH, BF16, F32 = (1, 0), (1,), (0,)
+# forward: (N, H, W, C, K, R, BN prologue, residual, storage types)
+TILE_FWD = [c + v + (BF16 if c[2] == 128 else BOTH,) for c, v in [
+    ((2, 8, 6, 16, 16, 1), (True, True)),          # BK16 TN1, the smallest of everything
+    ((3, 16, 12, 48, 48, 3), (True, False)),       # BK16 TN1, three chunks, tiles of 10 rows straddling images
+    ((4, 64, 48, 48, 48, 3), (True, True)),        # BK16 TN2: HRNet-W48 branch 1
+    ((4, 64, 48, 48, 96, 3), (True, False)),       # BK16 TN4, 96 of 128 accumulator columns live
+    ((3, 16, 12, 96, 192, 3), (True, True)),       # BK32 TN1
+    ((4, 64, 48, 32, 48, 1), (True, True)),        # BK32 TN2
+    ((4, 64, 48, 32, 48, 3), (False, True)),       # BK32 TN2; fp32: one chunk, ALLW at TN2
+    ((4, 64, 48, 96, 192, 1), (True, False)),      # BK32 TN4
+    ((2, 8, 6, 64, 16, 3), (True, True)),          # BK64 TN1 ALLW
+    ((2, 8, 6, 384, 96, 3), (True, True)),         # BK64 TN1, six chunks
+    ((4, 64, 48, 64, 48, 3), (True, False)),       # BK64 TN2 ALLW
+    ((2, 64, 48, 128, 128, 3), (True, False)),     # BK64 TN2
+    ((2, 64, 48, 192, 256, 1), (True, True)),      # BK64 TN4, all 128 columns live
+    ((2, 44, 48, 48, 384, 3), (True, True)),       # BK16 TN4 with three channel tiles of 128; 44 rows: the last tile of an image ends early
+    ((2, 64, 48, 16, 192, 1), (False, False)),     # BK16 TN4 without a prologue
+    ((1, 6, 128, 64, 64, 3), (True, False)),       # the 64-channel halo of 128-wide rows does not fit: BK32 (fp32: no narrower chunk, declined)
+    ((3, 20, 48, 32, 64, 3), (True, True)),        # ragged tiles; fp32: ALLW at TN1
+    ((5, 7, 6, 384, 96, 3), (False, True)),        # tiles of 21 rows over images of 7
+    ((2, 32, 24, 64, 64, 3), (True, True)),        # tiles of 5 rows straddling images
+]]
+# data gradient: forward convolution (N, H, W, C, K, R): the gradient reads K channels (the chunk) and writes C (the n-tiling).
+# Each runs unfolded and with the fold asked for; FOLD is compiled for TN <= 2 and C, K <= 128 -- (4, 64, 48, 128, 64, 1) runs at
+# TN4: the route declines the fold, the stand-alone apply runs, the result is the same
+TILE_BWD = [
+    (4, 64, 48, 48, 32, 3),       # BK32 TN2 (fp32: ALLW)
+    (4, 64, 48, 64, 128, 1),      # BK64 TN2
+    (2, 64, 48, 128, 64, 3),      # BK64 TN2 ALLW
+    (3, 16, 12, 96, 48, 3),       # BK16 TN1
+    (2, 32, 24, 48, 96, 3),       # BK32 TN1
+    (4, 64, 48, 64, 16, 1),       # BK16 TN2
+    (3, 16, 12, 32, 128, 3),      # BK64 TN1, two chunks
+    (2, 8, 6, 32, 64, 3),         # BK64 TN1 ALLW
+    (3, 16, 12, 48, 32, 3),       # BK32 TN1 (fp32: ALLW)
+    (4, 64, 48, 128, 64, 1),      # BK64 TN4: no FOLD variant
+]
+TILE_BWD_TN4 = (4, 64, 48, 128, 64, 1)
+assert TILE_BWD_TN4 in TILE_BWD
+# pairs (full and half resolution in one launch): (N, H, W, C, K, R, BN prologue, epilogue)
+TILE_PAIR = [c + v for c in [(2, 32, 32, 64, 64, 3), (2, 32, 24, 48, 96, 3), (3, 16, 12, 96, 48, 1)]
+             for v in ((True, 'plain'), (False, 'bnrelu_bwd'))]
+# wgrad_tile_kernel<T, R, TP, H4, SMALL>: (N, H, W, C, K, R, BN prologue, storage types).  bf16 3x3 cases stay outside wgrad3's
+# domain (C = K in {32, 64}, power-of-two width, with slabs); each runs with slabs and, up to 8192 pixels, with the single-block flush
+TILE_WGRAD = [
+    (2, 16, 48, 128, 64, 3, True, BOTH),       # <T, 3, 128>: two (bf16) / four (fp32) channel tiles -- the table is indexed c0 + c
+    (1, 16, 16, 192, 64, 3, True, BOTH),       # three channel tiles, a power-of-two width
+    (2, 16, 48, 48, 96, 3, True, BOTH),        # cn < CW; K tail (96 = 64 + 32)
+    (2, 32, 24, 64, 64, 3, True, BOTH),        # <bf16, 3, 128, H4> (fp32: rows of 24 are k-step aligned, the plain kernel)
+    (3, 16, 12, 128, 32, 3, True, BF16),       # H4 at W = 12, two channel tiles
+    (2, 64, 48, 32, 32, 3, True, BOTH),        # <bf16, 3, 128, false, SMALL>
+    (2, 32, 24, 64, 128, 1, True, BOTH),       # <T, 1, 128>, KSPLIT, an HRNet width
+    (2, 16, 48, 192, 96, 1, True, BOTH),       # ... three channel tiles, K tail
+    (3, 16, 48, 64, 64, 1, False, BOTH),       # ... without a prologue
+    (16, 64, 64, 16, 16, 1, True, BOTH),       # <T, 1, 256>: from 65536 pixels with 256 % W == 0 -- the smallest such shape
+]
+
+
+def wgrad_flushes(case):
+    """The flushes a TILE_WGRAD case runs with: slabs (True) and, on a small problem, the single block per (k, c) tile (False)."""
+    return (True, False) if case[0] * case[1] * case[2] <= 8192 else (True,)
+
+
+# stride 2 (3x3, pad 1; HRNet's transitions and fuse layers, the 3 -> 64 stem convolution): conv_mfma / conv_smallc / conv_naive
+# and their weight gradients.  (N, H, W, C, K) of tests/test_hrnet_gpu.py S2; a BN prologue where C % 8 == 0
+S2 = [(2, 16, 12, 32, 64), (2, 32, 24, 16, 16), (1, 64, 48, 64, 128), (3, 8, 6, 8, 8), (2, 64, 64, 3, 64)]
+
+
 # the stem: (N, H, W, K, blocks) with P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1; at most 4096 output pixels.  blocks = the
 # "stem_blocks" option of the launch (0: the kernels' defaults); tiles are 128 output pixels = 128 / Q whole rows
 def _even(N, P, Q, K, blocks):
@@ -656,6 +752,30 @@ def stem_wgrad(bt, case):
     return stem_weight_gradient(bt, seed('stw', case[:4]), stem_dims(*case[:4]))
 
 
+def tile_forward(bt, case, wmode):
+    return forward(bt, seed('tf', case[:8], wmode), case[:6], wmode, case[6], case[7])[0]
+
+
+def tile_dgrad(bt, case, wmode, fold):
+    return dgrad(bt, seed('tb', case, wmode, fold), case, wmode, fold, False)
+
+
+def tile_pair(bt, case, wmode):
+    return pair(bt, seed('tp', case, wmode), case[:6], wmode, case[6], case[7])
+
+
+def tile_wgrad(bt, case):
+    return wgrad_only(bt, seed('tw', case[:7]), case[:6], case[6])
+
+
+def s2_forward(bt, case, wmode):
+    return forward(bt, seed('s2f', case, wmode), case + (3,), wmode, case[3] % 8 == 0, False, stride=2)[0]
+
+
+def s2_wgrad(bt, case):
+    return wgrad_only(bt, seed('s2w', case), case + (3,), case[3] % 8 == 0, stride=2)
+
+
 _STEM_FWD = STEM_S2D + STEM_MFMA + sorted({c[:4] + (0,) for c in STEM_DIRECT} - set(STEM_S2D))
 _STEM_WG = sorted({c[:4] for c in STEM_WGRAD})
 FAMILIES = [
@@ -671,4 +791,10 @@ FAMILIES = [
     (stem_forward, [(c, m, s) for c in _STEM_FWD for m in WMODES for s in (True, False)]),
     (stem_act, [(c, m) for c in STEM_ACT for m in WMODES]),
     (stem_wgrad, [(c,) for c in _STEM_WG]),
+    (tile_forward, [(c, m) for c in TILE_FWD for m in WMODES]),
+    (tile_dgrad, [(c, m, fo) for c in TILE_BWD for m in WMODES for fo in (False, True)]),
+    (tile_pair, [(c, m) for c in TILE_PAIR for m in WMODES]),
+    (tile_wgrad, [(c,) for c in TILE_WGRAD]),
+    (s2_forward, [(c, m) for c in S2 for m in WMODES]),
+    (s2_wgrad, [(c,) for c in S2]),
 ]

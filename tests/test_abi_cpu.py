@@ -189,6 +189,57 @@ def test_host_side_dispatch_predicates_of_round_3_without_a_device(runtime):
         assert lib.fpd_set_option(name, prev) == default
 
 
+def test_halo_tile_counters_and_variant_queries_without_a_device(runtime):
+    """"conv_tile_launches" / "wgrad_tile_launches" are read-only; fpd_conv_tile_variant() / fpd_conv_tile_pair_variant() /
+    fpd_wgrad_tile_variant() name the instantiation a launch would run (packing: include/fpd_amd.h), -1 where the kernel declines."""
+    import ctypes
+    R, lib = runtime, runtime.lib()
+    for name in (b'conv_tile_launches', b'wgrad_tile_launches'):
+        n = lib.fpd_set_option(name, 0)
+        assert n >= 0 and lib.fpd_set_option(name, n + 5) == n and lib.fpd_set_option(name, 0) == n
+    cv = lambda a: lib.fpd_conv_tile_variant(ctypes.byref(a))
+    pack = lambda esz, bk, tn, allw, fold: esz | bk << 4 | tn << 12 | allw << 16 | fold << 17
+    assert cv(_conv(R, 2, 16, 16, 64, 64, 3, bwd=False)) == pack(2, 64, 1, 1, 0)          # 4 tiles: TN = 1, one chunk, all nine taps staged
+    assert cv(_conv(R, 2, 16, 16, 64, 64, 3, bwd=False, dtype=R.F32)) == pack(4, 32, 1, 0, 0)
+    assert cv(_conv(R, 4, 64, 48, 96, 192, 1, bwd=False)) == pack(2, 32, 4, 0, 0)
+    a = _conv(R, 2, 16, 16, 64, 64, 3)
+    assert cv(a) == pack(2, 64, 1, 1, 0)
+    a.fold_x = 64                                                                        # the fold is asked for where fold_x is set
+    assert cv(a) == pack(2, 64, 1, 1, 1)
+    a = _conv(R, 4, 64, 48, 48, 96, 3)
+    a.fold_x = 64
+    assert cv(a) == pack(2, 16, 4, 0, 0)                                                 # TN = 4: no FOLD variant
+    assert cv(_conv(R, 2, 16, 16, 24, 64, 3, bwd=False)) == -1                           # C not a multiple of 16
+    assert cv(R.ConvT()) == -1 and lib.fpd_conv_tile_variant(None) == -1
+    pair = R.ConvPairT()
+    pair.a, pair.b = _conv(R, 2, 32, 32, 64, 64, 3, bwd=False), _conv(R, 2, 16, 16, 64, 64, 3, bwd=False)
+    assert lib.fpd_conv_tile_pair_variant(ctypes.byref(pair)) == pack(2, 64, 1, 1, 0)
+    pair.b = _conv(R, 2, 16, 16, 64, 32, 3, bwd=False)
+    assert lib.fpd_conv_tile_pair_variant(ctypes.byref(pair)) == -1                      # different K: not pairable
+    w = R.WgradT()
+    w.x = w.dy = w.dw = 64
+    w.N, w.H, w.W, w.C, w.K, w.R, w.S, w.stride, w.pad, w.P, w.Q = 32, 64, 64, 64, 64, 3, 3, 1, 1, 64, 64
+    w.dtype = R.BF16
+    wv = lambda: lib.fpd_wgrad_tile_variant(ctypes.byref(w))
+    wpack = lambda dt, r, tp, h4, small, ks: dt | r << 4 | tp << 8 | h4 << 20 | small << 21 | ks << 22
+    assert wv() == wpack(R.BF16, 3, 128, 0, 0, 0)                                        # no slabs: the single-block flush of wgrad_tile
+    w.partial, w.partial_stride = 64, 64 * 9 * 64 + 64
+    assert wv() == -1                                                                    # with slabs: wgrad3 takes it
+    w.C = w.K = 128
+    assert wv() == wpack(R.BF16, 3, 128, 0, 0, 0)
+    w.C = w.K = 32
+    w.H = w.W = w.P = w.Q = 48
+    assert wv() == wpack(R.BF16, 3, 128, 0, 1, 0)
+    w.H = w.W = w.P = w.Q = 24
+    assert wv() == wpack(R.BF16, 3, 128, 1, 0, 0)
+    w.N, w.H, w.W, w.P, w.Q, w.R, w.S, w.pad = 16, 64, 64, 64, 64, 1, 1, 0
+    assert wv() == wpack(R.BF16, 1, 256, 0, 0, 1)
+    w.dtype, w.N = R.F32, 15
+    assert wv() == wpack(R.F32, 1, 128, 0, 0, 1)
+    w.stride, w.P, w.Q = 2, 32, 32
+    assert wv() == -1 and lib.fpd_wgrad_tile_variant(None) == -1
+
+
 def test_stem_blocks_option_and_slab_queries_without_a_device(runtime):
     """fpd_set_option("stem_blocks"): 0 (the default) leaves every slab count of the stem's weight gradient as it was -- 256
     space-to-depth, 512 im2col, 1024 direct at most, one per tile below that --, n >= 1 caps all three; the launch counters are

@@ -1,4 +1,5 @@
-"""Preconditions of the bit-exact device tests (tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py), checked without a device: for every input
+"""Preconditions of the bit-exact device tests (tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py,
+tests/test_exact_tile_gpu.py), checked without a device: for every input
 construction of tests/_exact_inputs.py and every case of its lists
   * the BatchNorm coefficient identities hold bit for bit -- in the interpreter and in the arithmetic of the device (statistics
     through the limb split, eps = (double)(float)1e-5): invstd == 1.0f, scale == gamma, shift == beta - mu*gamma, mean == mu, and

@@ -100,6 +100,20 @@ class Bench:
                 self.n_c1 = R.set_option('conv_c1_launches', 0) - n0
                 R.set_option('conv_c1', cm)
                 R.set_option('conv_c1_blocks', cb)
+        if backend == 'tile' or (isinstance(backend, tuple) and backend[0] == 'tile'):
+            # the halo-tile kernels (csrc/conv_tile.hip, csrc/wgrad_tile.hip) as the shapes below the streaming kernels' thresholds,
+            # the HRNet path and an fp32 build get them: conv_c1, conv_c3 and conv_pp off.  self.n_tile = convolution launches
+            # conv_tile.hip served, self.n_wtile = launches of wgrad_tile_kernel itself
+            cm, c3m, pm = R.set_option('conv_c1', 0), R.set_option('conv_c3', 0), R.set_option('conv_pp', 0)
+            n0, w0 = R.set_option('conv_tile_launches', 0), R.set_option('wgrad_tile_launches', 0)
+            try:
+                return self.run(ops, 0, partials)
+            finally:
+                self.n_tile = R.set_option('conv_tile_launches', 0) - n0
+                self.n_wtile = R.set_option('wgrad_tile_launches', 0) - w0
+                R.set_option('conv_c1', cm)
+                R.set_option('conv_c3', c3m)
+                R.set_option('conv_pp', pm)
         if isinstance(backend, tuple) and backend[0] in ('bneck', 'head'):
             # ('bneck', n) / ('head', n): grid cap of the persistent fused Bottleneck / head kernel (csrc/bneck_fused.hip,
             # csrc/head_fused.hip), so that a block walks several tiles even on small tensors
