@@ -846,11 +846,14 @@ class FusedFPDStep:
          teacher forward (eval BN) -> student forward (train BN) -> fused pose+KD loss fwd/bwd
          -> student backward -> [RCCL all-reduce of the flat gradient] -> flat Adam (sgd=: flat SGD instead)
          [-> ema=: the weight average of a lib.utils.utils.ModelEma, one more launch in the optimizer's range].
+    clip=: a lib.utils.utils.GradClipper of the student clips the (reduced) gradient to a global L2 norm at the head of the
+    optimizer's range.
     No host synchronisation inside; losses are read back only when asked for."""
 
     def __init__(self, student_state, student_cfg, teacher_state, teacher_cfg, batch, height, width, alpha,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, world_size=1, adam=None, teacher_chunks=None,
-                 use_target_weight=(True, True), ohkm=None, sgd=None, kl=None, ema=None):
+                 use_target_weight=(True, True), ohkm=None, sgd=None, kl=None, ema=None,
+                 clip=None):
         dev = student_state.device
         if adam is not None and sgd is not None:
             raise R.FpdError('FusedFPDStep: adam= and sgd= are mutually exclusive')
@@ -946,7 +949,7 @@ class FusedFPDStep:
         self.n_param = n
         self._dist_work = None
         if sgd is not None:         # share the momentum buffer / step / lr with a lib.utils.utils.FusedSGD; no Adam moments
-            self._add_sgd(sgd, student_state, n, ema)
+            self._add_sgd(sgd, student_state, n, ema, clip)
             return
         if adam is not None:        # share moments / step / lr with a lib.utils.utils.FusedAdam (checkpointable state)
             self.m, self.v, self.lr_dev, self.step_dev = adam.m, adam.v, adam.lr_dev, adam.step_dev
@@ -969,9 +972,24 @@ class FusedFPDStep:
         a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
         self._adam_args = a
         b = len(self.student.plan)
+        self._add_clip(clip, student_state)
         self.student.plan.add(R.OP_ADAM, a)
         self._add_ema(ema, student_state)
         self.student.rng['adam'] = (b, len(self.student.plan))
+
+    def _add_clip(self, clip, student_state):
+        """clip=: one OP_GRAD_CLIP in front of the optimizer op, INSIDE its range -- student_step, the deferred run behind the
+        overlapped all-reduce, flush() and a captured graph all replay that range, so each clips exactly once per update and
+        after the gradients are averaged (the loss kernel folds 1/world into them: every rank sees the same reduced arena, hence
+        the same norm, and no collective is added).  It scales the gradient arena in place, so the optimizer op is unchanged."""
+        self.clip = clip
+        if clip is None:
+            return
+        a = clip.clip_args()
+        if a.grad != student_state.A.tensor('grad').data_ptr() or a.n != student_state.table.sizes['param']:
+            raise R.FpdError('FusedFPDStep: clip= clips the gradient of another model than the student of this step')
+        self._clip_args = a
+        self.student.plan.add(R.OP_GRAD_CLIP, a)
 
     def _add_ema(self, ema, student_state):
         """ema=: one OP_EMA behind the optimizer op, INSIDE its range -- whatever replays that range (student_step, the deferred
@@ -987,7 +1005,7 @@ class FusedFPDStep:
         self._ema_args = a
         self.student.plan.add(R.OP_EMA, a)
 
-    def _add_sgd(self, sgd, student_state, n, ema=None):
+    def _add_sgd(self, sgd, student_state, n, ema=None, clip=None):
         """The optimizer range ('adam' by name, so that run / capture / phase timing need not know) = one OP_SGD with the
         hyperparameters of the FusedSGD's param group as they are NOW (core.function keys its step cache on them)."""
         g = sgd.param_groups[0]
@@ -1004,6 +1022,7 @@ class FusedFPDStep:
         a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
         self._sgd_args = a
         b = len(self.student.plan)
+        self._add_clip(clip, student_state)
         self.student.plan.add(R.OP_SGD, a)
         self._add_ema(ema, student_state)
         self.student.rng['adam'] = (b, len(self.student.plan))

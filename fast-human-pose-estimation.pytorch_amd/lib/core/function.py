@@ -68,11 +68,13 @@ def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
 
 
 def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True), ohkm=None,
-                   kl=None, ema=None):
+                   kl=None, ema=None, clip=None):
     """One FusedFPDStep per (student, teacher, batch shape); shares the optimizer state with the FusedAdam / FusedSGD object.
     tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair;
     kl: its temperature pair.  ema: a utils.ModelEma of the student, averaged inside the step (its decay and warm-up live
     in the recorded plan op, so they are part of the key; the object is compared by identity like the optimizer).
+    clip: a utils.GradClipper of the student (its max_norm lives in the recorded plan op, so it is part of the key; the object
+    is compared by identity).
     A FusedSGD's (momentum, weight_decay, nesterov) live in the recorded plan op, so they are part of the key."""
     s, t = _unwrap(model), (_unwrap(tmodel) if tmodel is not None else None)
     # The cache lives ON the student module (not in a module-level dict keyed by id(): ids are recycled once an object
@@ -88,17 +90,19 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
         key += (('sgd', float(g['momentum']), float(g['weight_decay']), bool(g['nesterov'])),)
     if ema is not None:
         key += (('ema', float(ema.decay), bool(ema.warmup)),)
+    if clip is not None:
+        key += (('clip', float(clip.max_norm)),)
     hit = cache.get(key)
-    if hit is not None and hit[0] is t and hit[1] is optimizer and hit[3] is ema:
+    if hit is not None and hit[0] is t and hit[1] is optimizer and hit[3] is ema and hit[4] is clip:
         return hit[2]
     n, _, h, w = batch_shape
     assert t is not None or alpha == 0.0
     step = E.FusedFPDStep(s.device_state(), s.cfg_hg, t.device_state() if t is not None else None,
                           t.cfg_hg if t is not None else None, n, h, w, alpha,
                           lr=float(optimizer.param_groups[0]['lr']), world_size=world_size,
-                          use_target_weight=use_target_weight, ohkm=ohkm, kl=kl, ema=ema,
+                          use_target_weight=use_target_weight, ohkm=ohkm, kl=kl, ema=ema, clip=clip,
                           **{'sgd' if is_sgd else 'adam': optimizer})
-    cache[key] = (t, optimizer, step, ema)
+    cache[key] = (t, optimizer, step, ema, clip)
     return step
 
 
@@ -128,19 +132,19 @@ def _on_device(t, dev):
 
 
 def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
-               output_dir='', rank=0, ema=None):
+               output_dir='', rank=0, ema=None, clip=None):
     """The loop shared by fpd_train (function.py:99-187) and train (function.py:28-96; tmodel None, alpha 0)."""
     vis, img_writer = _debug_writer(config, rank)
     try:
         return _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
-                               alpha, output_dir, vis, img_writer, ema)
+                               alpha, output_dir, vis, img_writer, ema, clip)
     finally:
         if img_writer is not None:
             img_writer.close()
 
 
 def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
-                    output_dir, vis, img_writer, ema=None):
+                    output_dir, vis, img_writer, ema=None, clip=None):
     kd_mode = tmodel is not None
     use_w, ohkm, kl = crit if len(crit) == 3 else tuple(crit) + (None,)
     batch_time, data_time = AverageMeter(), AverageMeter()
@@ -170,7 +174,7 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
             if step is not None:                       # batch shape changed (last, smaller batch): finish the old step
                 step.flush()
                 drain()
-            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm, kl, ema)
+            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm, kl, ema, clip)
             metric = step.enable_metric(min_slots=config.PRINT_FREQ + 1)   # PCK + losses of every iteration, logged on the device
             metric.drain()
             n_img = inp.size(0)
@@ -212,6 +216,10 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
                       'Accuracy {acc.val:.3f} ({acc.avg:.3f})'.format(
                           epoch, i, len(train_loader), batch_time=batch_time, speed=speed, data_time=data_time,
                           loss=losses, acc=acc)
+            if clip is not None:               # read behind the drain above: the loop's only wait, none is added
+                st = clip.stats()
+                last_norm = clip.norm()
+                msg += '\tGradNorm {last:.4f}  Clipped {clipped}/{calls}'.format(last=last_norm, clipped=st['clipped'], calls=st['calls'])
             logger.info(msg)
             if writer_dict is not None and writer_dict.get('writer') is not None:
                 w, gs = writer_dict['writer'], writer_dict['train_global_steps']
@@ -220,6 +228,8 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
                     w.add_scalar('train_kd_pose_loss', kd_pose_losses.val, gs)
                 w.add_scalar('train_loss', losses.val, gs)
                 w.add_scalar('train_acc', acc.val, gs)
+                if clip is not None:
+                    w.add_scalar('train_grad_norm', last_norm, gs)
                 writer_dict['train_global_steps'] = gs + 1
         else:
             batch_time.update(time.time() - end)
@@ -232,21 +242,22 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
 
 
 def fpd_train(config, train_loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch,
-              output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1, rank=0, ema=None):
+              output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1, rank=0, ema=None, clip=None):
     """function.py:99-187 (same positional signature; allreduce / world_size / rank are the data-parallel extras: only
-    rank 0 writes DEBUG images; ema: a utils.ModelEma of the student, updated inside every fused step).  Returns the epoch's
+    rank 0 writes DEBUG images; ema: a utils.ModelEma of the student, updated inside every fused step; clip: a
+    utils.GradClipper of the student, applied inside every fused step and reported in the `Epoch:` line).  Returns the epoch's
     average loss (the reference returns None)."""
     crit = _check_supported(optimizer, pose_criterion, kd_pose_criterion)
     return _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
-                      float(config.KD.ALPHA), output_dir, rank, ema)['loss']
+                      float(config.KD.ALPHA), output_dir, rank, ema, clip)['loss']
 
 
 def train(config, train_loader, model, criterion, optimizer, epoch, output_dir, tb_log_dir, writer_dict,
-          allreduce=None, world_size=1, rank=0, ema=None):
+          allreduce=None, world_size=1, rank=0, ema=None, clip=None):
     """function.py:28-96: plain (non-distillation) training = the same fused step without a teacher graph (alpha 0)."""
     crit = _check_supported(optimizer, criterion, criterion)
     return _run_epoch(config, train_loader, model, None, crit, optimizer, epoch, writer_dict, allreduce, world_size, 0.0,
-                      output_dir, rank, ema)['loss']
+                      output_dir, rank, ema, clip)['loss']
 
 
 def _to_numpy(v):

@@ -294,6 +294,74 @@ class ModelEma:
             self.warmup = bool(sd['warmup'])
 
 
+class GradClipper:
+    """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) over the model's flat gradient arena as ONE fpd_grad_clip
+    call (csrc/grad_clip.hip: float64 sum of squares, coefficient, in-place scale; three launches, no host wait) -- by
+    clip() between loss.backward() and optimizer.step() on the module-API path, or as the first plan op of the fused step's
+    optimizer range (FusedFPDStep(clip=)).  max_norm = inf measures the norm and scales nothing.  The clipper owns the
+    scratch, the device pair (norm, coef) of the last call and three device counters (calls, clipped, non-finite norm).
+    Create it after .to(device), like the optimizer."""
+
+    def __init__(self, model, max_norm):
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:                   # refuses a NaN too
+            raise ValueError('Invalid max_norm: %r (expected > 0; inf measures without clipping)' % (max_norm,))
+        self.model = model.module if hasattr(model, 'module') else model
+        if not hasattr(self.model, '_flat') or not hasattr(self.model, 'table'):
+            raise R.FpdError('GradClipper: %s is not a HIP-backed model (lib.models)' % type(self.model).__name__)
+        self.max_norm = max_norm
+        dev = self.model._flat['param'].device
+        nbytes = R.lib().fpd_grad_clip_scratch_bytes(self.model.table.sizes['param'])
+        if nbytes < 0:
+            R.check(int(nbytes), 'fpd_grad_clip_scratch_bytes')
+        self.partial = torch.zeros(nbytes // 8, dtype=torch.float64, device=dev)
+        self.out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+        self.counters = torch.zeros(3, dtype=torch.int64, device=dev)
+
+    def clip_args(self):
+        """The filled fpd_grad_clip_t over the gradient arena of the model's device state."""
+        st = self.model.device_state()
+        a = R.GradClipT()
+        a.n, a.grad, a.max_norm = st.table.sizes['param'], st.A.tensor('grad').data_ptr(), self.max_norm
+        a.partial, a.partial_bytes = self.partial.data_ptr(), self.partial.numel() * 8
+        a.out, a.counters = self.out.data_ptr(), self.counters.data_ptr()
+        return a
+
+    @torch.no_grad()
+    def clip(self):
+        """Clip now, on the current stream; returns the device tensor of the norm (no synchronisation)."""
+        R.check(R.lib().fpd_grad_clip(self.clip_args(), R.current_stream()), 'fpd_grad_clip')
+        return self.out[0]
+
+    __call__ = clip
+
+    def norm(self):
+        """Gradient norm of the last call, before clipping -- synchronises."""
+        return float(self.out[0].item())
+
+    def coef(self):
+        """The factor the last call scaled the gradient by (1: not clipped) -- synchronises."""
+        return float(self.out[1].item())
+
+    def stats(self):
+        """{'calls', 'clipped', 'nonfinite'} since creation -- synchronises."""
+        c = self.counters.tolist()
+        return {'calls': c[0], 'clipped': c[1], 'nonfinite': c[2]}
+
+
+def get_grad_clipper(cfg, model):
+    """TRAIN.CLIP_GRAD_NORM -> a GradClipper of `model`: 0 (the default) = none, .inf = measure and log only."""
+    v = cfg.TRAIN.CLIP_GRAD_NORM
+    if isinstance(v, str) and v.lower() in ('.inf', '+.inf'):     # YAML's spelling, as a KEY VALUE pair of the command line
+        v = 'inf'
+    max_norm = float(v)
+    if max_norm == 0.0:
+        return None
+    if not max_norm > 0.0:
+        raise ValueError('TRAIN.CLIP_GRAD_NORM must be 0 (off), positive or .inf (measure only), got %r' % (cfg.TRAIN.CLIP_GRAD_NORM,))
+    return GradClipper(model, max_norm)
+
+
 def multistep_lr(base_lr, milestones, gamma, epoch):
     """Learning rate the reference trains epoch `epoch` with (tools/fpd_train.py:236-239,253: MultiStepLR built with
     last_epoch = -1 and stepped at the START of every epoch, so epoch e runs at the scheduler's value for e + 1, i.e.

@@ -426,6 +426,26 @@ typedef struct {
     int64_t* updates_dev;  /* updates done so far; read by every thread, incremented behind the kernel */
 } fpd_ema_t;
 
+/* torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type = 2, error_if_nonfinite = False) over one flat fp32 gradient
+ * arena, scaled in place, so that every optimizer launch behind it works unchanged.  Arithmetic in csrc/grad_clip_math.h:
+ *   S = sum (double)g[i] * (double)g[i];  norm = (float)sqrt(S);  coef = max_norm / (norm + 1e-6f);  coef > 1 -> 1 (NaN stays)
+ *   g[i] = g[i] * coef                          skipped for the whole arena only when coef == 1 exactly
+ * Three launches on the stream: per-block float64 sums of squares into partial[block] (256 threads a block, the grid cap of
+ * the flat optimizer launches, 16-byte loads where `grad` is 16-byte aligned, element by element otherwise); one block that
+ * adds the partials in index order and writes out[0] = norm, out[1] = coef, counters[0] += 1, counters[1] += (coef < 1),
+ * counters[2] += !isfinite(norm); the scale.  No atomics: the result is a function of the values, n and the alignment.
+ * max_norm = +inf measures without clipping.  n == 0 is legal: norm 0, coef 1.
+ * Refused before any launch: n < 0 or n >= 2^60, a null grad with n > 0, a null out or partial, partial_bytes below
+ * fpd_grad_clip_scratch_bytes(n), a misaligned pointer, max_norm NaN or <= 0, out / partial / counters overlapping grad or
+ * each other. */
+typedef struct {
+    int64_t n; float* grad;          /* flat fp32 arena, scaled in place */
+    float max_norm; int32_t _pad;    /* > 0, +inf allowed */
+    double* partial; int64_t partial_bytes;   /* caller-owned, >= fpd_grad_clip_scratch_bytes(n), 8-byte aligned */
+    float* out;                      /* [2]: norm, coef */
+    int64_t* counters;               /* optional [3]: calls, clipped, non-finite */
+} fpd_grad_clip_t;
+
 /* Per-conv working copies of the weights: cast to `dtype` in K,R,S,C order (forward operand)
  * and the flipped, IO-swapped C,R,S,K copy (data-gradient operand).  One launch for a table. */
 typedef struct {
@@ -515,6 +535,13 @@ int fpd_ema(const fpd_ema_t* a, fpd_stream_t stream);
  * single elements, with a stride of 256 * blocks).  vec_elems[s], s < nseg: the leading elements of segment s moved as
  * 16-byte vectors (a multiple of 4; 0 = the element-by-element path).  Returns 0, or the error code fpd_ema() would give. */
 int fpd_ema_geometry(const fpd_ema_t* a, int32_t* blocks, int64_t* vec_elems);
+int fpd_grad_clip(const fpd_grad_clip_t* a, fpd_stream_t stream);
+/* bytes of `partial` that serve n elements at any alignment of grad (8 per block of the largest grid); negative: n refused */
+int64_t fpd_grad_clip_scratch_bytes(int64_t n);
+/* The launches fpd_grad_clip() makes for `a` as it stands (pure host code, nothing is dereferenced).  blocks: the grid of the
+ * sum and of the scale launch = the partials written; *vec_elems: the leading elements read as 16-byte vectors (a multiple
+ * of 4; 0 = element by element).  Returns 0, or the error code fpd_grad_clip() would give. */
+int fpd_grad_clip_geometry(const fpd_grad_clip_t* a, int32_t* blocks, int64_t* vec_elems);
 int fpd_weight_prep(const fpd_wprep_entry_t* table_dev, int32_t n_entries, int64_t max_elems, int32_t dtype,
                     fpd_stream_t stream);
 int fpd_bn_update_running(const fpd_bnupd_entry_t* table_dev, int32_t n_entries, fpd_stream_t stream);
@@ -1001,7 +1028,8 @@ enum {
     FPD_OP_SGD = 25,            /* args: fpd_sgd_t */
     FPD_OP_EW_MERGE = 26,       /* args: fpd_ew_merge_t */
     FPD_OP_LOSS_KL = 27,        /* args: fpd_loss_kl_t */
-    FPD_OP_EMA = 28             /* args: fpd_ema_t */
+    FPD_OP_EMA = 28,            /* args: fpd_ema_t */
+    FPD_OP_GRAD_CLIP = 29       /* args: fpd_grad_clip_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;

@@ -19,7 +19,9 @@ the pose criterion a JointsOHKMMSELoss(topk=LOSS.TOPK), LOSS.USE_OHKM of the tea
 the reference declares both keys and its tools never read them (its class is never instantiated).  TRAIN.EMA keeps an
 exponential moving average of the student (utils.ModelEma, TRAIN.EMA_DECAY / EMA_WARMUP), updated inside the fused step:
 the per-epoch validation, model_best.pth and final_state.pth then hold the average; checkpoint.pth keeps the raw weights
-(what a resume continues from) and gains ema_state_dict / ema_updates.
+(what a resume continues from) and gains ema_state_dict / ema_updates.  TRAIN.CLIP_GRAD_NORM (0 = off, .inf = measure only)
+clips the gradient of every update to that global L2 norm inside the fused step (utils.GradClipper) and adds `GradNorm` /
+`Clipped` to the `Epoch:` line.
 """
 import argparse
 import logging
@@ -42,8 +44,8 @@ from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa
 from fpd_amd.lib.dataset.device_pipeline import unbiased_targets  # noqa: E402
 from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
 from fpd_amd.lib.core.loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
-from fpd_amd.lib.utils.utils import (ModelEma, get_model_summary, get_optimizer, load_checkpoint, multistep_lr,  # noqa: E402
-                                     save_checkpoint)
+from fpd_amd.lib.utils.utils import (ModelEma, get_grad_clipper, get_model_summary, get_optimizer, load_checkpoint,  # noqa: E402
+                                     multistep_lr, save_checkpoint)
 
 
 def parse_args(description='Train keypoints network (FPD)', with_teacher=True):
@@ -195,6 +197,9 @@ def run(args, normal=False):
 
     optimizer = get_optimizer(cfg, model)                                                     # :218
     ema = ModelEma(model, decay=float(cfg.TRAIN.EMA_DECAY), warmup=bool(cfg.TRAIN.EMA_WARMUP)) if cfg.TRAIN.EMA else None
+    clip = get_grad_clipper(cfg, model)                    # TRAIN.CLIP_GRAD_NORM: None when 0; a negative value raises
+    if clip is not None:
+        logger.info('=> gradient clipping: global L2 norm %g', clip.max_norm)
     begin_epoch, best_perf = cfg.TRAIN.BEGIN_EPOCH, 0.0
     ckpt = os.path.join(out_dir, 'checkpoint.pth')
     if cfg.AUTO_RESUME and os.path.exists(ckpt):                                              # :224-234
@@ -224,10 +229,10 @@ def run(args, normal=False):
         optimizer.param_groups[0]['lr'] = multistep_lr(base_lr, cfg.TRAIN.LR_STEP, cfg.TRAIN.LR_FACTOR, epoch)   # :253
         if train_type == 'FPD':                                                               # :255-264
             loss = fpd_train(cfg, loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch, out_dir,
-                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank, ema=ema)
+                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank, ema=ema, clip=clip)
         else:
             loss = train(cfg, loader, model, pose_criterion, optimizer, epoch, out_dir, cfg.LOG_DIR, writer_dict,
-                         allreduce=allreduce, world_size=world, rank=rank, ema=ema)
+                         allreduce=allreduce, world_size=world, rank=rank, ema=ema, clip=clip)
         torch.cuda.synchronize()
         logger.info('=> epoch %d done in %.1fs, %.1f samples/s, last logged loss %.5f', epoch, time.time() - t0,
                     len(loader) * bs * world / max(time.time() - t0, 1e-9), loss)
