@@ -695,9 +695,37 @@ int fpd_elementwise_pair(const fpd_ew_pair_t* p, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+static int validate_loss_dims(const fpd_loss_t* a, const char* what) {
+    FPD_REQUIRE(a, "%s: null pointer", what);
+    FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0, "%s: non-positive dimension", what);
+    if (a->J > FPD_MAX_JOINTS || a->S > FPD_MAX_STACKS || a->S < 1)
+        return fpd_fail(-3, "%s: J=%d (<=%d), S=%d (1..%d)", what, a->J, FPD_MAX_JOINTS, a->S, FPD_MAX_STACKS);
+    FPD_REQUIRE((int64_t)a->B * a->H * a->W * a->J < ((int64_t)1 << 31), "%s: tensor too large for 32-bit indexing", what);
+    return 0;
+}
+
+// What every loss entry point asks of its fpd_loss_t, before any launch
+static int validate_loss(const fpd_loss_t* a, const char* what) {
+    FPD_REQUIRE(a->teacher && a->target && a->weight && a->losses, "%s: null pointer", what);
+    const int rc = validate_loss_dims(a, what);
+    if (rc) return rc;
+    FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "%s: bad dtype %d", what, a->dtype);
+    for (int s = 0; s < a->S; ++s) FPD_REQUIRE(a->out[s], "%s: null map of stack %d", what, s);
+    return 0;
+}
+
+// The caller's arena of fp64 partial sums against what fpd_<what>_scratch_bytes() answers
+static int validate_loss_scratch(const void* scratch, int64_t bytes, int64_t need, const char* what) {
+    FPD_REQUIRE(scratch && ((uintptr_t)scratch & 7) == 0, "%s: scratch is null or not 8-byte aligned", what);
+    FPD_REQUIRE(bytes >= need, "%s: scratch of %lld bytes, fpd_%s_scratch_bytes() asks for %lld", what, (long long)bytes, what, (long long)need);
+    return 0;
+}
+
 int fpd_loss(const fpd_loss_t* a, fpd_stream_t stream) {
-    FPD_REQUIRE(a && a->teacher && a->target && a->weight && a->losses, "loss: null pointer");
-    int rc = fpd_loss_launch(*a, (hipStream_t)stream);
+    FPD_REQUIRE(a, "loss: null pointer");
+    int rc = validate_loss(a, "loss");
+    if (rc) return rc;
+    rc = fpd_loss_launch(*a, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
 
@@ -711,15 +739,6 @@ int fpd_loss_geometry(const fpd_loss_t* a, int32_t* vectorised, int32_t* blocks,
     return 0;
 }
 
-static int validate_loss_dims(const fpd_loss_t* a, const char* what) {
-    FPD_REQUIRE(a, "%s: null pointer", what);
-    FPD_REQUIRE(a->B > 0 && a->J > 0 && a->H > 0 && a->W > 0, "%s: non-positive dimension", what);
-    if (a->J > FPD_MAX_JOINTS || a->S > FPD_MAX_STACKS || a->S < 1)
-        return fpd_fail(-3, "%s: J=%d (<=%d), S=%d (1..%d)", what, a->J, FPD_MAX_JOINTS, a->S, FPD_MAX_STACKS);
-    FPD_REQUIRE((int64_t)a->B * a->H * a->W * a->J < ((int64_t)1 << 31), "%s: tensor too large for 32-bit indexing", what);
-    return 0;
-}
-
 int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a) {
     const int rc = validate_loss_dims(a, "loss_ohkm_scratch_bytes");
     return rc ? rc : fpd_loss_ohkm_scratch_size(*a);
@@ -728,17 +747,12 @@ int64_t fpd_loss_ohkm_scratch_bytes(const fpd_loss_t* a) {
 int fpd_loss_ohkm(const fpd_loss_ohkm_t* k, fpd_stream_t stream) {
     FPD_REQUIRE(k, "loss_ohkm: null pointer");
     const fpd_loss_t* a = &k->base;
-    FPD_REQUIRE(a->teacher && a->target && a->weight && a->losses, "loss_ohkm: null pointer");
-    int rc = validate_loss_dims(a, "loss_ohkm");
+    int rc = validate_loss(a, "loss_ohkm");
     if (rc) return rc;
-    FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "loss_ohkm: bad dtype %d", a->dtype);
-    for (int s = 0; s < a->S; ++s) FPD_REQUIRE(a->out[s], "loss_ohkm: null map of stack %d", s);
     FPD_REQUIRE(k->topk_pose >= 1 && k->topk_pose <= a->J && k->topk_kd >= 1 && k->topk_kd <= a->J,
                 "loss_ohkm: topk (%d, %d) outside [1, J=%d]", k->topk_pose, k->topk_kd, a->J);
-    const int64_t need = fpd_loss_ohkm_scratch_size(*a);
-    FPD_REQUIRE(k->scratch && ((uintptr_t)k->scratch & 7) == 0, "loss_ohkm: scratch is null or not 8-byte aligned");
-    FPD_REQUIRE(k->scratch_bytes >= need, "loss_ohkm: scratch of %lld bytes, fpd_loss_ohkm_scratch_bytes() asks for %lld",
-                (long long)k->scratch_bytes, (long long)need);
+    rc = validate_loss_scratch(k->scratch, k->scratch_bytes, fpd_loss_ohkm_scratch_size(*a), "loss_ohkm");
+    if (rc) return rc;
     rc = fpd_loss_ohkm_launch(*k, (hipStream_t)stream);
     return rc ? rc : check_launch();
 }
@@ -751,18 +765,13 @@ int64_t fpd_loss_kl_scratch_bytes(const fpd_loss_t* a) {
 int fpd_loss_kl(const fpd_loss_kl_t* k, fpd_stream_t stream) {
     FPD_REQUIRE(k, "loss_kl: null pointer");
     const fpd_loss_t* a = &k->base;
-    FPD_REQUIRE(a->teacher && a->target && a->weight && a->losses, "loss_kl: null pointer");
-    int rc = validate_loss_dims(a, "loss_kl");
+    int rc = validate_loss(a, "loss_kl");
     if (rc) return rc;
-    FPD_REQUIRE(a->dtype == FPD_F32 || a->dtype == FPD_BF16, "loss_kl: bad dtype %d", a->dtype);
-    for (int s = 0; s < a->S; ++s) FPD_REQUIRE(a->out[s], "loss_kl: null map of stack %d", s);
     FPD_REQUIRE(k->kl_pose || k->kl_kd, "loss_kl: neither term is KL (two MSE terms are fpd_loss)");
     FPD_REQUIRE(!k->kl_pose || (k->temp_pose > 0.f && k->temp_pose < INFINITY), "loss_kl: pose temperature %g is not positive", (double)k->temp_pose);
     FPD_REQUIRE(!k->kl_kd || (k->temp_kd > 0.f && k->temp_kd < INFINITY), "loss_kl: distillation temperature %g is not positive", (double)k->temp_kd);
-    const int64_t need = fpd_loss_kl_scratch_size(*a);
-    FPD_REQUIRE(k->scratch && ((uintptr_t)k->scratch & 7) == 0, "loss_kl: scratch is null or not 8-byte aligned");
-    FPD_REQUIRE(k->scratch_bytes >= need, "loss_kl: scratch of %lld bytes, fpd_loss_kl_scratch_bytes() asks for %lld",
-                (long long)k->scratch_bytes, (long long)need);
+    rc = validate_loss_scratch(k->scratch, k->scratch_bytes, fpd_loss_kl_scratch_size(*a), "loss_kl");
+    if (rc) return rc;
     fpd_loss_kl_t kk = *k;
     if (!kk.kl_pose) kk.temp_pose = 1.f;         // (an MSE term's temperature is not read; keep its reciprocal finite)
     if (!kk.kl_kd) kk.temp_kd = 1.f;

@@ -5,81 +5,21 @@
 // effect of nn.BatchNorm2d(momentum=0.1) (lib/models/hourglass.py:10).
 #include <algorithm>
 
-#include "common.h"
+#include "loss_common.h"
 
 namespace {
 
-// Block = 64 consecutive pixels of one image x all J joints.  The fp32 target arrives in the loader's
-// NCHW layout; it is read coalesced along hw and turned through LDS so the NHWC maps are read/written
-// with consecutive lanes on consecutive joints.
-template <typename T>
-__global__ __launch_bounds__(256) void loss_kernel(const fpd_loss_t a) {
-    constexpr int PT = 64;
-    __shared__ float s_tg[PT * 33];       // [pixel][joint] with J <= 32, padded rows
-    __shared__ double s_acc[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int J = a.J, HW = a.H * a.W;
-    const int tiles_per_img = (HW + PT - 1) / PT;
-    const int b = blockIdx.x / tiles_per_img, p0 = (blockIdx.x - b * tiles_per_img) * PT;
-    const int LDJ = J + 1;
-    if (a.target_nchw) {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int j = i / PT, p = i - j * PT;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * J + j) * HW + p0 + p] : 0.f;
-        }
-    } else {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int p = i / J, j = i - p * J;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * HW + p0 + p) * J + j] : 0.f;
-        }
-    }
-    __syncthreads();
-    const double cnt = (double)a.B * J * HW;
-    const float gs = a.grad_scale / (float)cnt;
-    const T* tch = reinterpret_cast<const T*>(a.teacher);
-    float pose = 0.f, kd = 0.f;
-    for (int i = tid; i < J * PT; i += 256) {
-        const int p = i / J, j = i - p * J;
-        if (p0 + p >= HW) continue;
-        const size_t off = ((size_t)b * HW + p0 + p) * J + j;
-        const float wgt = a.weight[b * J + j], w2 = wgt * wgt;
-        const float wk = a.weight_kd ? a.weight_kd[b * J + j] : wgt, w2k = wk * wk;
-        const float g = s_tg[p * LDJ + j];
-        const float t = DT<T>::ld(tch + off);
-        for (int s = 0; s < a.S; ++s) {
-            const float pv = DT<T>::ld(reinterpret_cast<const T*>(a.out[s]) + off);
-            const float dg = pv - g, dt = pv - t;
-            pose += w2 * dg * dg;
-            kd += w2k * dt * dt;
-            if (a.dout[s] != nullptr)
-                DT<T>::st(reinterpret_cast<T*>(a.dout[s]) + off, gs * ((1.f - a.alpha) * w2 * dg + a.alpha * w2k * dt));
-        }
-    }
-    const double dp = wave_sum_d((double)pose), dk = wave_sum_d((double)kd);
-    if (lane == 0) { s_acc[0][wave] = dp; s_acc[1][wave] = dk; }
-    __syncthreads();
-    if (tid == 0) {
-        // Order-independent sum over the blocks (bit-repeatable losses): every contribution is rounded to a multiple of
-        // 2^-44 (5.7e-14), so the fp64 additions are EXACT while the loss stays below 2^9 -- whatever order they arrive in.
-        const double sc = 0.5 / cnt, q = 17592186044416.0;     // 2^44
-        const double vp = sc * (s_acc[0][0] + s_acc[0][1] + s_acc[0][2] + s_acc[0][3]);
-        const double vk = sc * (s_acc[1][0] + s_acc[1][1] + s_acc[1][2] + s_acc[1][3]);
-        atomicAdd(a.losses + 0, rint(vp * q) / q);
-        atomicAdd(a.losses + 1, rint(vk * q) / q);
-    }
-}
-
-// Vectorised variant (J a multiple of the 16-byte vector: 8 joints in bf16, 4 in fp32): block = 128 consecutive pixels of one
-// image; a thread owns ONE 16-byte vector of joints of one pixel for all S stacks -- one vector load per map, one vector store
-// per gradient (the element-per-thread kernel above moves 2-byte words: 65 us for the 2 M elements of the benchmark, on the
-// student's critical chain).  Same arithmetic per element, same per-block sums (fixed order), same grid-aligned loss terms.
+// Block = tpb tiles of PT consecutive pixels of one image x all J joints; a thread owns V joints of one pixel for all S stacks:
+// one load per map, one store per gradient.  Two forms.  <V = DT<T>::VEC, PT = 128>: J a multiple of the 16-byte vector (8 joints
+// in bf16, 4 in fp32) and aligned maps (the element-per-thread form moves 2-byte words: 65 us for the 2 M elements of the
+// benchmark, on the student's critical chain).  <V = 1, PT = 64>, launched with tpb = 1: any J, any alignment.  Same arithmetic
+// per element, same per-block sums (fixed order), same grid-aligned loss terms.
 // Round 5: a block walks `tpb` tiles of its image and adds ONE pair of loss terms at the end.  With a block per tile the 2 x 1 024
 // fp64 atomics of the benchmark shape all hit the same two addresses and serialise in the L2 at ~20 ns each: 36 us for 42 MB of
 // traffic, between the student's forward and backward where nothing else of the chain can run (r05 trace; requesting all maps of a
 // pixel up front changed nothing).
-template <typename T>
-__global__ __launch_bounds__(256) void loss_vec_kernel(const fpd_loss_t a, const int tpb) {
-    constexpr int VEC = DT<T>::VEC, PT = 128;
+template <typename T, int V, int PT>
+__global__ __launch_bounds__(256) void loss_kernel(const fpd_loss_t a, const int tpb) {
     __shared__ float s_tg[PT * 33];       // [pixel][joint], J <= 32, padded rows
     __shared__ double s_acc[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -90,59 +30,47 @@ __global__ __launch_bounds__(256) void loss_vec_kernel(const fpd_loss_t a, const
     const double cnt = (double)a.B * J * HW;
     const float gs = a.grad_scale / (float)cnt;
     const T* tch = reinterpret_cast<const T*>(a.teacher);
-    const int VPP = J / VEC;                     // vectors per pixel
+    const int VPP = J / V;                       // vectors per pixel
     float pose = 0.f, kd = 0.f;
     for (int tt = tile0; tt < min(tile0 + tpb, tiles_per_img); ++tt) {
-    const int p0 = tt * PT;
-    __syncthreads();                             // the previous tile's targets have been read
-    if (a.target_nchw) {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int j = i / PT, p = i - j * PT;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * J + j) * HW + p0 + p] : 0.f;
-        }
-    } else {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int p = i / J, j = i - p * J;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * HW + p0 + p) * J + j] : 0.f;
-        }
-    }
-    __syncthreads();
-    for (int v = tid; v < PT * VPP; v += 256) {
-        const int p = v / VPP, j0 = (v - p * VPP) * VEC;
-        if (p0 + p >= HW) continue;
-        const size_t off = ((size_t)b * HW + p0 + p) * J + j0;
-        float w2[VEC], w2k[VEC], g[VEC], t[VEC];
+        const int p0 = tt * PT;
+        __syncthreads();                         // the previous tile's targets have been read
+        load_target_tile<PT>(a, b, p0, s_tg);
+        __syncthreads();
+        for (int v = tid; v < PT * VPP; v += 256) {
+            const int p = v / VPP, j0 = (v - p * VPP) * V;
+            if (p0 + p >= HW) continue;
+            const size_t off = ((size_t)b * HW + p0 + p) * J + j0;
+            float w2[V], w2k[V], g[V], t[V];
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float wgt = a.weight[b * J + j0 + e];
-            const float wk = a.weight_kd ? a.weight_kd[b * J + j0 + e] : wgt;
-            w2[e] = wgt * wgt; w2k[e] = wk * wk;
-            g[e] = s_tg[p * LDJ + j0 + e];
-        }
-        DT<T>::unpack(*reinterpret_cast<const uint4*>(tch + off), t);
-        for (int s = 0; s < a.S; ++s) {
-            float pv[VEC], d[VEC];
-            DT<T>::unpack(*reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.out[s]) + off), pv);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float dg = pv[e] - g[e], dt = pv[e] - t[e];
-                pose += w2[e] * dg * dg;
-                kd += w2k[e] * dt * dt;
-                d[e] = gs * ((1.f - a.alpha) * w2[e] * dg + a.alpha * w2k[e] * dt);
+            for (int e = 0; e < V; ++e) {
+                const float wgt = a.weight[b * J + j0 + e];
+                const float wk = a.weight_kd ? a.weight_kd[b * J + j0 + e] : wgt;
+                w2[e] = wgt * wgt; w2k[e] = wk * wk;
+                g[e] = s_tg[p * LDJ + j0 + e];
             }
-            if (a.dout[s] != nullptr) *reinterpret_cast<uint4*>(reinterpret_cast<T*>(a.dout[s]) + off) = DT<T>::pack(d);
+            ld_vec<T, V>(tch + off, t);
+            for (int s = 0; s < a.S; ++s) {
+                float pv[V], d[V];
+                ld_vec<T, V>(reinterpret_cast<const T*>(a.out[s]) + off, pv);
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    const float dg = pv[e] - g[e], dt = pv[e] - t[e];
+                    pose += w2[e] * dg * dg;
+                    kd += w2k[e] * dt * dt;
+                    d[e] = gs * ((1.f - a.alpha) * w2[e] * dg + a.alpha * w2k[e] * dt);
+                }
+                if (a.dout[s] != nullptr) st_vec<T, V>(reinterpret_cast<T*>(a.dout[s]) + off, d);
+            }
         }
     }
-    }                                            // tiles of this block
     const double dp = wave_sum_d((double)pose), dk = wave_sum_d((double)kd);
     if (lane == 0) { s_acc[0][wave] = dp; s_acc[1][wave] = dk; }
     __syncthreads();
     if (tid == 0) {
-        const double sc = 0.5 / cnt, q = 17592186044416.0;     // 2^44 (see loss_kernel)
-        const double vp = sc * (s_acc[0][0] + s_acc[0][1] + s_acc[0][2] + s_acc[0][3]);
-        const double vk = sc * (s_acc[1][0] + s_acc[1][1] + s_acc[1][2] + s_acc[1][3]);
-        atomicAdd(a.losses + 0, rint(vp * q) / q);
-        atomicAdd(a.losses + 1, rint(vk * q) / q);
+        const double sc = 0.5 / cnt;
+        loss_add_aligned(a.losses, 0, sc * (s_acc[0][0] + s_acc[0][1] + s_acc[0][2] + s_acc[0][3]));
+        loss_add_aligned(a.losses, 1, sc * (s_acc[1][0] + s_acc[1][1] + s_acc[1][2] + s_acc[1][3]));
     }
 }
 
@@ -302,21 +230,13 @@ __global__ void nhwc_to_nchw_kernel(const T* src, float* dst, int N, int C, int 
 // below and the query fpd_loss_geometry() both come through here.
 int fpd_loss_geometry_of(const fpd_loss_t& a, int* vectorised, int* blocks, int* tiles_per_block) {
     if (a.J > 32 || a.S > FPD_MAX_STACKS || a.S < 1) return fpd_fail(-3, "loss: J=%d (<=32), S=%d (1..%d)", a.J, a.S, FPD_MAX_STACKS);
-    const int vec = a.dtype == FPD_BF16 ? 8 : 4;
-    bool aligned = a.J % vec == 0 && ((uintptr_t)a.teacher & 15) == 0;
-    for (int s = 0; s < a.S; ++s) aligned = aligned && ((uintptr_t)a.out[s] & 15) == 0 && ((uintptr_t)a.dout[s] & 15) == 0;
-    *vectorised = aligned ? 1 : 0;
-    if (aligned) {                               // 16-byte vectors of joints (the benchmark's J = 16)
-        // <= 256 blocks (= 512 same-address atomics), tiles of one image per block
-        const int tpi = cdiv(a.H * a.W, 128);
-        int tpb = 1;
-        while (a.B * cdiv(tpi, tpb) > 256 && tpb < tpi) ++tpb;
-        *tiles_per_block = tpb;
-        *blocks = a.B * cdiv(tpi, tpb);
-        return 0;
-    }
-    *tiles_per_block = 1;                        // a block per 64-pixel tile
-    *blocks = a.B * cdiv(a.H * a.W, 64);
+    const int V = loss_vector_width(a);
+    // 16-byte vectors of joints (the benchmark's J = 16): 128-pixel tiles, <= 256 blocks (= 512 same-address atomics), tiles of
+    // one image per block.  Else a block per 64-pixel tile, however many.
+    const LossGeo g = V > 1 ? loss_geo(a, V, 128, 256) : loss_geo(a, 1, 64, INT_MAX);
+    *vectorised = V > 1 ? 1 : 0;
+    *tiles_per_block = g.tpb;
+    *blocks = a.B * g.cpi;
     return 0;
 }
 
@@ -324,17 +244,11 @@ int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st) {
     int vectorised = 0, blocks = 0, tpb = 0;
     const int rc = fpd_loss_geometry_of(a, &vectorised, &blocks, &tpb);
     if (rc) return rc;
-    if (vectorised) {
-        if (a.dtype == FPD_BF16)
-            FPD_LAUNCH((loss_vec_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, a, tpb);
-        else
-            FPD_LAUNCH((loss_vec_kernel<float>), dim3(blocks), dim3(256), 0, st, a, tpb);
-        return 0;
-    }
-    if (a.dtype == FPD_BF16)
-        FPD_LAUNCH((loss_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, a);
-    else
-        FPD_LAUNCH((loss_kernel<float>), dim3(blocks), dim3(256), 0, st, a);
+    loss_dispatch(a, [&](auto t, auto v) {
+        using T = typename decltype(t)::type;
+        constexpr int V = decltype(v)::value;
+        FPD_LAUNCH((loss_kernel<T, V, (V > 1 ? 128 : 64)>), dim3(blocks), dim3(256), 0, st, a, tpb);
+    });
     return 0;
 }
 

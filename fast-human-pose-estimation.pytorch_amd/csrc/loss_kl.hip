@@ -8,15 +8,16 @@
 // no logarithm of a probability is taken, and a reference row that equals the student row gives exactly 0 (same statistics
 // routine, same order, a_x - b_x == 0).
 //
-// Fixed order throughout, no floating-point atomics but the grid-aligned loss terms (see loss_adam.hip): results are
+// Fixed order throughout, no floating-point atomics but the grid-aligned loss terms (see loss_common.h): results are
 // bit-repeatable and nothing needs zeroing but `losses`.  Geometry, the LDS turn of an NCHW target and the vector / scalar joint
-// split are loss_ohkm.hip's.
+// split are loss_common.h's, shared with loss_ohkm.hip.
 //   1. kl_rows_kernel: block = (image, chunk of 128-pixel tiles).  Pass A takes the maximum of every row over the block's
 //      pixels and sums the MSE terms; pass B (the same pixels, now cache-resident) sums exp((x - M)/T) row by row -- one exp per
 //      element, no rescaling.  The block stores (M, Z) of every row and its two MSE sums to its own slab of the caller's scratch.
 //   2. kl_grad_kernel: same grid; a block merges the slabs of its image in chunk order (fp64, the usual rescaling rule), walks
 //      its pixels once more, writes the gradient with one rounding and adds its share of the two loss terms.
 #include "conv_dispatch.h"
+#include "loss_common.h"
 
 // "equal rows give exactly zero" needs a product rounded the same way wherever it is formed: no contraction into an fma
 #pragma clang fp contract(off)
@@ -24,51 +25,18 @@
 namespace {
 
 constexpr int PT = 128;                  // pixels per LDS tile of the target
-constexpr int KL_MAX_BLOCKS = 512;       // a block of launch 2 re-reads the slabs of its image: few chunks per image
-
-struct KlGeo {
-    int tpb;       // tiles a block walks
-    int cpi;       // chunks (= blocks) per image
-    int vpad;      // joint vectors per pixel, rounded up to a power of two: lanes vpad apart hold the same joints
-};
+constexpr int MAX_BLOCKS = 512;          // a block of launch 2 re-reads the slabs of its image: few chunks per image
 
 // Rows of statistics.  Maxima do not depend on the temperature: [0, S) the stacks, S the target, S + 1 the teacher map.
 // Sums do: 2 s + t the stack s at the temperature of term t (0 pose, 1 kd), 2 S the target (pose), 2 S + 1 the teacher (kd).
 // Slab of one block, in doubles: M [S + 2][J], Z [2 S + 2][J], the two MSE sums.
 __host__ __device__ __forceinline__ int slab_doubles(int S, int J) { return (3 * S + 4) * J + 2; }
 
-template <typename T, int V>
-__device__ __forceinline__ void ld_vec(const T* p, float* f) {
-    if constexpr (V == 1) f[0] = DT<T>::ld(p);
-    else DT<T>::unpack(*reinterpret_cast<const uint4*>(p), f);
-}
-template <typename T, int V>
-__device__ __forceinline__ void st_vec(T* p, const float* f) {
-    if constexpr (V == 1) DT<T>::st(p, f[0]);
-    else *reinterpret_cast<uint4*>(p) = DT<T>::pack(f);
-}
-
-// targets of pixels [p0, p0 + PT) of image b -> s_tg[pixel][joint] (rows padded to J + 1); callers synchronise around it
-__device__ __forceinline__ void load_target_tile(const fpd_loss_t& a, int b, int p0, float* s_tg) {
-    const int J = a.J, HW = a.H * a.W, LDJ = J + 1, tid = threadIdx.x;
-    if (a.target_nchw) {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int j = i / PT, p = i - j * PT;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * J + j) * HW + p0 + p] : 0.f;
-        }
-    } else {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int p = i / J, j = i - p * J;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * HW + p0 + p) * J + j] : 0.f;
-        }
-    }
-}
-
 // V joints per thread: a 16-byte vector (J a multiple of it, aligned maps) or one element (any J).  A thread keeps ONE joint
 // vector jv = tid % vpad for all its pixels.  Which term is KL is compiled in, so that a launch carries the state of its own
 // terms only; the row statistics of the second launch stay in LDS (a thread has few pixels: registers would buy nothing).
 template <typename T, int V, int SMAX, bool KLP, bool KLK>
-__global__ __launch_bounds__(256) void kl_rows_kernel(const fpd_loss_kl_t k, const KlGeo geo) {
+__global__ __launch_bounds__(256) void kl_rows_kernel(const fpd_loss_kl_t k, const LossGeo geo) {
     const fpd_loss_t& a = k.base;
     constexpr int NM = SMAX + 2, NZ = 2 * SMAX + 2;
     __shared__ float s_tg[PT * 33];
@@ -103,7 +71,7 @@ __global__ __launch_bounds__(256) void kl_rows_kernel(const fpd_loss_kl_t k, con
         for (int tt = tile0; tt < tile1; ++tt) {
             const int p0 = tt * PT;
             __syncthreads();                     // the previous tile's targets have been read
-            load_target_tile(a, b, p0, s_tg);
+            load_target_tile<PT>(a, b, p0, s_tg);
             __syncthreads();
             if (!on) continue;
             for (int p = pl; p < PT && p0 + p < HW; p += ppi) {
@@ -162,7 +130,7 @@ __global__ __launch_bounds__(256) void kl_rows_kernel(const fpd_loss_kl_t k, con
             const int p0 = tt * PT;
             if (tgt && geo.tpb > 1) {            // (with one tile per block pass A has left it in place)
                 __syncthreads();
-                load_target_tile(a, b, p0, s_tg);
+                load_target_tile<PT>(a, b, p0, s_tg);
                 __syncthreads();
             }
             if (!on) continue;
@@ -207,7 +175,7 @@ __global__ __launch_bounds__(256) void kl_rows_kernel(const fpd_loss_kl_t k, con
 }
 
 template <typename T, int V, int SMAX, bool KLP, bool KLK>
-__global__ __launch_bounds__(256) void kl_grad_kernel(const fpd_loss_kl_t k, const KlGeo geo) {
+__global__ __launch_bounds__(256) void kl_grad_kernel(const fpd_loss_kl_t k, const LossGeo geo) {
     const fpd_loss_t& a = k.base;
     constexpr int NM = SMAX + 2, NZ = 2 * SMAX + 2;
     __shared__ float s_tg[PT * 33];
@@ -282,7 +250,7 @@ __global__ __launch_bounds__(256) void kl_grad_kernel(const fpd_loss_kl_t k, con
     for (int tt = tile0; tt < tile1; ++tt) {
         const int p0 = tt * PT;
         __syncthreads();
-        load_target_tile(a, b, p0, s_tg);
+        load_target_tile<PT>(a, b, p0, s_tg);
         __syncthreads();
         if (!on) continue;
         for (int p = pl; p < PT && p0 + p < HW; p += ppi) {
@@ -347,62 +315,35 @@ __global__ __launch_bounds__(256) void kl_grad_kernel(const fpd_loss_kl_t k, con
         } else {
             v = s_mse[tid] * (0.5 / cnt);
         }
-        const double q = 17592186044416.0;       // 2^44: grid-aligned terms, exact in any order (see loss_kernel)
-        atomicAdd(a.losses + tid, rint(v * q) / q);
+        loss_add_aligned(a.losses, tid, v);
     }
 }
 
-KlGeo kl_geo(const fpd_loss_t& a, int V) {
-    KlGeo g;
-    const int tpi = cdiv(a.H * a.W, PT);
-    g.tpb = 1;
-    while (a.B * cdiv(tpi, g.tpb) > KL_MAX_BLOCKS && g.tpb < tpi) ++g.tpb;
-    g.cpi = cdiv(tpi, g.tpb);
-    g.vpad = 1;
-    while (g.vpad * V < a.J) g.vpad <<= 1;
-    return g;
-}
-
 template <typename T, int V, int SMAX, bool KLP, bool KLK>
-void kl_launch_m(const fpd_loss_kl_t& k, const KlGeo& g, hipStream_t st) {
+void kl_launch_m(const fpd_loss_kl_t& k, const LossGeo& g, hipStream_t st) {
     const dim3 grid((unsigned)(k.base.B * g.cpi));
     FPD_LAUNCH((kl_rows_kernel<T, V, SMAX, KLP, KLK>), grid, dim3(256), 0, st, k, g);
     FPD_LAUNCH((kl_grad_kernel<T, V, SMAX, KLP, KLK>), grid, dim3(256), 0, st, k, g);
 }
 template <typename T, int V, int SMAX>
-void kl_launch(const fpd_loss_kl_t& k, const KlGeo& g, hipStream_t st) {
+void kl_launch(const fpd_loss_kl_t& k, const LossGeo& g, hipStream_t st) {
     if (k.kl_pose && k.kl_kd) kl_launch_m<T, V, SMAX, true, true>(k, g, st);
     else if (k.kl_pose) kl_launch_m<T, V, SMAX, true, false>(k, g, st);
     else kl_launch_m<T, V, SMAX, false, true>(k, g, st);
 }
-template <typename T, int V>
-void kl_launch_s(const fpd_loss_kl_t& k, const KlGeo& g, hipStream_t st) {
-    const int S = k.base.S;      // register budget of the row statistics follows the stack count
-    if (S == 1) kl_launch<T, V, 1>(k, g, st);
-    else if (S == 2) kl_launch<T, V, 2>(k, g, st);
-    else if (S <= 4) kl_launch<T, V, 4>(k, g, st);
-    else kl_launch<T, V, FPD_MAX_STACKS>(k, g, st);
-}
-
 }  // namespace
 
 int64_t fpd_loss_kl_scratch_size(const fpd_loss_t& a) {
-    const KlGeo g = kl_geo(a, 1);                // (tpb, cpi do not depend on the vector width)
+    const LossGeo g = loss_geo(a, 1, PT, MAX_BLOCKS);
     return (int64_t)a.B * g.cpi * slab_doubles(a.S, a.J) * (int64_t)sizeof(double);
 }
 
 int fpd_loss_kl_launch(const fpd_loss_kl_t& k, hipStream_t st) {
-    const fpd_loss_t& a = k.base;
-    const int vec = a.dtype == FPD_BF16 ? 8 : 4;
-    bool aligned = a.J % vec == 0 && ((uintptr_t)a.teacher & 15) == 0;
-    for (int s = 0; s < a.S; ++s) aligned = aligned && ((uintptr_t)a.out[s] & 15) == 0 && ((uintptr_t)a.dout[s] & 15) == 0;
-    const KlGeo g = kl_geo(a, aligned ? vec : 1);
-    if (a.dtype == FPD_BF16) {
-        if (aligned) kl_launch_s<bf16_t, 8>(k, g, st);
-        else kl_launch_s<bf16_t, 1>(k, g, st);
-    } else {
-        if (aligned) kl_launch_s<float, 4>(k, g, st);
-        else kl_launch_s<float, 1>(k, g, st);
-    }
+    loss_dispatch(k.base, [&](auto t, auto v) {
+        using T = typename decltype(t)::type;
+        constexpr int V = decltype(v)::value;
+        const LossGeo g = loss_geo(k.base, V, PT, MAX_BLOCKS);
+        loss_dispatch_stacks(k.base.S, [&](auto smax) { kl_launch<T, V, decltype(smax)::value>(k, g, st); });
+    });
     return 0;
 }

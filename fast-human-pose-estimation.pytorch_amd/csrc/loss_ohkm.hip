@@ -4,58 +4,26 @@
 // L[n,:] of every sample are kept (among equal L the LOWER joint index wins), loss = 1/(B k) * sum of the kept L.  k = J keeps
 // every joint = JointsMSELoss, which is how a mixed pair (one criterion OHKM, the other MSE) is evaluated.
 //
-// Fixed order throughout, no floating-point atomics but the two grid-aligned loss terms (see loss_adam.hip): results are
+// Fixed order throughout, no floating-point atomics but the two grid-aligned loss terms (see loss_common.h): results are
 // bit-repeatable and nothing needs zeroing but `losses`.
 //   1. ohkm_rows_kernel: block = (image, chunk of 128-pixel tiles); reads every stack's map, the target (turned through LDS like
-//      loss_vec_kernel) and the teacher map once and stores its partial sum w^2 (p-r)^2 of every (stack, term, joint) to its
+//      loss_kernel) and the teacher map once and stores its partial sum w^2 (p-r)^2 of every (stack, term, joint) to its
 //      own slab of the caller's scratch: double [B][chunks][S][2][J].
 //   2. ohkm_grad_kernel: same grid; a block adds the slabs of its image in chunk order (fp64), ranks the joints of every
 //      (stack, term) into a one-word mask, and writes the masked gradient of its pixels with one rounding.  The chunk-0 block
 //      of an image adds the image's two loss terms and stores the masks.
 #include "conv_dispatch.h"
+#include "loss_common.h"
 
 namespace {
 
 constexpr int PT = 128;                  // pixels per LDS tile of the target
-constexpr int OHKM_MAX_BLOCKS = 512;     // a block of launch 2 re-reads the slabs of its image: few chunks per image
-
-struct OhkmGeo {
-    int tpb;       // tiles a block walks
-    int cpi;       // chunks (= blocks) per image
-    int vpad;      // joint vectors per pixel, rounded up to a power of two: lanes vpad apart hold the same joints
-};
-
-template <typename T, int V>
-__device__ __forceinline__ void ld_vec(const T* p, float* f) {
-    if constexpr (V == 1) f[0] = DT<T>::ld(p);
-    else DT<T>::unpack(*reinterpret_cast<const uint4*>(p), f);
-}
-template <typename T, int V>
-__device__ __forceinline__ void st_vec(T* p, const float* f) {
-    if constexpr (V == 1) DT<T>::st(p, f[0]);
-    else *reinterpret_cast<uint4*>(p) = DT<T>::pack(f);
-}
-
-// targets of pixels [p0, p0 + PT) of image b -> s_tg[pixel][joint] (rows padded to J + 1); callers synchronise around it
-__device__ __forceinline__ void load_target_tile(const fpd_loss_t& a, int b, int p0, float* s_tg) {
-    const int J = a.J, HW = a.H * a.W, LDJ = J + 1, tid = threadIdx.x;
-    if (a.target_nchw) {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int j = i / PT, p = i - j * PT;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * J + j) * HW + p0 + p] : 0.f;
-        }
-    } else {
-        for (int i = tid; i < J * PT; i += 256) {
-            const int p = i / J, j = i - p * J;
-            s_tg[p * LDJ + j] = (p0 + p < HW) ? a.target[((size_t)b * HW + p0 + p) * J + j] : 0.f;
-        }
-    }
-}
+constexpr int MAX_BLOCKS = 512;          // a block of launch 2 re-reads the slabs of its image: few chunks per image
 
 // V joints per thread: a 16-byte vector (J a multiple of it, aligned maps) or one element (any J).  A thread keeps ONE joint
 // vector jv = tid % vpad for all its pixels, so its sums stay in registers: SMAX stacks x 2 terms x V joints.
 template <typename T, int V, int SMAX>
-__global__ __launch_bounds__(256) void ohkm_rows_kernel(const fpd_loss_ohkm_t k, const OhkmGeo geo) {
+__global__ __launch_bounds__(256) void ohkm_rows_kernel(const fpd_loss_ohkm_t k, const LossGeo geo) {
     const fpd_loss_t& a = k.base;
     __shared__ float s_tg[PT * 33];
     __shared__ double s_w[4][SMAX * 2 * 32];     // per wave: [stack][term][joint]
@@ -81,7 +49,7 @@ __global__ __launch_bounds__(256) void ohkm_rows_kernel(const fpd_loss_ohkm_t k,
     for (int tt = tile0; tt < min(tile0 + geo.tpb, tiles_per_img); ++tt) {
         const int p0 = tt * PT;
         __syncthreads();                         // the previous tile's targets have been read
-        load_target_tile(a, b, p0, s_tg);
+        load_target_tile<PT>(a, b, p0, s_tg);
         __syncthreads();
         if (!on) continue;
         for (int p = pl; p < PT && p0 + p < HW; p += ppi) {
@@ -126,7 +94,7 @@ __global__ __launch_bounds__(256) void ohkm_rows_kernel(const fpd_loss_ohkm_t k,
 }
 
 template <typename T, int V, int SMAX>
-__global__ __launch_bounds__(256) void ohkm_grad_kernel(const fpd_loss_ohkm_t k, const OhkmGeo geo) {
+__global__ __launch_bounds__(256) void ohkm_grad_kernel(const fpd_loss_ohkm_t k, const LossGeo geo) {
     const fpd_loss_t& a = k.base;
     __shared__ float s_tg[PT * 33];
     __shared__ double s_row[SMAX * 2 * 32];      // sum w^2 (p-r)^2 over the image: [stack][term][joint]
@@ -179,8 +147,7 @@ __global__ __launch_bounds__(256) void ohkm_grad_kernel(const fpd_loss_ohkm_t k,
             double v = 0.0;
             for (int s = 0; s < S; ++s) v += s_pair[s * 2 + tid];
             v *= 0.5 / (bhw * (tid ? k.topk_kd : k.topk_pose));
-            const double q = 17592186044416.0;   // 2^44: grid-aligned terms, exact in any order (see loss_kernel)
-            atomicAdd(a.losses + tid, rint(v * q) / q);
+            loss_add_aligned(a.losses, tid, v);
         }
     }
     if (!grads) return;
@@ -205,7 +172,7 @@ __global__ __launch_bounds__(256) void ohkm_grad_kernel(const fpd_loss_ohkm_t k,
     for (int tt = tile0; tt < min(tile0 + geo.tpb, tiles_per_img); ++tt) {
         const int p0 = tt * PT;
         __syncthreads();
-        load_target_tile(a, b, p0, s_tg);
+        load_target_tile<PT>(a, b, p0, s_tg);
         __syncthreads();
         if (!on) continue;
         for (int p = pl; p < PT && p0 + p < HW; p += ppi) {
@@ -231,51 +198,26 @@ __global__ __launch_bounds__(256) void ohkm_grad_kernel(const fpd_loss_ohkm_t k,
     }
 }
 
-OhkmGeo ohkm_geo(const fpd_loss_t& a, int V) {
-    OhkmGeo g;
-    const int tpi = cdiv(a.H * a.W, PT);
-    g.tpb = 1;
-    while (a.B * cdiv(tpi, g.tpb) > OHKM_MAX_BLOCKS && g.tpb < tpi) ++g.tpb;
-    g.cpi = cdiv(tpi, g.tpb);
-    g.vpad = 1;
-    while (g.vpad * V < a.J) g.vpad <<= 1;
-    return g;
-}
-
 template <typename T, int V, int SMAX>
-void ohkm_launch(const fpd_loss_ohkm_t& k, const OhkmGeo& g, hipStream_t st) {
+void ohkm_launch(const fpd_loss_ohkm_t& k, const LossGeo& g, hipStream_t st) {
     const dim3 grid((unsigned)(k.base.B * g.cpi));
     FPD_LAUNCH((ohkm_rows_kernel<T, V, SMAX>), grid, dim3(256), 0, st, k, g);
     FPD_LAUNCH((ohkm_grad_kernel<T, V, SMAX>), grid, dim3(256), 0, st, k, g);
-}
-template <typename T, int V>
-void ohkm_launch_s(const fpd_loss_ohkm_t& k, const OhkmGeo& g, hipStream_t st) {
-    const int S = k.base.S;      // register budget of the row sums follows the stack count
-    if (S == 1) ohkm_launch<T, V, 1>(k, g, st);
-    else if (S == 2) ohkm_launch<T, V, 2>(k, g, st);
-    else if (S <= 4) ohkm_launch<T, V, 4>(k, g, st);
-    else ohkm_launch<T, V, FPD_MAX_STACKS>(k, g, st);
 }
 
 }  // namespace
 
 int64_t fpd_loss_ohkm_scratch_size(const fpd_loss_t& a) {
-    const OhkmGeo g = ohkm_geo(a, 1);            // (tpb, cpi do not depend on the vector width)
+    const LossGeo g = loss_geo(a, 1, PT, MAX_BLOCKS);
     return (int64_t)a.B * g.cpi * a.S * 2 * a.J * (int64_t)sizeof(double);
 }
 
 int fpd_loss_ohkm_launch(const fpd_loss_ohkm_t& k, hipStream_t st) {
-    const fpd_loss_t& a = k.base;
-    const int vec = a.dtype == FPD_BF16 ? 8 : 4;
-    bool aligned = a.J % vec == 0 && ((uintptr_t)a.teacher & 15) == 0;
-    for (int s = 0; s < a.S; ++s) aligned = aligned && ((uintptr_t)a.out[s] & 15) == 0 && ((uintptr_t)a.dout[s] & 15) == 0;
-    const OhkmGeo g = ohkm_geo(a, aligned ? vec : 1);
-    if (a.dtype == FPD_BF16) {
-        if (aligned) ohkm_launch_s<bf16_t, 8>(k, g, st);
-        else ohkm_launch_s<bf16_t, 1>(k, g, st);
-    } else {
-        if (aligned) ohkm_launch_s<float, 4>(k, g, st);
-        else ohkm_launch_s<float, 1>(k, g, st);
-    }
+    loss_dispatch(k.base, [&](auto t, auto v) {
+        using T = typename decltype(t)::type;
+        constexpr int V = decltype(v)::value;
+        const LossGeo g = loss_geo(k.base, V, PT, MAX_BLOCKS);
+        loss_dispatch_stacks(k.base.S, [&](auto smax) { ohkm_launch<T, V, decltype(smax)::value>(k, g, st); });
+    });
     return 0;
 }

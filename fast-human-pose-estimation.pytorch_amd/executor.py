@@ -923,26 +923,15 @@ class FusedFPDStep:
             A.tensor('weight').fill_(1.0)
         A.alloc('losses', 4)
         if self.ohkm is not None:
-            d = R.LossT()
-            d.B, d.J, d.H, d.W, d.S = self.B, self.J, self.hh, self.hw, len(g.outputs)
-            nbytes = R.lib().fpd_loss_ohkm_scratch_bytes(d)
-            if nbytes < 0:
-                R.check(int(nbytes), 'fpd_loss_ohkm_scratch_bytes')
-            A.alloc('ohkm_scratch', nbytes // 8)
+            self._alloc_loss_scratch('ohkm')
             A.alloc('ohkm_masks', len(g.outputs) * 2 * self.B)
         if self.kl is not None:
-            d = R.LossT()
-            d.B, d.J, d.H, d.W, d.S = self.B, self.J, self.hh, self.hw, len(g.outputs)
-            nbytes = R.lib().fpd_loss_kl_scratch_bytes(d)
-            if nbytes < 0:
-                R.check(int(nbytes), 'fpd_loss_kl_scratch_bytes')
-            A.alloc('kl_scratch', nbytes // 8)
+            self._alloc_loss_scratch('kl')
         self.student.mid_ops = [G.Op('loss', extra_in=list(g.outputs), extra_out=list(g.out_grads))]
-        add_loss = self._add_loss_kl if self.kl is not None else self._add_loss if self.ohkm is None else self._add_loss_ohkm
-        self.student.mid_native = [lambda plan: add_loss(plan, 0)]
+        self.student.mid_native = [lambda plan: self._add_loss(plan, 0)]
         self.student.finalize()
         b = len(self.student.plan)                 # second loss op reading the other staged teacher map
-        add_loss(self.student.plan, 1)
+        self._add_loss(self.student.plan, 1)
         self.student.rng['mid1'] = (b, len(self.student.plan))
         # optimizer state (torch.optim.Adam semantics, lib/utils/utils.py:69-73)
         n = student_state.table.sizes['param']
@@ -1058,35 +1047,37 @@ class FusedFPDStep:
         s.losses = A.tensor('losses').data_ptr()
         s.grad_scale = 1.0 / self.world_size
 
-    def _add_loss(self, plan, slot):
-        plan.add(*self.student.low.memset('losses'))
-        s = R.LossT()
-        self._fill_loss(s, slot)
-        plan.add(R.OP_LOSS, s)
+    def _alloc_loss_scratch(self, kind):
+        """The arena '<kind>_scratch' of fp64 partial sums that fpd_loss_<kind>_scratch_bytes() asks for at this step's shape."""
+        d = R.LossT()
+        d.B, d.J, d.H, d.W, d.S = self.B, self.J, self.hh, self.hw, len(self.student.g.outputs)
+        query = 'fpd_loss_%s_scratch_bytes' % kind
+        nbytes = getattr(R.lib(), query)(d)
+        if nbytes < 0:
+            R.check(int(nbytes), query)
+        self.student.A.alloc(kind + '_scratch', nbytes // 8)
 
-    def _add_loss_ohkm(self, plan, slot):
-        """_add_loss with hard-keypoint mining (csrc/loss_ohkm.hip): the same arguments + topk pair, scratch and masks."""
+    def _add_loss(self, plan, slot):
+        """The zeroing of `losses` and the step's loss op: MSE (csrc/loss_adam.hip), with hard-keypoint mining (csrc/loss_ohkm.hip:
+        + topk pair, scratch and masks) or with a spatial-softmax KL term (csrc/loss_kl.hip: + flags, temperatures and scratch)."""
         A = self.student.A
         plan.add(*self.student.low.memset('losses'))
-        k = R.LossOhkmT()
-        self._fill_loss(k.base, slot)
-        k.topk_pose, k.topk_kd = self.ohkm
-        sc = A.tensor('ohkm_scratch')
-        k.scratch, k.scratch_bytes = sc.data_ptr(), sc.numel() * sc.element_size()
-        k.masks = A.tensor('ohkm_masks').data_ptr()
-        plan.add(R.OP_LOSS_OHKM, k)
-
-    def _add_loss_kl(self, plan, slot):
-        """_add_loss with a spatial-softmax KL term (csrc/loss_kl.hip): the same arguments + flags, temperatures and scratch."""
-        plan.add(*self.student.low.memset('losses'))
-        k = R.LossKlT()
-        self._fill_loss(k.base, slot)
-        tp, tk = self.kl
-        k.kl_pose, k.kl_kd = int(tp is not None), int(tk is not None)
-        k.temp_pose, k.temp_kd = tp or 1.0, tk or 1.0
-        sc = self.student.A.tensor('kl_scratch')
-        k.scratch, k.scratch_bytes = sc.data_ptr(), sc.numel() * sc.element_size()
-        plan.add(R.OP_LOSS_KL, k)
+        if self.kl is not None:
+            op, k, kind = R.OP_LOSS_KL, R.LossKlT(), 'kl'
+            tp, tk = self.kl
+            k.kl_pose, k.kl_kd = int(tp is not None), int(tk is not None)
+            k.temp_pose, k.temp_kd = tp or 1.0, tk or 1.0
+        elif self.ohkm is not None:
+            op, k, kind = R.OP_LOSS_OHKM, R.LossOhkmT(), 'ohkm'
+            k.topk_pose, k.topk_kd = self.ohkm
+            k.masks = A.tensor('ohkm_masks').data_ptr()
+        else:
+            op, k, kind = R.OP_LOSS, R.LossT(), None
+        self._fill_loss(k if kind is None else k.base, slot)
+        if kind is not None:
+            sc = A.tensor(kind + '_scratch')
+            k.scratch, k.scratch_bytes = sc.data_ptr(), sc.numel() * sc.element_size()
+        plan.add(op, k)
 
     def ohkm_masks(self):
         """[S][2][B] int32 of the last step: bit j = joint j of (stack, {pose, kd}, sample) was kept -- synchronises."""

@@ -31,8 +31,9 @@ SHAPES = {   # B, J, H, W, S
     'C': (2, 16, 64, 64, 4),     # vector path, the benchmark's map
     'D': (1, 32, 8, 8, 1),       # the largest J
     'E': (5, 16, 128, 128, 1),   # 5 x 128 tiles > 512 blocks: a block walks two tiles (and turns the target again in its second pass)
+    'F': (2, 16, 12, 9, 2),      # run one element off the 16-byte grid: J a multiple of the vector on the scalar path, 16 joint lanes
 }
-CHUNKS = {'A': 1, 'B': 4, 'C': 32, 'D': 1, 'E': 64}
+CHUNKS = {'A': 1, 'B': 4, 'C': 32, 'D': 1, 'E': 64, 'F': 1}
 SEEDS = 8
 MARGIN = 4.0
 
@@ -46,9 +47,10 @@ def _nchw64(t):
     return t.detach().cpu().double().permute(0, 3, 1, 2).contiguous().numpy()
 
 
-def run_kl(outs, teacher, target, w, temps, alpha, dtype, w_kd=None, nchw=1, dout=True, grad_scale=1.0, keep=False):
+def run_kl(outs, teacher, target, w, temps, alpha, dtype, w_kd=None, nchw=1, dout=True, grad_scale=1.0, keep=False, offset=0):
     """One fpd_loss_kl call.  outs / teacher: NHWC CPU tensors already in the storage type; target: NCHW float32 CPU tensor;
-    w / w_kd: [B,J] float32; temps: (T_pose or None, T_kd or None), None = that term is MSE.
+    w / w_kd: [B,J] float32; temps: (T_pose or None, T_kd or None), None = that term is MSE.  offset: every map and gradient
+    starts that many elements behind a 16-byte boundary, between guard elements that have to stay intact.
     -> dict(losses [2] float64, douts: NCHW float64 numpy, raw: the gradient buffers' bytes, scratch, chunks)."""
     from fpd_amd import runtime as R
     dev = torch.device('cuda:0')
@@ -57,12 +59,20 @@ def run_kl(outs, teacher, target, w, temps, alpha, dtype, w_kd=None, nchw=1, dou
     k = R.LossKlT()
     a = k.base
     a.B, a.J, a.H, a.W, a.S, a.dtype, a.target_nchw, a.alpha, a.grad_scale = B, J, H, W, S, dtype, nchw, alpha, grad_scale
-    d_outs = [o.to(dev).contiguous() for o in outs]
-    d_douts = [torch.full_like(o, float('nan')) for o in d_outs]
+    guarded = []
+    if offset:
+        from tests.test_step_kernels_gpu import Guarded
+        guarded = [Guarded(o.numel(), o.dtype, o, offset) for o in outs + [teacher]] + [Guarded(o.numel(), o.dtype, None, offset) for o in outs]
+        d_outs, d_t, d_douts = ([x.t.view(outs[0].shape) for x in guarded[i:j]] for i, j in ((0, S), (S, S + 1), (S + 1, 2 * S + 1)))
+        d_t = d_t[0]
+        assert all(x.data_ptr() % 16 == offset * x.element_size() for x in d_outs + d_douts + [d_t])
+    else:
+        d_outs = [o.to(dev).contiguous() for o in outs]
+        d_douts = [torch.full_like(o, float('nan')) for o in d_outs]
+        d_t = teacher.to(dev).contiguous()
     for i in range(S):
         a.out[i] = d_outs[i].data_ptr()
         a.dout[i] = d_douts[i].data_ptr() if dout else None
-    d_t = teacher.to(dev).contiguous()
     d_tg = (target if nchw else target.permute(0, 2, 3, 1)).contiguous().to(dev)
     d_w = w.float().contiguous().to(dev)
     d_wk = w_kd.float().contiguous().to(dev) if w_kd is not None else None
@@ -84,6 +94,7 @@ def run_kl(outs, teacher, target, w, temps, alpha, dtype, w_kd=None, nchw=1, dou
         torch.cuda.synchronize()
         raws.append((losses.cpu().numpy().tobytes(), [d.cpu().view(torch.uint8).numpy().tobytes() for d in d_douts],
                      scratch.cpu().numpy().tobytes()))
+    assert all(x.intact() for x in guarded)
     return {'losses': losses.cpu().numpy(), 'douts': [_nchw64(d) for d in d_douts], 'raws': raws,
             'chunks': nbytes // (B * slab)}
 
@@ -184,6 +195,8 @@ ACCURACY = [   # shape, dtype, target_nchw, (T_pose, T_kd), alpha, kwargs
     ('D', 1, 0, (1.0, 0.05), 1.0, {'kd_weights': True}),
     ('E', 0, 1, (1.0, 0.05), 0.5, {}),
     ('E', 1, 0, (None, 1.0), 0.5, {}),
+    ('F', 0, 1, (1.0, 4.0), 0.5, {'offset': 1}),
+    ('F', 1, 0, (None, 1.0), 0.5, {'offset': 1}),
 ]
 
 
@@ -195,7 +208,8 @@ def test_kernel_is_within_four_times_torch_float32_of_float64(case):
     bar = measured_bar(shape, dtype, temps, alpha, kdw, gs)
     outs, teacher, target, w, w_kd = make_inputs(100, *shape, dtype, kdw)
     ref = reference(outs, teacher, target, w, temps, alpha, w_kd, gs)
-    got = run_kl(outs, teacher, target, w, temps, alpha, dtype, w_kd=w_kd, nchw=nchw, dout=kw.get('dout', True), grad_scale=gs)
+    got = run_kl(outs, teacher, target, w, temps, alpha, dtype, w_kd=w_kd, nchw=nchw, dout=kw.get('dout', True), grad_scale=gs,
+                 offset=kw.get('offset', 0))
     assert got['chunks'] == CHUNKS[name]
     check(got, ref, bar, dtype, 'accuracy %s' % (case,), grads=kw.get('dout', True))
     if not kw.get('dout', True):

@@ -104,6 +104,16 @@ def test_validation_errors_without_device(runtime):
     big.B, big.H, big.W = 32, 64, 64                             # the benchmark's maps: 32 tiles per image in 16 chunks of 2
     assert lib.fpd_loss_ohkm_scratch_bytes(big) == 32 * 16 * 2 * 2 * 16 * 8
     assert lib.fpd_loss_ohkm_scratch_bytes(_args(R, J=33).base) < 0 and lib.fpd_loss_ohkm_scratch_bytes(None) < 0
+    # fpd_loss asks the same of its fpd_loss_t, before any launch
+    assert lib.fpd_loss(None, None) != 0 and 'null' in err()
+    assert lib.fpd_loss(_args(R, J=33).base, None) == -3 and 'loss: J=33 (<=32)' in err()
+    a = _args(R).base
+    a.out[1] = None
+    assert lib.fpd_loss(a, None) == -2 and 'loss: null map of stack 1' in err()
+    assert lib.fpd_loss(_args(R, dtype=7).base, None) == -2 and 'loss: bad dtype 7' in err()
+    big = _args(R).base
+    big.B, big.H, big.W = 2048, 256, 256                         # 2^31 elements
+    assert lib.fpd_loss(big, None) == -2 and 'loss: tensor too large for 32-bit indexing' in err()
 
 
 def test_plan_accepts_the_op_and_checks_its_args_size(runtime):

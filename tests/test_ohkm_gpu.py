@@ -28,9 +28,11 @@ def _nchw64(t):
     return t.detach().cpu().double().permute(0, 3, 1, 2).contiguous().numpy()
 
 
-def run_ohkm(outs, teacher, target, w, topk, alpha, dtype, w_kd=None, nchw=1, dout=True, grad_scale=1.0):
+def run_ohkm(outs, teacher, target, w, topk, alpha, dtype, w_kd=None, nchw=1, dout=True, grad_scale=1.0, offset=0):
     """One fpd_loss_ohkm call.  outs / teacher: NHWC CPU tensors already in the storage type; target: NCHW float32 CPU tensor;
-    w / w_kd: [B,J] float32.  -> dict(losses [2] float64, douts: NCHW float64 numpy, masks uint32 [S,2,B], rows float64 [S,2,B,J])."""
+    w / w_kd: [B,J] float32.  offset: every map and gradient starts that many elements behind a 16-byte boundary, between guard
+    elements that have to stay intact.
+    -> dict(losses [2] float64, douts: NCHW float64 numpy, masks uint32 [S,2,B], rows float64 [S,2,B,J])."""
     from fpd_amd import runtime as R
     dev = torch.device('cuda:0')
     B, H, W, J = outs[0].shape
@@ -38,12 +40,20 @@ def run_ohkm(outs, teacher, target, w, topk, alpha, dtype, w_kd=None, nchw=1, do
     k = R.LossOhkmT()
     a = k.base
     a.B, a.J, a.H, a.W, a.S, a.dtype, a.target_nchw, a.alpha, a.grad_scale = B, J, H, W, S, dtype, nchw, alpha, grad_scale
-    d_outs = [o.to(dev).contiguous() for o in outs]
-    d_douts = [torch.full_like(o, float('nan')) for o in d_outs]
+    guarded = []
+    if offset:
+        from tests.test_step_kernels_gpu import Guarded
+        guarded = [Guarded(o.numel(), o.dtype, o, offset) for o in outs + [teacher]] + [Guarded(o.numel(), o.dtype, None, offset) for o in outs]
+        d_outs, d_t, d_douts = ([x.t.view(outs[0].shape) for x in guarded[i:j]] for i, j in ((0, S), (S, S + 1), (S + 1, 2 * S + 1)))
+        d_t = d_t[0]
+        assert all(x.data_ptr() % 16 == offset * x.element_size() for x in d_outs + d_douts + [d_t])
+    else:
+        d_outs = [o.to(dev).contiguous() for o in outs]
+        d_douts = [torch.full_like(o, float('nan')) for o in d_outs]
+        d_t = teacher.to(dev).contiguous()
     for i in range(S):
         a.out[i] = d_outs[i].data_ptr()
         a.dout[i] = d_douts[i].data_ptr() if dout else None
-    d_t = teacher.to(dev).contiguous()
     d_tg = (target if nchw else target.permute(0, 2, 3, 1)).contiguous().to(dev)
     d_w = w.float().contiguous().to(dev)
     d_wk = w_kd.float().contiguous().to(dev) if w_kd is not None else None
@@ -58,6 +68,7 @@ def run_ohkm(outs, teacher, target, w, topk, alpha, dtype, w_kd=None, nchw=1, do
     k.scratch, k.scratch_bytes, k.masks = scratch.data_ptr(), nbytes, masks.data_ptr()
     R.check(R.lib().fpd_loss_ohkm(k, R.current_stream()), 'fpd_loss_ohkm')
     torch.cuda.synchronize()
+    assert all(x.intact() for x in guarded)
     rows = scratch.view(B, -1, S, 2, J).cpu().numpy()
     return {'losses': losses.cpu().numpy(), 'douts': [_nchw64(d) for d in d_douts],
             'masks': masks.cpu().numpy().view(np.uint32), 'rows': rows.sum(1).transpose(1, 2, 0, 3), 'chunks': rows.shape[1]}
@@ -163,8 +174,23 @@ def _dyadic(S, seed=5, B=2, J=16, H=8, W=8):
 
 
 @pytest.mark.parametrize('dtype', [0, 1])
-@pytest.mark.parametrize('S', [1, 2])
-def test_dyadic_inputs_are_bit_exact(S, dtype):
+@pytest.mark.parametrize('S,misaligned', [(1, False), (2, False), (2, True)], ids=['1', '2', 'misaligned'])
+def test_dyadic_inputs_are_bit_exact(S, misaligned, dtype):
+    if misaligned:
+        # J a multiple of the vector but every map and gradient one element off the 16-byte grid: the scalar kernels with
+        # 16 joint lanes per pixel, on a ragged 108-pixel tile.  B k HW is no power of two here, so the gradient is rounded:
+        # what is expected is what the aligned run (the vector kernels) gives on the same inputs, bit for bit.
+        outs, teacher, target, w = _dyadic(2, B=2, J=16, H=12, W=9)
+        outs, teacher = [o.to(_tdt(dtype)) for o in outs], teacher.to(_tdt(dtype))
+        want = run_ohkm(outs, teacher, target, w, (8, 8), 0.5, dtype)
+        got = run_ohkm(outs, teacher, target, w, (8, 8), 0.5, dtype, offset=1)
+        ref = reference(outs, teacher, target, w, (8, 8), 0.5)
+        assert np.array_equal(got['rows'], ref['rows']) and np.array_equal(got['masks'], ref['masks'])      # (sums of dyadic products: exact)
+        assert np.array_equal(got['rows'], want['rows']) and np.array_equal(got['masks'], want['masks'])
+        assert np.array_equal(got['losses'], want['losses'])
+        for g, r in zip(got['douts'], want['douts']):
+            assert not np.isnan(r).any() and np.array_equal(g, r)
+        return
     outs, teacher, target, w = _dyadic(S)
     outs, teacher = [o.to(_tdt(dtype)) for o in outs], teacher.to(_tdt(dtype))       # exact: 6 significant bits
     ref = reference(outs, teacher, target, w, (8, 8), 0.5)

@@ -13,9 +13,16 @@ second launch is not measured here).
 times fpd_loss_kl (csrc/loss_kl.hip, two launches; pose term MSE, distillation term KL at that temperature) instead, by the same
 protocol, and reports the launch gap as the difference of the two entry points on an 8x8 map of one image, where neither has
 work to speak of.  --step adds the whole train step of the benchmark pair (hourglass 128 x 4 student, 256 x 8 teacher, 256x256
-images): FusedFPDStep(kl=(None, T)) against the default step, each sample in a process of its own, the two kinds alternating."""
+images): FusedFPDStep(kl=(None, T)) against the default step, each sample in a process of its own, the two kinds alternating.
+
+    python tools/loss_bench.py --digest [--kl T] [...]
+
+times nothing: one call each of fpd_loss, fpd_loss_ohkm, fpd_loss_kl (None, T) and fpd_loss_kl (T, T) on the same seeded inputs,
+and one line per call with the SHA-256 of everything it wrote.  Two builds of the library (FPD_AMD_LIB) print the same lines
+or do not compute the same bytes."""
 import argparse
 import ctypes as C
+import hashlib
 import os
 import statistics
 import sys
@@ -51,6 +58,32 @@ def launch_gap(kk, dt, tdt, dev, timed, a):
         u1.append(timed(one, a.calls)), u2.append(timed(two, a.calls))
     m1, m2 = statistics.median(u1), statistics.median(u2)
     return ['launch gap: one 8x8 map  fpd_loss %.2f us (1 launch)  fpd_loss_kl %.2f us (2 launches)  difference %.2f us' % (m1, m2, m2 - m1)]
+
+
+def kl_args(base, kl_pose, temp, dev):
+    """fpd_loss_kl_t over the maps of `base`: distillation term KL at `temp`, pose term too if kl_pose; and its scratch (keep it alive)"""
+    kk = R.LossKlT()
+    C.memmove(C.byref(kk.base), C.byref(base), C.sizeof(R.LossT))
+    kk.kl_pose, kk.kl_kd, kk.temp_pose, kk.temp_kd = int(kl_pose), 1, temp if kl_pose else 1.0, temp
+    nbytes = R.lib().fpd_loss_kl_scratch_bytes(kk.base)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    kk.scratch, kk.scratch_bytes = scratch.data_ptr(), nbytes
+    return kk, scratch
+
+
+def digest(a, k, losses, douts, masks, dev):
+    """--digest: what every entry point writes on the seeded inputs, as SHA-256 (default temperature 2)"""
+    lib, st, T = R.lib(), R.current_stream(), a.kl or 2.0
+    sha = lambda t: hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+    (k1, s1), (k2, s2) = kl_args(k.base, False, T, dev), kl_args(k.base, True, T, dev)
+    for name, fn, arg in (('fpd_loss', lib.fpd_loss, k.base), ('fpd_loss_ohkm topk=%d' % a.topk, lib.fpd_loss_ohkm, k),
+                          ('fpd_loss_kl (None, %g)' % T, lib.fpd_loss_kl, k1), ('fpd_loss_kl (%g, %g)' % (T, T), lib.fpd_loss_kl, k2)):
+        for t in [losses, masks] + douts:
+            t.zero_()
+        R.check(fn(arg, st), name)
+        torch.cuda.synchronize()
+        print('%-24s losses %s  dout %s%s' % (name, sha(losses), ' '.join(sha(d) for d in douts),
+                                             '  masks ' + sha(masks) if fn is lib.fpd_loss_ohkm else ''))
 
 
 def step_child(a, dev):
@@ -132,6 +165,7 @@ def main():
     ap.add_argument('--step-procs', type=int, default=3, help='processes per kind of step')
     ap.add_argument('--step-child', default='', choices=['', 'default', 'kl'], help=argparse.SUPPRESS)
     ap.add_argument('--step-steps', type=int, default=20)
+    ap.add_argument('--digest', action='store_true', help='no timing: one call of every entry point and the SHA-256 of what it wrote')
     ap.add_argument('--out', default='')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'loss_bench needs the GPU'
@@ -158,17 +192,14 @@ def main():
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     masks = torch.zeros(S * 2 * B, dtype=torch.int32, device=dev)
     k.scratch, k.scratch_bytes, k.masks = scratch.data_ptr(), nbytes, masks.data_ptr()
+    if a.digest:
+        return digest(a, k, losses, douts, masks, dev)
     lib, st = R.lib(), R.current_stream()
     new = 'fpd_loss_ohkm' if a.kl is None else 'fpd_loss_kl'
     calls = {'fpd_loss': lambda: R.check(lib.fpd_loss(k.base, st), 'fpd_loss'),
              'fpd_loss_ohkm': lambda: R.check(lib.fpd_loss_ohkm(k, st), 'fpd_loss_ohkm')}
     if a.kl is not None:
-        kk = R.LossKlT()
-        C.memmove(C.byref(kk.base), C.byref(k.base), C.sizeof(R.LossT))
-        kk.kl_pose, kk.kl_kd, kk.temp_pose, kk.temp_kd = 0, 1, 1.0, a.kl
-        kbytes = lib.fpd_loss_kl_scratch_bytes(kk.base)
-        kscratch = torch.empty(kbytes // 8, dtype=torch.float64, device=dev)
-        kk.scratch, kk.scratch_bytes = kscratch.data_ptr(), kbytes
+        kk, kscratch = kl_args(k.base, False, a.kl, dev)
         del calls['fpd_loss_ohkm']
         calls['fpd_loss_kl'] = lambda: R.check(lib.fpd_loss_kl(kk, st), 'fpd_loss_kl')
 
