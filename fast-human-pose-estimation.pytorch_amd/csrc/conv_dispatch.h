@@ -178,6 +178,8 @@ int fpd_ema_geometry_of(const fpd_ema_t& a, int* blocks, int64_t* nvec);      //
 int fpd_grad_clip_launch(const fpd_grad_clip_t& a, hipStream_t st);      // csrc/grad_clip.hip: sums of squares, finalise, in-place scale
 int fpd_grad_clip_geometry_of(const fpd_grad_clip_t& a, int* blocks, int64_t* nvec);      // its validation, grid and 16-byte vectors
 int64_t fpd_grad_clip_scratch_size(int64_t n);
+int fpd_grad_accum_launch(const fpd_grad_accum_t& a, hipStream_t st);    // csrc/grad_accum.hip: one streaming launch, three modes
+int fpd_grad_accum_geometry_of(const fpd_grad_accum_t& a, int* blocks, int64_t* nvec);    // its validation, grid and 16-byte vectors
 int fpd_weight_prep_launch(const fpd_wprep_entry_t* table, int n, int64_t max_elems, int dtype, hipStream_t st);
 int fpd_bn_update_running_launch(const fpd_bnupd_entry_t* table, int n, hipStream_t st);
 int fpd_cast_launch(const void* src, void* dst, int64_t n, int sd, int dd, hipStream_t st);

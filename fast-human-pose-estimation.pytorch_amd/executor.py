@@ -848,13 +848,19 @@ class FusedFPDStep:
          [-> ema=: the weight average of a lib.utils.utils.ModelEma, one more launch in the optimizer's range].
     clip=: a lib.utils.utils.GradClipper of the student clips the (reduced) gradient to a global L2 norm at the head of the
     optimizer's range.
+    accum=k > 1: one optimizer update per window of k student_step calls (micro-batches), see _add_accum.
     No host synchronisation inside; losses are read back only when asked for."""
 
     def __init__(self, student_state, student_cfg, teacher_state, teacher_cfg, batch, height, width, alpha,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, world_size=1, adam=None, teacher_chunks=None,
                  use_target_weight=(True, True), ohkm=None, sgd=None, kl=None, ema=None,
-                 clip=None):
+                 clip=None, accum=None):
         dev = student_state.device
+        if accum is None:
+            accum = 1
+        if isinstance(accum, bool) or not isinstance(accum, int) or not 1 <= accum <= 1024:
+            raise R.FpdError('FusedFPDStep: accum=%r: an integer in [1, 1024] (micro-batches per optimizer update)' % (accum,))
+        self.accum = accum
         if adam is not None and sgd is not None:
             raise R.FpdError('FusedFPDStep: adam= and sgd= are mutually exclusive')
         # JointsMSELoss(use_target_weight) of the pose / distillation criterion (tools/fpd_train.py:145-147,177-179):
@@ -939,6 +945,7 @@ class FusedFPDStep:
         self._dist_work = None
         if sgd is not None:         # share the momentum buffer / step / lr with a lib.utils.utils.FusedSGD; no Adam moments
             self._add_sgd(sgd, student_state, n, ema, clip)
+            self._add_accum(student_state)
             return
         if adam is not None:        # share moments / step / lr with a lib.utils.utils.FusedAdam (checkpointable state)
             self.m, self.v, self.lr_dev, self.step_dev = adam.m, adam.v, adam.lr_dev, adam.step_dev
@@ -965,6 +972,33 @@ class FusedFPDStep:
         self.student.plan.add(R.OP_ADAM, a)
         self._add_ema(ema, student_state)
         self.student.rng['adam'] = (b, len(self.student.plan))
+        self._add_accum(student_state)
+
+    def _add_accum(self, student_state):
+        """accum=k > 1: three one-op ranges behind the optimizer's, over the gradient arena and an arena `acc` of the same size --
+        'acc0' (acc = grad), 'acc' (acc += grad) and 'accfin' (grad = acc * *scale_dev).  student_step runs 'acc0' or 'acc'
+        behind every backward and closes the window behind the k-th: it fills scale_dev with 1/m (stream-ordered, like lr_dev; m
+        is the window's length, so that flush() can close a shorter one with the same recorded op), runs 'accfin' and then
+        the tail of a k = 1 step (_update) on the gradient arena, which now holds the window's mean.  All-reduce, clip, optimizer and EMA therefore run
+        once per window; nothing is recorded INSIDE the optimizer's range.  The loss op carries no 1/k.  k == 1 adds nothing."""
+        self._acc_j = 0                 # micro-batches in the open window
+        self._acc_allreduce = None      # the hook of the last student_step: flush() takes none
+        self.updates = 0                # windows closed = optimizer updates enqueued (or deferred behind an all-reduce)
+        if self.accum == 1:
+            return
+        dev = student_state.device
+        n = self.n_param
+        self.acc = torch.empty(n, dtype=torch.float32, device=dev)
+        self.scale_dev = torch.ones(1, dtype=torch.float32, device=dev)
+        plan = self.student.plan
+        for name, mode in (('acc0', R.ACCUM_FIRST), ('acc', R.ACCUM_ADD), ('accfin', R.ACCUM_FIN)):
+            a = R.GradAccumT()
+            a.n, a.mode = n, mode
+            a.grad, a.acc = student_state.A.tensor('grad').data_ptr(), self.acc.data_ptr()
+            a.scale_dev = self.scale_dev.data_ptr()
+            b = len(plan)
+            plan.add(R.OP_GRAD_ACCUM, a)
+            self.student.rng[name] = (b, len(plan))
 
     def _add_clip(self, clip, student_state):
         """clip=: one OP_GRAD_CLIP in front of the optimizer op, INSIDE its range -- student_step, the deferred run behind the
@@ -1145,11 +1179,30 @@ class FusedFPDStep:
         if getattr(self, 'metric', None) is not None:
             self.metric.enqueue()
         s.run('bwd')
+        if self.accum > 1:
+            s.run('acc0' if self._acc_j == 0 else 'acc')
+            self._acc_j += 1
+            self._acc_allreduce = allreduce
+            if self._acc_j == self.accum:
+                self._close_window()
+        else:
+            self._update(allreduce)
+        self._k_s += 1
+
+    def _update(self, allreduce):
+        """The tail of an update on the gradient arena: the all-reduce hook with the optimizer's range deferred, or the range."""
         if allreduce is not None:
             self._dist_work = allreduce(self.student.state.A.tensor('grad'), self.grad_buckets())
         else:
-            s.run('adam')
-        self._k_s += 1
+            self.student.run('adam')
+        self.updates += 1
+
+    def _close_window(self):
+        """grad = the mean of the open window's m micro-batch gradients, then the update."""
+        m, self._acc_j = self._acc_j, 0
+        self.scale_dev.fill_(1.0 / m)
+        self.student.run('accfin')
+        self._update(self._acc_allreduce)
 
     def grad_buckets(self):
         """[(first element, end element, wait)] of the flat gradient arena in completion order: `wait(stream)` makes a
@@ -1158,6 +1211,8 @@ class FusedFPDStep:
         whole arena, no wait needed: it is issued behind the backward) when the phases are replayed as hipGraphs."""
         s = self.student
         n = self.n_param
+        if self.accum > 1:                     # no slice is final before 'accfin', which is issued behind everything
+            return [(0, n, None)]
         if s.graphs.get('bwd') is not None or not getattr(s, 'bucket_ops', None):
             return [(0, n, None)]
         table = s.state.table
@@ -1178,7 +1233,7 @@ class FusedFPDStep:
         cap = torch.cuda.Stream(device=self.student.state.device)
         for t in self.teachers:
             t.capture(['fwd'], cap)
-        self.student.capture(['prep', 'fwd', 'mid', 'mid1', 'bwd', 'adam'], cap)
+        self.student.capture(['prep', 'fwd', 'mid', 'mid1', 'bwd', 'adam'] + (['acc0', 'acc', 'accfin'] if self.accum > 1 else []), cap)
 
     def step(self, allreduce=None):
         """Un-pipelined iteration on the batch given to set_batch(): teacher forward, then the student step."""
@@ -1197,7 +1252,10 @@ class FusedFPDStep:
         self.flush()
 
     def flush(self):
-        """Apply a pending (overlapped) optimizer update -- call after the last step()."""
+        """Apply a pending (overlapped) optimizer update -- call after the last step().  accum > 1: first close a partial
+        window of m < k micro-batches (scale 1/m, the all-reduce hook of the last student_step); the next window starts anew."""
+        if self._acc_j > 0:
+            self._close_window()
         if self._dist_work is not None:
             self._dist_work()
             self._dist_work = None
@@ -1211,6 +1269,9 @@ class FusedFPDStep:
         out = {'teacher_fwd': count(self.teacher, 'fwd') * len(self.teachers)} if self.teacher is not None else {}
         for ph in ('prep', 'fwd', 'mid', 'bwd', 'adam'):
             out['student_' + ph] = count(self.student, ph)
+        if self.accum > 1:                     # per micro-batch: 'acc0' or 'acc'; 'accfin' and student_adam run once per window
+            out['student_acc'] = count(self.student, 'acc')
+            out['student_accfin'] = count(self.student, 'accfin')
         out['total'] = sum(out.values())
         return out
 

@@ -94,7 +94,10 @@ def _defaults():
                   'EMA': False, 'EMA_DECAY': 0.9998, 'EMA_WARMUP': True,
                   # not in the reference: clip the gradient to this global L2 norm inside the fused step (utils.GradClipper);
                   # 0 = off, .inf = measure and log the norm only; the tools refuse a negative value
-                  'CLIP_GRAD_NORM': 0.0},
+                  'CLIP_GRAD_NORM': 0.0,
+                  # not in the reference: one optimizer update per this many batches, their gradients averaged inside the fused
+                  # step (FusedFPDStep accum=); 1 = every batch; the tools refuse a value below 1
+                  'ACCUM_STEPS': 1},
         'TEST': {'BATCH_SIZE_PER_GPU': 32, 'FLIP_TEST': False, 'POST_PROCESS': False, 'SHIFT_HEATMAP': False, 'MODEL_FILE': '',
                  # read by DATASET.DATASET coco (default.py:110-119); NMS_THRE and BBOX_THRE are accepted and unused, as there
                  'USE_GT_BBOX': False, 'IMAGE_THRE': 0.1, 'NMS_THRE': 0.6, 'SOFT_NMS': False, 'OKS_THRE': 0.5, 'IN_VIS_THRE': 0.0,

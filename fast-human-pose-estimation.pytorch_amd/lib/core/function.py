@@ -68,13 +68,14 @@ def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
 
 
 def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, use_target_weight=(True, True), ohkm=None,
-                   kl=None, ema=None, clip=None):
+                   kl=None, ema=None, clip=None, accum=None):
     """One FusedFPDStep per (student, teacher, batch shape); shares the optimizer state with the FusedAdam / FusedSGD object.
     tmodel None = plain (non-distillation) training: no teacher graph, alpha must be 0.  ohkm: FusedFPDStep's topk pair;
     kl: its temperature pair.  ema: a utils.ModelEma of the student, averaged inside the step (its decay and warm-up live
     in the recorded plan op, so they are part of the key; the object is compared by identity like the optimizer).
     clip: a utils.GradClipper of the student (its max_norm lives in the recorded plan op, so it is part of the key; the object
-    is compared by identity).
+    is compared by identity).  accum: FusedFPDStep's micro-batches per update; above 1 it adds plan ranges, so it is part of
+    the key (None and 1 are the same step).
     A FusedSGD's (momentum, weight_decay, nesterov) live in the recorded plan op, so they are part of the key."""
     s, t = _unwrap(model), (_unwrap(tmodel) if tmodel is not None else None)
     # The cache lives ON the student module (not in a module-level dict keyed by id(): ids are recycled once an object
@@ -92,6 +93,8 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
         key += (('ema', float(ema.decay), bool(ema.warmup)),)
     if clip is not None:
         key += (('clip', float(clip.max_norm)),)
+    if accum is not None and accum != 1:
+        key += (('accum', accum),)
     hit = cache.get(key)
     if hit is not None and hit[0] is t and hit[1] is optimizer and hit[3] is ema and hit[4] is clip:
         return hit[2]
@@ -100,7 +103,7 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     step = E.FusedFPDStep(s.device_state(), s.cfg_hg, t.device_state() if t is not None else None,
                           t.cfg_hg if t is not None else None, n, h, w, alpha,
                           lr=float(optimizer.param_groups[0]['lr']), world_size=world_size,
-                          use_target_weight=use_target_weight, ohkm=ohkm, kl=kl, ema=ema, clip=clip,
+                          use_target_weight=use_target_weight, ohkm=ohkm, kl=kl, ema=ema, clip=clip, accum=accum,
                           **{'sgd' if is_sgd else 'adam': optimizer})
     cache[key] = (t, optimizer, step, ema, clip)
     return step
@@ -132,19 +135,21 @@ def _on_device(t, dev):
 
 
 def _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
-               output_dir='', rank=0, ema=None, clip=None):
+               output_dir='', rank=0, ema=None, clip=None, accum=None):
     """The loop shared by fpd_train (function.py:99-187) and train (function.py:28-96; tmodel None, alpha 0)."""
     vis, img_writer = _debug_writer(config, rank)
     try:
         return _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
-                               alpha, output_dir, vis, img_writer, ema, clip)
+                               alpha, output_dir, vis, img_writer, ema, clip, accum)
     finally:
         if img_writer is not None:
             img_writer.close()
 
 
 def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size, alpha,
-                    output_dir, vis, img_writer, ema=None, clip=None):
+                    output_dir, vis, img_writer, ema=None, clip=None, accum=None):
+    """accum > 1: one optimizer update per window of `accum` batches (FusedFPDStep._add_accum).  Both flush() calls below also
+    close a partial window, so a window never spans batch shapes or epochs; meters and the `Epoch:` line stay per batch."""
     kd_mode = tmodel is not None
     use_w, ohkm, kl = crit if len(crit) == 3 else tuple(crit) + (None,)
     batch_time, data_time = AverageMeter(), AverageMeter()
@@ -158,6 +163,7 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
     nxt = next(it, None)
     i = -1
     n_img = 0
+    updates = upd0 = 0         # optimizer updates of the steps this epoch has finished with / `step.updates` when it took `step`
 
     def drain():
         """Feed the meters with every iteration since the last drain (function.py:150-155); synchronises."""
@@ -174,7 +180,9 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
             if step is not None:                       # batch shape changed (last, smaller batch): finish the old step
                 step.flush()
                 drain()
-            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm, kl, ema, clip)
+                updates += step.updates - upd0
+            step = fused_step_for(model, tmodel, optimizer, inp.shape, alpha, world_size, use_w, ohkm, kl, ema, clip, accum)
+            upd0 = step.updates
             metric = step.enable_metric(min_slots=config.PRINT_FREQ + 1)   # PCK + losses of every iteration, logged on the device
             metric.drain()
             n_img = inp.size(0)
@@ -220,6 +228,8 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
                 st = clip.stats()
                 last_norm = clip.norm()
                 msg += '\tGradNorm {last:.4f}  Clipped {clipped}/{calls}'.format(last=last_norm, clipped=st['clipped'], calls=st['calls'])
+            if step.accum > 1:
+                msg += '\tUpdates {0}'.format(updates + step.updates - upd0)
             logger.info(msg)
             if writer_dict is not None and writer_dict.get('writer') is not None:
                 w, gs = writer_dict['writer'], writer_dict['train_global_steps']
@@ -237,27 +247,30 @@ def _run_epoch_body(config, train_loader, model, tmodel, crit, optimizer, epoch,
     if step is not None:
         step.flush()
         drain()
+        updates += step.updates - upd0
     return {'loss': losses.avg, 'pose_loss': pose_losses.avg, 'kd_pose_loss': kd_pose_losses.avg, 'acc': acc.avg,
+            'updates': updates,
             'iterations': losses.count // max(n_img, 1) if n_img else 0}
 
 
 def fpd_train(config, train_loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch,
-              output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1, rank=0, ema=None, clip=None):
+              output_dir, tb_log_dir, writer_dict, allreduce=None, world_size=1, rank=0, ema=None, clip=None, accum=None):
     """function.py:99-187 (same positional signature; allreduce / world_size / rank are the data-parallel extras: only
     rank 0 writes DEBUG images; ema: a utils.ModelEma of the student, updated inside every fused step; clip: a
-    utils.GradClipper of the student, applied inside every fused step and reported in the `Epoch:` line).  Returns the epoch's
+    utils.GradClipper of the student, applied inside every fused step and reported in the `Epoch:` line; accum: batches per
+    optimizer update, TRAIN.ACCUM_STEPS).  Returns the epoch's
     average loss (the reference returns None)."""
     crit = _check_supported(optimizer, pose_criterion, kd_pose_criterion)
     return _run_epoch(config, train_loader, model, tmodel, crit, optimizer, epoch, writer_dict, allreduce, world_size,
-                      float(config.KD.ALPHA), output_dir, rank, ema, clip)['loss']
+                      float(config.KD.ALPHA), output_dir, rank, ema, clip, accum)['loss']
 
 
 def train(config, train_loader, model, criterion, optimizer, epoch, output_dir, tb_log_dir, writer_dict,
-          allreduce=None, world_size=1, rank=0, ema=None, clip=None):
+          allreduce=None, world_size=1, rank=0, ema=None, clip=None, accum=None):
     """function.py:28-96: plain (non-distillation) training = the same fused step without a teacher graph (alpha 0)."""
     crit = _check_supported(optimizer, criterion, criterion)
     return _run_epoch(config, train_loader, model, None, crit, optimizer, epoch, writer_dict, allreduce, world_size, 0.0,
-                      output_dir, rank, ema, clip)['loss']
+                      output_dir, rank, ema, clip, accum)['loss']
 
 
 def _to_numpy(v):

@@ -362,6 +362,14 @@ def get_grad_clipper(cfg, model):
     return GradClipper(model, max_norm)
 
 
+def get_accum_steps(cfg):
+    """TRAIN.ACCUM_STEPS -> the accum= of the fused step: batches per optimizer update, 1 (the default) = every batch."""
+    v = cfg.TRAIN.ACCUM_STEPS
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError('TRAIN.ACCUM_STEPS must be an integer >= 1 (batches per optimizer update), got %r' % (v,))
+    return v
+
+
 def multistep_lr(base_lr, milestones, gamma, epoch):
     """Learning rate the reference trains epoch `epoch` with (tools/fpd_train.py:236-239,253: MultiStepLR built with
     last_epoch = -1 and stepped at the START of every epoch, so epoch e runs at the scheduler's value for e + 1, i.e.

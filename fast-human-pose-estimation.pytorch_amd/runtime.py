@@ -18,7 +18,8 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
 (OP_CONV, OP_WGRAD, OP_STEM_FWD, OP_STEM_WGRAD, OP_EW, OP_LOSS, OP_ADAM, OP_MEMSET, OP_WPREP, OP_BNUPD,
  OP_WREDUCE, OP_BNECK, OP_BNECK_FOLD, OP_CONV_PAIR, OP_BNECK_PAIR, OP_EW_PAIR, OP_PCK, OP_HEAD, OP_HEAD_FOLD,
  OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE, OP_LOSS_KL, OP_EMA,
- OP_GRAD_CLIP) = range(30)
+ OP_GRAD_CLIP, OP_GRAD_ACCUM) = range(31)
+ACCUM_FIRST, ACCUM_ADD, ACCUM_FIN = 0, 1, 2
 EWM_MAXPOOL_BWD, EWM_SUMPOOL = 0, 1
 AFFSUM_MAX = 4
 MAX_STACKS = 8
@@ -279,6 +280,10 @@ class GradClipT(C.Structure):
                 ('out', _vp), ('counters', _vp)]
 
 
+class GradAccumT(C.Structure):
+    _fields_ = [('n', _i64), ('grad', _vp), ('acc', _vp), ('scale_dev', _vp), ('mode', _i32), ('_pad', _i32)]
+
+
 class WprepEntryT(C.Structure):
     _fields_ = [('w', _vp), ('w_fwd', _vp), ('w_bwd', _vp), ('K', _i32), ('R', _i32), ('S', _i32), ('C', _i32)]
 
@@ -312,7 +317,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT, 'fpd_dark_t': DarkT,
             'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
             'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT, 'fpd_ema_t': EmaT,
-            'fpd_grad_clip_t': GradClipT}
+            'fpd_grad_clip_t': GradClipT, 'fpd_grad_accum_t': GradAccumT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -381,6 +386,8 @@ SYMBOLS = {
     'fpd_grad_clip': (C.c_int, [C.POINTER(GradClipT), _vp]),
     'fpd_grad_clip_scratch_bytes': (C.c_int64, [C.c_int64]),
     'fpd_grad_clip_geometry': (C.c_int, [C.POINTER(GradClipT), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'fpd_grad_accum': (C.c_int, [C.POINTER(GradAccumT), _vp]),
+    'fpd_grad_accum_geometry': (C.c_int, [C.POINTER(GradAccumT), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'fpd_weight_prep': (C.c_int, [_vp, _i32, _i64, _i32, _vp]),
     'fpd_bn_update_running': (C.c_int, [_vp, _i32, _vp]),
     'fpd_cast': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),

@@ -446,6 +446,24 @@ typedef struct {
     int64_t* counters;               /* optional [3]: calls, clipped, non-finite */
 } fpd_grad_clip_t;
 
+/* Gradient accumulation over a window of micro-batches: one launch over two flat fp32 arenas of n elements, in one of three
+ * modes (a field, so that a recorded plan op is fixed).  Arithmetic in csrc/grad_accum_math.h:
+ *   FPD_ACCUM_FIRST  acc[i] = grad[i]              a copy of the bits; acc is not read, so it needs no zero-fill
+ *   FPD_ACCUM_ADD    acc[i] = acc[i] + grad[i]     one float32 addition; grad is not written
+ *   FPD_ACCUM_FIN    grad[i] = acc[i] * s          one float32 multiplication, s = *scale_dev; acc is not written
+ * 256 threads a block, the grid cap of the flat optimizer launches, 16-byte vectors where both bases are 16-byte aligned and
+ * element by element otherwise, a scalar tail, no atomics.  n == 0 is legal.
+ * Refused before any launch: n < 0 or n >= 2^60, a null grad or acc with n > 0, a pointer that is not 4-byte aligned, grad
+ * overlapping acc, scale_dev overlapping either arena, an unknown mode, a null scale_dev in FIN. */
+enum { FPD_ACCUM_FIRST = 0, FPD_ACCUM_ADD = 1, FPD_ACCUM_FIN = 2 };
+typedef struct {
+    int64_t n;
+    float* grad;                     /* read in FIRST and ADD, written in FIN */
+    float* acc;                      /* written in FIRST, read and written in ADD, read in FIN */
+    const float* scale_dev;          /* device float, read by FIN when the launch runs; may be null in FIRST and ADD */
+    int32_t mode; int32_t _pad;
+} fpd_grad_accum_t;
+
 /* Per-conv working copies of the weights: cast to `dtype` in K,R,S,C order (forward operand)
  * and the flipped, IO-swapped C,R,S,K copy (data-gradient operand).  One launch for a table. */
 typedef struct {
@@ -542,6 +560,11 @@ int64_t fpd_grad_clip_scratch_bytes(int64_t n);
  * sum and of the scale launch = the partials written; *vec_elems: the leading elements read as 16-byte vectors (a multiple
  * of 4; 0 = element by element).  Returns 0, or the error code fpd_grad_clip() would give. */
 int fpd_grad_clip_geometry(const fpd_grad_clip_t* a, int32_t* blocks, int64_t* vec_elems);
+int fpd_grad_accum(const fpd_grad_accum_t* a, fpd_stream_t stream);
+/* The launch fpd_grad_accum() makes for `a` as it stands (pure host code, nothing is dereferenced).  blocks: its grid;
+ * *vec_elems: the leading elements moved as 16-byte vectors (a multiple of 4; 0 = element by element).  Returns 0, or the
+ * error code fpd_grad_accum() would give. */
+int fpd_grad_accum_geometry(const fpd_grad_accum_t* a, int32_t* blocks, int64_t* vec_elems);
 int fpd_weight_prep(const fpd_wprep_entry_t* table_dev, int32_t n_entries, int64_t max_elems, int32_t dtype,
                     fpd_stream_t stream);
 int fpd_bn_update_running(const fpd_bnupd_entry_t* table_dev, int32_t n_entries, fpd_stream_t stream);
@@ -1029,7 +1052,8 @@ enum {
     FPD_OP_EW_MERGE = 26,       /* args: fpd_ew_merge_t */
     FPD_OP_LOSS_KL = 27,        /* args: fpd_loss_kl_t */
     FPD_OP_EMA = 28,            /* args: fpd_ema_t */
-    FPD_OP_GRAD_CLIP = 29       /* args: fpd_grad_clip_t */
+    FPD_OP_GRAD_CLIP = 29,      /* args: fpd_grad_clip_t */
+    FPD_OP_GRAD_ACCUM = 30      /* args: fpd_grad_accum_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;

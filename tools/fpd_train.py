@@ -21,7 +21,9 @@ exponential moving average of the student (utils.ModelEma, TRAIN.EMA_DECAY / EMA
 the per-epoch validation, model_best.pth and final_state.pth then hold the average; checkpoint.pth keeps the raw weights
 (what a resume continues from) and gains ema_state_dict / ema_updates.  TRAIN.CLIP_GRAD_NORM (0 = off, .inf = measure only)
 clips the gradient of every update to that global L2 norm inside the fused step (utils.GradClipper) and adds `GradNorm` /
-`Clipped` to the `Epoch:` line.
+`Clipped` to the `Epoch:` line.  TRAIN.ACCUM_STEPS k > 1 makes one optimizer update per k batches, their gradients averaged
+inside the fused step (each batch keeps its own BatchNorm statistics, as a DataParallel replica would); a window never spans
+epochs, and the `Epoch:` line gains `Updates`.
 """
 import argparse
 import logging
@@ -44,7 +46,7 @@ from fpd_amd.lib.dataset import SyntheticPose, coco, mpii, synthetic_aug  # noqa
 from fpd_amd.lib.dataset.device_pipeline import unbiased_targets  # noqa: E402
 from fpd_amd.lib.dataset.device_dataset import block_range  # noqa: E402
 from fpd_amd.lib.core.loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss  # noqa: E402
-from fpd_amd.lib.utils.utils import (ModelEma, get_grad_clipper, get_model_summary, get_optimizer, load_checkpoint,  # noqa: E402
+from fpd_amd.lib.utils.utils import (ModelEma, get_accum_steps, get_grad_clipper, get_model_summary, get_optimizer, load_checkpoint,  # noqa: E402
                                      multistep_lr, save_checkpoint)
 
 
@@ -200,6 +202,10 @@ def run(args, normal=False):
     clip = get_grad_clipper(cfg, model)                    # TRAIN.CLIP_GRAD_NORM: None when 0; a negative value raises
     if clip is not None:
         logger.info('=> gradient clipping: global L2 norm %g', clip.max_norm)
+    accum = get_accum_steps(cfg)                           # TRAIN.ACCUM_STEPS: batches per optimizer update; below 1 raises
+    if accum > 1:
+        logger.info('=> gradient accumulation: %d micro-batches of %d per update, effective batch %d', accum, bs * world,
+                    accum * bs * world)
     begin_epoch, best_perf = cfg.TRAIN.BEGIN_EPOCH, 0.0
     ckpt = os.path.join(out_dir, 'checkpoint.pth')
     if cfg.AUTO_RESUME and os.path.exists(ckpt):                                              # :224-234
@@ -229,10 +235,11 @@ def run(args, normal=False):
         optimizer.param_groups[0]['lr'] = multistep_lr(base_lr, cfg.TRAIN.LR_STEP, cfg.TRAIN.LR_FACTOR, epoch)   # :253
         if train_type == 'FPD':                                                               # :255-264
             loss = fpd_train(cfg, loader, model, tmodel, pose_criterion, kd_pose_criterion, optimizer, epoch, out_dir,
-                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank, ema=ema, clip=clip)
+                             cfg.LOG_DIR, writer_dict, allreduce=allreduce, world_size=world, rank=rank, ema=ema, clip=clip,
+                             accum=accum)
         else:
             loss = train(cfg, loader, model, pose_criterion, optimizer, epoch, out_dir, cfg.LOG_DIR, writer_dict,
-                         allreduce=allreduce, world_size=world, rank=rank, ema=ema, clip=clip)
+                         allreduce=allreduce, world_size=world, rank=rank, ema=ema, clip=clip, accum=accum)
         torch.cuda.synchronize()
         logger.info('=> epoch %d done in %.1fs, %.1f samples/s, last logged loss %.5f', epoch, time.time() - t0,
                     len(loader) * bs * world / max(time.time() - t0, 1e-9), loss)
