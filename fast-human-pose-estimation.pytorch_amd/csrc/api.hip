@@ -85,6 +85,7 @@ int fpd_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "conv_c3_launches")) return fpd_conv_c3_option(2, value);
     if (!strcmp(name, "conv_tile_launches")) return fpd_conv_tile_launches();        // (read-only: launches conv_tile.hip has served)
     if (!strcmp(name, "wgrad_tile_launches")) return fpd_wgrad_tile_launches();      // (read-only: launches of wgrad_tile_kernel; those handed to wgrad3 are not counted)
+    if (!strcmp(name, "wgrad3_launches")) return fpd_wgrad3_launches();              // (read-only: launches served by wgrad3.hip)
     if (!strcmp(name, "bneck_blocks")) return fpd_bneck_blocks_option(value);
     if (!strcmp(name, "bneck_upadd")) return fpd_bneck_upadd_option(value);          // up-add formed on load (fpd_bneck_t.x2) offered at all
     if (!strcmp(name, "head_blocks")) return fpd_head_blocks_option(value);

@@ -102,6 +102,7 @@ int fpd_wgrad_tile_partials(const fpd_wgrad_t& a);
 int fpd_wgrad_tile_launch(const fpd_wgrad_t& a, hipStream_t st);
 int fpd_wgrad_tile_variant_of(const fpd_wgrad_t& a);      // the wgrad_tile_kernel instantiation that launch runs (packed, see wgrad_tile.hip), -1: declined or handed to wgrad3
 int fpd_wgrad_tile_launches();                     // "wgrad_tile_launches"
+int fpd_wgrad3_launches();                         // "wgrad3_launches" (wgrad3.hip: the launches fpd_wgrad_tile_launch handed over)
 int fpd_wgrad_mfma_partials(const fpd_wgrad_t& a);
 int fpd_wgrad_mfma_launch(const fpd_wgrad_t& a, hipStream_t st);
 int fpd_wgrad_smallc_partials(const fpd_wgrad_t& a);

@@ -22,6 +22,9 @@
 // what the specialised kernel below, the default, is built around.)  At the end the four waves' accumulators are added in a FIXED order through LDS and stored to the
 // range's slab -- no atomics: fpd_wgrad_reduce() adds the slabs in index order, identical bytes run to run.
 // Replaces autograd of nn.Conv2d (weight / bias gradient) in /root/reference/lib/models/hourglass.py:23 (conv2 of a Bottleneck).
+// Bit-exact tests: tests/test_exact_wgrad3_gpu.py on the list W3_WGRAD of tests/_exact_inputs.py (both piece counts, every width,
+// ranges of 1..7 tiles, uneven cuts, ranges that start inside an image, tiles that straddle two images, up to 64 ranges);
+// tests/test_exact_wgrad3_cpu.py restates w3_grid() and asserts without a device that the list reaches those geometries.
 #include <algorithm>
 #include <cstdlib>
 
@@ -687,7 +690,10 @@ static bool w3_grid(const fpd_wgrad_t& a, W3Grid& g) {
     while ((1 << g.lgW) < a.W) ++g.lgW;
     g.nrows = W3_TP / a.W;
     g.ring = 2 * g.nrows + 2;
-    if ((a.N * a.H) % g.nrows != 0 || g.nrows > a.H) return false;       // whole tiles only, a tile within one image's rows (the student's maps)
+    // whole tiles only, and nrows <= H: a tile touches at most two images.  H % nrows != 0 is accepted -- a tile may STRADDLE two
+    // images (rows 16..23 | 0..7 at 2 x 24 x 16): the ring holds flat rows and each k-step's own image row ph[h] decides between
+    // the ring and the zero pixels (the student's maps never get there; tests/test_exact_wgrad3_gpu.py runs it at nrows 16, 8, 4)
+    if ((a.N * a.H) % g.nrows != 0 || g.nrows > a.H) return false;
     g.mtiles = a.N * a.H / g.nrows;
     g.npieces = (a.K / 32) * (a.C / 32);
     // ranges: >= 4 256-pixel tiles per block (prologue + flush of a block cost several tiles; a range is a 144 KB slab), <= 64 slabs, whole groups of 8 (XCDs)
@@ -715,19 +721,26 @@ bool fpd_wgrad3_takes(const fpd_wgrad_t& a) {      // (the variant query of wgra
     W3Grid g;
     return w3_takes(a, g);
 }
+static std::atomic<int> g_w3_launches{0};      // launches this unit has served (tests: "wgrad3_launches")
+int fpd_wgrad3_launches() { return g_w3_launches.load(std::memory_order_relaxed); }
+
 int fpd_wgrad3_launch(const fpd_wgrad_t& a, hipStream_t st) {
     W3Grid g;
     if (!w3_takes(a, g)) return 1;
+    if (a.partial_stride < (int64_t)a.K * 9 * a.C + a.K)      // (include/fpd_amd.h fpd_wgrad_t; before any HIP call)
+        return fpd_fail(-2, "wgrad: partial_stride %lld smaller than weight + bias", (long long)a.partial_stride);
     static const int spec = 1;      // specialised waves (wgrad3s); the uniform kernel stays for fpd_set_option-free A/B builds (-DW3_UNIFORM would select it)
     if (spec) {
         static LdsAttr configured_s;
         if (int rc_ = configured_s.ensure(reinterpret_cast<const void*>(&wgrad3s_kernel<0>), g.lds_s)) return rc_;
         FPD_LAUNCH(wgrad3s_kernel<0>, dim3(g.blocks), dim3(W3_BLK), g.lds_s, st, a, g.nrows, g.lgW, g.npieces, g.nranges, g.mtiles);
+        g_w3_launches.fetch_add(1, std::memory_order_relaxed);
         return 0;
     }
     static LdsAttr configured;
     if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&wgrad3_kernel), g.lds)) return rc_;
     FPD_LAUNCH(wgrad3_kernel, dim3(g.blocks), dim3(W3_BLK), g.lds, st, a, g.nrows, g.lgW, g.npieces, g.nranges, g.mtiles);
+    g_w3_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
 

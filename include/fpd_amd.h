@@ -1107,7 +1107,8 @@ int fpd_set_backend(int32_t backend);         /* FPD_BACKEND_*; returns previous
  * space-to-depth kernels (csrc/stem_s2d.hip) / the im2col kernels (csrc/stem_mfma.hip); a stem launch that moves neither was
  * served by the direct kernels (csrc/stem.hip); "conv_c1_launches" / "conv_c3_launches" / "conv_tile_launches" = read-only:
  * convolution launches served so far by csrc/conv_c1.hip / conv_c3.hip / conv_tile.hip; "wgrad_tile_launches" = read-only:
- * launches of wgrad_tile_kernel itself (csrc/wgrad_tile.hip; those its launch function hands to wgrad3 are not counted).  Returns the
+ * launches of wgrad_tile_kernel itself (csrc/wgrad_tile.hip; those its launch function hands to wgrad3 are not counted);
+ * "wgrad3_launches" = read-only: the fpd_conv_wgrad() launches served by csrc/wgrad3.hip.  Returns the
  * previous value (>= 0; 0 for "wgrad_tile_only"), negative = unknown option. */
 int fpd_set_option(const char* name, int32_t value);
 int fpd_abi_sizeof(const char* struct_name);  /* sizeof of a struct above, -1 if unknown */

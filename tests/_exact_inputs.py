@@ -1,7 +1,8 @@
 """Input constructions, op lists and case lists of the bit-exact tests of the streaming kernels, of the stem, of the halo-tile
-kernels and of the stride-2 convolutions (tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py, tests/test_exact_tile_gpu.py
-on the device; tests/test_exact_inputs_cpu.py for the preconditions, tests/test_exact_variants_cpu.py for the kernel
-instantiations the halo-tile lists reach).  No device is needed to import or use this module.
+kernels, of the wgrad3 weight gradient and of the stride-2 convolutions (tests/test_exact_stream_gpu.py, tests/test_exact_stem_gpu.py,
+tests/test_exact_tile_gpu.py, tests/test_exact_wgrad3_gpu.py on the device; tests/test_exact_inputs_cpu.py for the preconditions,
+tests/test_exact_variants_cpu.py for the kernel instantiations the halo-tile lists reach, tests/test_exact_wgrad3_cpu.py for the
+launch geometries the wgrad3 list reaches).  No device is needed to import or use this module.
 
 Everything here is a small dyadic rational, chosen so that the specification (oracle/plan_interp.py) is EXACT: a kernel that
 groups its partial sums differently, folds its coefficients in another order or rounds an fp32 accumulator to bf16 once must
@@ -236,9 +237,10 @@ def forward(bt, gen, dims, wmode, use_bn, use_res, b=None, stride=1):
     return b, op
 
 
-def wgrad_only(bt, gen, dims, use_bn, stride=1):
+def wgrad_only(bt, gen, dims, use_bn, stride=1, bias=True):
     """A weight gradient as a launch of its own: dw, dbias of conv(relu(bn(x))) (exact per-channel train-mode prologue, or
-    none: the raw x) against dy.  dims = (N, H, W, C, K, R) of the forward convolution."""
+    none: the raw x) against dy.  dims = (N, H, W, C, K, R) of the forward convolution.  bias False: dbias = None (a convolution
+    without a bias: the launch forms dw alone)."""
     N, H, W, C, K, R = dims
     b = Built()
     pad = (R - 1) // 2
@@ -246,9 +248,9 @@ def wgrad_only(bt, gen, dims, use_bn, stride=1):
     x = bt.act((N, H, W, C), small(gen, N, H, W, C, density=0.6 if use_bn else 0.3), 'x')
     dy = bt.act((N, P, Q, K), small(gen, N, P, Q, K, density=0.3), 'dy')
     bn = b.bn(bt, gen, C, N * H * W) if use_bn else None
-    dw, db = bt.buf('grad', (K, R, R, C), torch.zeros(K, R, R, C)), bt.buf('grad', (K,), torch.zeros(K))
+    dw, db = bt.buf('grad', (K, R, R, C), torch.zeros(K, R, R, C)), (bt.buf('grad', (K,), torch.zeros(K)) if bias else None)
     b.ops.append(G.Op('wgrad', x=x, dy=dy, dw=dw, dbias=db, bn=bn, dims=(N, H, W, C, K, R, R, stride, pad, P, Q)))
-    b.compare += [('dw', dw), ('dbias', db)]
+    b.compare += [('dw', dw)] + ([('dbias', db)] if bias else [])
     return b
 
 
@@ -452,8 +454,10 @@ def _check_wgrad(A, b, op, label):
     dy = PI._act(A, op.dy).double()
     tot = torch.nn.grad.conv2d_weight(_nchw(a.abs()), (K, C, R, S), _nchw(dy.abs()), stride=stride, padding=pad)
     _headroom(tot, quantum(a) * quantum(dy), label + ' dw')
-    _headroom(dy.abs().sum((0, 1, 2)), quantum(dy), label + ' dbias')
-    assert float(A.view(op.dw).abs().max()) > 0 and float(A.view(op.dbias).abs().max()) > 0, label + ': all-zero gradient'
+    assert float(A.view(op.dw).abs().max()) > 0, label + ': all-zero gradient'
+    if op.dbias is not None:                              # (a launch without a bias gradient forms dw alone)
+        _headroom(dy.abs().sum((0, 1, 2)), quantum(dy), label + ' dbias')
+        assert float(A.view(op.dbias).abs().max()) > 0, label + ': all-zero bias gradient'
 
 
 def _check_apply(A, b, op, label):
@@ -629,7 +633,8 @@ assert TILE_BWD_TN4 in TILE_BWD
 TILE_PAIR = [c + v for c in [(2, 32, 32, 64, 64, 3), (2, 32, 24, 48, 96, 3), (3, 16, 12, 96, 48, 1)]
              for v in ((True, 'plain'), (False, 'bnrelu_bwd'))]
 # wgrad_tile_kernel<T, R, TP, H4, SMALL>: (N, H, W, C, K, R, BN prologue, storage types).  bf16 3x3 cases stay outside wgrad3's
-# domain (C = K in {32, 64}, power-of-two width, with slabs); each runs with slabs and, up to 8192 pixels, with the single-block flush
+# domain (C = K in {32, 64}, power-of-two width, with slabs: W3_WGRAD below is the list inside it); each runs with slabs and, up
+# to 8192 pixels, with the single-block flush
 TILE_WGRAD = [
     (2, 16, 48, 128, 64, 3, True, BOTH),       # <T, 3, 128>: two (bf16) / four (fp32) channel tiles -- the table is indexed c0 + c
     (1, 16, 16, 192, 64, 3, True, BOTH),       # three channel tiles, a power-of-two width
@@ -647,6 +652,68 @@ TILE_WGRAD = [
 def wgrad_flushes(case):
     """The flushes a TILE_WGRAD case runs with: slabs (True) and, on a small problem, the single block per (k, c) tile (False)."""
     return (True, False) if case[0] * case[1] * case[2] <= 8192 else (True,)
+
+
+# wgrad3 (csrc/wgrad3.hip, the specialised-wave kernel; bf16, 3x3, C = K in {32, 64}, W in {16, 32, 64, 128}, with slabs;
+# tests/test_exact_wgrad3_gpu.py): (N, H, W, C, K, BN prologue).  A tile is 256 pixels = nrows = 256 / W flat image rows, the
+# N*H / nrows tiles are cut into contiguous ranges, a block owns one 32 x 32 piece of one range and keeps the halo in a ring of
+# 2 nrows + 2 rows.  The comments give tiles, ranges and the tiles per range as w3_geometry() below -- the restatement of the
+# library's launch geometry -- finds them; tests/test_exact_wgrad3_cpu.py asserts the restatement against the library's answers
+# and that the list reaches the geometries named here.  No tensor has more than 65536 pixels.
+W3_WGRAD = [
+    (1, 16, 16, 64, 64, True),       # 1, 1, {1}: one tile = one image, both halo rows outside; 28 of 32 blocks idle
+    (2, 16, 16, 64, 64, True),       # 2, 1, {2}: the prefetch of tile i + 2 finds nothing; an image change between the tiles
+    (3, 16, 16, 64, 64, False),      # 3, 1, {3}: no prologue; two image changes
+    (2, 24, 16, 64, 64, True),       # 3, 1, {3}: H % nrows != 0 -- the middle tile STRADDLES two images (rows 16..23 | 0..7)
+    (2, 12, 32, 32, 32, True),       # ... at nrows = 8, one piece
+    (2, 6, 64, 64, 64, True),        # ... at nrows = 4
+    (1, 8, 32, 64, 64, True),        # 1, 1, {1}: H == nrows at every width
+    (1, 4, 64, 64, 64, True),
+    (1, 2, 128, 64, 64, True),       # ... W = 128: the two leading rows are staged as four vectors per thread
+    (3, 2, 128, 32, 32, True),       # 3, 1, {3}: W = 128, every tile a whole image, one piece
+    (1, 14, 128, 32, 32, True),      # 7, 1, {7}: the ring of 6 rows wraps three times
+    (3, 6, 128, 64, 64, True),       # 9, 2, {4, 5}: uneven cut; the second range starts in the middle of an image
+    (5, 24, 32, 32, 32, False),      # 15, 3, {5}: one piece, 3 of 8 blocks live, start slots {0, 4, 8}
+    (17, 16, 16, 32, 32, True),      # 17, 4, {4, 5}: start slots {0, 30, 26, 22} of a ring of 34; four image changes in a range
+    (3, 40, 64, 32, 32, True),       # 30, 7, {4, 5}: 7 ranges in a grid of 8 -- one idle block in a full group
+    (2, 64, 64, 64, 64, True),       # 32, 8, {4}: the first full group, 4 pieces x 8 ranges, no idle block
+    (9, 32, 32, 64, 64, True),       # 36, 8, {4, 5}: 9 ranges rounded down to 8; start slots {0, 14}
+    (5, 40, 64, 64, 64, True),       # 50, 8, {6, 7}: image changes in the middle of the ranges
+    (5, 52, 64, 64, 64, True),       # 65, 16, {4, 5}: a second group of eight with an uneven cut
+    (9, 40, 32, 32, 32, True),       # 45, 8, {5, 6}: eight distinct start slots
+    (1, 64, 128, 32, 32, True),      # 32, 8, {4}: W = 128 at 8 ranges
+    (2, 40, 128, 32, 32, True),      # 40, 8, {5}
+    (2, 128, 128, 32, 32, True),     # 128, 32, {4}: the shape class of the student's layer1 -- 32 ranges, four groups, one piece
+    (16, 64, 64, 32, 32, False),     # 256, 64, {4}: the largest grid a one-piece launch gets; 65536 pixels, the cap of TILE_WGRAD
+]
+# ... and one launch without a bias gradient, at 4 pieces: the bias lanes of the ct == 0 pieces are there and stay unused
+W3_NO_BIAS = (9, 32, 32, 64, 64, True)
+assert W3_NO_BIAS in W3_WGRAD and all(c[0] * c[1] * c[2] <= 65536 for c in W3_WGRAD)
+
+
+def w3_geometry(N, H, W, C, K, ranges=32):
+    """csrc/wgrad3.hip w3_grid() and the kernel's block map restated (ranges: FPD_WGRAD3_RANGES, default 32) -> None where the
+    kernel declines, else a dict: nrows, ring, mtiles, npieces, nranges, blocks, cuts (fpd_cut: range i walks tiles
+    cuts[i] .. cuts[i + 1] - 1), live = {block: (range, piece)} of the blocks that do not return at once."""
+    if not ((C, K) in ((64, 64), (32, 32)) and W in (16, 32, 64, 128)):
+        return None
+    nrows = 256 // W
+    if (N * H) % nrows != 0 or nrows > H:
+        return None
+    mtiles, npieces = N * H // nrows, (K // 32) * (C // 32)
+    r = min(ranges * 4 // npieces, max(1, mtiles // 4))
+    if r >= 8:
+        r = r // 8 * 8
+    nranges = max(1, min(r, mtiles))
+    blocks = (nranges + 7) // 8 * 8 * npieces
+    live = {}
+    for b in range(blocks):
+        q = b >> 3
+        rng = (q // npieces) * 8 + (b & 7)
+        if rng < nranges:
+            live[b] = (rng, q % npieces)
+    return dict(nrows=nrows, ring=2 * nrows + 2, mtiles=mtiles, npieces=npieces, nranges=nranges, blocks=blocks,
+                cuts=[i * mtiles // nranges for i in range(nranges + 1)], live=live)
 
 
 # stride 2 (3x3, pad 1; HRNet's transitions and fuse layers, the 3 -> 64 stem convolution): conv_mfma / conv_smallc / conv_naive
@@ -768,6 +835,10 @@ def tile_wgrad(bt, case):
     return wgrad_only(bt, seed('tw', case[:7]), case[:6], case[6])
 
 
+def w3_wgrad(bt, case, bias=True):
+    return wgrad_only(bt, seed('w3', case, bias), case[:5] + (3,), case[5], bias=bias)
+
+
 def s2_forward(bt, case, wmode):
     return forward(bt, seed('s2f', case, wmode), case + (3,), wmode, case[3] % 8 == 0, False, stride=2)[0]
 
@@ -795,6 +866,7 @@ FAMILIES = [
     (tile_dgrad, [(c, m, fo) for c in TILE_BWD for m in WMODES for fo in (False, True)]),
     (tile_pair, [(c, m) for c in TILE_PAIR for m in WMODES]),
     (tile_wgrad, [(c,) for c in TILE_WGRAD]),
+    (w3_wgrad, [(c, True) for c in W3_WGRAD] + [(W3_NO_BIAS, False)]),
     (s2_forward, [(c, m) for c in S2 for m in WMODES]),
     (s2_wgrad, [(c,) for c in S2]),
 ]

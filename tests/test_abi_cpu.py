@@ -190,11 +190,11 @@ def test_host_side_dispatch_predicates_of_round_3_without_a_device(runtime):
 
 
 def test_halo_tile_counters_and_variant_queries_without_a_device(runtime):
-    """"conv_tile_launches" / "wgrad_tile_launches" are read-only; fpd_conv_tile_variant() / fpd_conv_tile_pair_variant() /
+    """"conv_tile_launches" / "wgrad_tile_launches" / "wgrad3_launches" are read-only; fpd_conv_tile_variant() / fpd_conv_tile_pair_variant() /
     fpd_wgrad_tile_variant() name the instantiation a launch would run (packing: include/fpd_amd.h), -1 where the kernel declines."""
     import ctypes
     R, lib = runtime, runtime.lib()
-    for name in (b'conv_tile_launches', b'wgrad_tile_launches'):
+    for name in (b'conv_tile_launches', b'wgrad_tile_launches', b'wgrad3_launches'):
         n = lib.fpd_set_option(name, 0)
         assert n >= 0 and lib.fpd_set_option(name, n + 5) == n and lib.fpd_set_option(name, 0) == n
     cv = lambda a: lib.fpd_conv_tile_variant(ctypes.byref(a))

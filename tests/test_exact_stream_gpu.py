@@ -93,6 +93,7 @@ def test_c3_dgrad_exact(case, fold, wmode):
     """dz, both sums, the dw / dbias of the separate weight-gradient launch behind it; folded: dgamma, dbeta, the operand du."""
     bt, b = _run(X.c3_dgrad, (case, wmode, fold), ('c3', case[3]), partials=True)
     assert bt.n_c3 == 1, 'the strip kernel did not take the data gradient'
+    assert bt.n_w3 == 1, 'the weight gradient behind it was not served by wgrad3 (tests/test_exact_wgrad3_gpu.py is its own test)'
     if fold:
         assert bt.n_folded == 1 and getattr(b.h['dg'], 'fold_active', False), 'the BN-backward apply was not folded'
     _equal(bt, b, (case, fold, wmode), *(['du'] if fold else []))

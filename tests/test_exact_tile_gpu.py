@@ -16,6 +16,9 @@ launch TN = 1 almost everywhere.  Here
   * stride 2 (conv_mfma / conv_smallc / conv_naive and their weight gradients) forward and weight gradient, back ends 0 and 1
     (back end 2 walks the same kernels as 0 for a stride-2 shape: the halo-tile kernels decline it).
 
+(The bf16 3x3 weight gradients that wgrad_tile's launch function hands to wgrad3 -- C = K in {32, 64}, power-of-two widths, with
+slabs -- have their own file, tests/test_exact_wgrad3_gpu.py.)
+
 Every conv_tile / wgrad_tile test asserts through the launch counters that the kernel served the launch, and that the fold was
 taken exactly where fpd_conv_tile_variant() -- the route function of the launch -- says FOLD.  Which instantiation each case
 launches, and that the lists reach all of them, is checked without a device by tests/test_exact_variants_cpu.py; the

@@ -64,7 +64,16 @@ class Bench:
                 self.gpu.view(b).copy_(v)
         return self
 
-    def run(self, ops, backend, partials=False):
+    poison_slabs = False
+
+    def run(self, ops, backend, partials=False, poison_slabs=None):
+        """poison_slabs: the slab workspace of the weight gradients (uninitialised memory otherwise) is filled with NaN before
+        the plan runs -- a slab word that a kernel leaves unwritten and the reduction reads then shows in dw / dbias.  (Kept on
+        the bench: the back ends below come back here with backend 0 and the three arguments subclasses know.)
+        self.n_w3 / self.n_wtile = launches csrc/wgrad3.hip served / of wgrad_tile_kernel itself during the run (every back end
+        below ends in the plain one)."""
+        if poison_slabs is not None:
+            self.poison_slabs = poison_slabs
         if backend == 'pp' or (isinstance(backend, tuple) and backend[0] == 'pp'):
             # the persistent ping-pong convolution (csrc/conv_pp.hip) forced for every in-domain bf16 shape; ('pp', n): n blocks,
             # so that a block owns many tiles (uneven ranges, ragged last tiles, long ping-pong loops) even on small tensors
@@ -138,17 +147,24 @@ class Bench:
                 lowered.append(low.wprep([(e['w'], e.get('w_fwd'), e.get('w_bwd')) for e in op.entries]))
             else:
                 lowered.append(low.op(op))
+        kept = len(low.keep)
         low.finish_partials()
+        if self.poison_slabs:                # the workspace is the first thing finish_partials() keeps
+            ws = low.keep[kept] if len(low.keep) > kept else None
+            assert ws is not None and ws.dtype == torch.float32 and ws.numel() == low.partial_elems > 0, 'no slab workspace to poison'
+            ws.fill_(float('nan'))
         for code, st in lowered:
             plan.add(code, st)
         self.n_partial_ops = len(low.partials)
         self.n_fused = len(low.fused)
         R.set_backend(prev)
         prev = R.set_backend(backend)
+        w3, wt = R.set_option('wgrad3_launches', 0), R.set_option('wgrad_tile_launches', 0)
         try:
             plan.run(0, len(plan))
             torch.cuda.synchronize()
         finally:
+            self.n_w3, self.n_wtile = R.set_option('wgrad3_launches', 0) - w3, R.set_option('wgrad_tile_launches', 0) - wt
             R.set_backend(prev)
 
     def compare(self, b, atol, rtol, label):
