@@ -98,7 +98,7 @@ int fpd_abi_sizeof(const char* n) {
     SZ(fpd_bn_t); SZ(fpd_conv_t); SZ(fpd_wgrad_t); SZ(fpd_stem_t); SZ(fpd_ew_t); SZ(fpd_loss_t); SZ(fpd_adam_t);
     SZ(fpd_wprep_entry_t); SZ(fpd_bnupd_entry_t); SZ(fpd_memset_t); SZ(fpd_table_t); SZ(fpd_wreduce_entry_t); SZ(fpd_bneck_t); SZ(fpd_conv_pair_t); SZ(fpd_bneck_pair_t); SZ(fpd_ew_pair_t); SZ(fpd_pck_t); SZ(fpd_head_t); SZ(fpd_affsum_t); SZ(fpd_layout_t);
     SZ(fpd_conv_f8_t); SZ(fpd_wquant_entry_t); SZ(fpd_flipmerge_t); SZ(fpd_finalpreds_t); SZ(fpd_targets_t); SZ(fpd_warp_src_t); SZ(fpd_warp_t);
-    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t); SZ(fpd_loss_kl_t); SZ(fpd_ema_t); SZ(fpd_grad_clip_t); SZ(fpd_grad_accum_t);
+    SZ(fpd_loss_ohkm_t); SZ(fpd_sgd_t); SZ(fpd_ew_merge_t); SZ(fpd_loss_kl_t); SZ(fpd_ema_t); SZ(fpd_grad_clip_t); SZ(fpd_grad_accum_t); SZ(fpd_adamw_t);
     SZ(fpd_aug_img_t); SZ(fpd_aug_db_t); SZ(fpd_aug_crop_t); SZ(fpd_augment_t); SZ(fpd_warp_aug_t); SZ(fpd_targets_w_t); SZ(fpd_targets_unbiased_t);
     SZ(fpd_oks_nms_t); SZ(fpd_coco_match_t); SZ(fpd_coco_accum_t); SZ(fpd_val_post_t); SZ(fpd_dark_t);
     SZ(fpd_vis_minmax_t); SZ(fpd_vis_max_preds_t); SZ(fpd_vis_joints_grid_t); SZ(fpd_vis_heatmap_grid_t);
@@ -786,6 +786,22 @@ int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream) {
     return rc ? rc : check_launch();
 }
 
+int fpd_adamw(const fpd_adamw_t* a, fpd_stream_t stream) {
+    FPD_REQUIRE(a, "adamw: null pointer");
+    int rc = fpd_adamw_launch(*a, (hipStream_t)stream);      // (validates through fpd_adamw_geometry_of before it launches)
+    return rc ? rc : check_launch();
+}
+int fpd_adamw_geometry(const fpd_adamw_t* a, int32_t* blocks, int64_t* vec_elems) {
+    FPD_REQUIRE(a && blocks && vec_elems, "adamw_geometry: null pointer");
+    int b = 0;
+    int64_t nvec = 0;
+    const int rc = fpd_adamw_geometry_of(*a, &b, &nvec);
+    if (rc) return rc;
+    *blocks = b;
+    *vec_elems = 4 * nvec;
+    return 0;
+}
+
 int fpd_sgd(const fpd_sgd_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a && a->param && a->grad, "sgd: null pointer");
     FPD_REQUIRE(a->n >= 0, "sgd: n = %lld is negative", (long long)a->n);
@@ -873,7 +889,7 @@ int fpd_nhwc_to_nchw(const void* src, float* dst, int32_t N, int32_t C, int32_t 
 struct fpd_op {
     int32_t type;
     union {
-        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_loss_kl_t losskl; fpd_adam_t adam; fpd_sgd_t sgd; fpd_ew_merge_t ewm; fpd_ema_t ema; fpd_grad_clip_t clip; fpd_grad_accum_t accum;
+        fpd_affsum_t affsum; fpd_layout_t layout; fpd_conv_f8_t conv8; fpd_conv_t conv; fpd_conv_pair_t pair; fpd_bneck_t bneck; fpd_bneck_pair_t bpair; fpd_ew_pair_t epair; fpd_pck_t pck; fpd_head_t head; fpd_wgrad_t wgrad; fpd_stem_t stem; fpd_ew_t ew; fpd_loss_t loss; fpd_loss_ohkm_t lossk; fpd_loss_kl_t losskl; fpd_adam_t adam; fpd_sgd_t sgd; fpd_ew_merge_t ewm; fpd_ema_t ema; fpd_grad_clip_t clip; fpd_grad_accum_t accum; fpd_adamw_t adamw;
         fpd_memset_t mset; fpd_table_t table;
     } u;
 };
@@ -931,6 +947,7 @@ int fpd_plan_add(fpd_plan* p, int32_t op, const void* args, int64_t bytes) {
         case FPD_OP_LOSS_OHKM: want = sizeof(fpd_loss_ohkm_t); break;
         case FPD_OP_LOSS_KL: want = sizeof(fpd_loss_kl_t); break;
         case FPD_OP_ADAM: want = sizeof(fpd_adam_t); break;
+        case FPD_OP_ADAMW: want = sizeof(fpd_adamw_t); break;
         case FPD_OP_SGD: want = sizeof(fpd_sgd_t); break;
         case FPD_OP_EMA: want = sizeof(fpd_ema_t); break;
         case FPD_OP_GRAD_CLIP: want = sizeof(fpd_grad_clip_t); break;
@@ -1013,6 +1030,7 @@ static void set_op_tag(int idx, const fpd_op& o) {
         case FPD_OP_LOSS_OHKM: snprintf(t, sizeof(t), "loss_ohkm B=%d J=%d H=%d W=%d S=%d k=%d,%d", o.u.lossk.base.B, o.u.lossk.base.J, o.u.lossk.base.H, o.u.lossk.base.W, o.u.lossk.base.S, o.u.lossk.topk_pose, o.u.lossk.topk_kd); break;
         case FPD_OP_LOSS_KL: snprintf(t, sizeof(t), "loss_kl B=%d J=%d H=%d W=%d S=%d kl=%d,%d T=%g,%g", o.u.losskl.base.B, o.u.losskl.base.J, o.u.losskl.base.H, o.u.losskl.base.W, o.u.losskl.base.S, o.u.losskl.kl_pose, o.u.losskl.kl_kd, (double)o.u.losskl.temp_pose, (double)o.u.losskl.temp_kd); break;
         case FPD_OP_ADAM: snprintf(t, sizeof(t), "adam n=%lld", (long long)o.u.adam.n); break;
+        case FPD_OP_ADAMW: snprintf(t, sizeof(t), "adamw n=%lld wd=%g%s%s", (long long)o.u.adamw.n, (double)o.u.adamw.weight_decay, o.u.adamw.vmax ? " amsgrad" : "", o.u.adamw.no_decay_bits ? " mask" : ""); break;
         case FPD_OP_SGD: snprintf(t, sizeof(t), "sgd n=%lld momentum=%g wd=%g%s", (long long)o.u.sgd.n, (double)o.u.sgd.momentum, (double)o.u.sgd.weight_decay, o.u.sgd.nesterov ? " nesterov" : ""); break;
         case FPD_OP_EMA: snprintf(t, sizeof(t), "ema nseg=%d n0=%lld decay=%g%s", o.u.ema.nseg, (long long)o.u.ema.seg[0].n, o.u.ema.decay, o.u.ema.warmup ? " warmup" : ""); break;
         case FPD_OP_GRAD_CLIP: snprintf(t, sizeof(t), "grad_clip n=%lld max_norm=%g", (long long)o.u.clip.n, (double)o.u.clip.max_norm); break;
@@ -1047,6 +1065,7 @@ static int run_op(const fpd_op& o, fpd_stream_t s) {
         case FPD_OP_LOSS_OHKM: return fpd_loss_ohkm(&o.u.lossk, s);
         case FPD_OP_LOSS_KL: return fpd_loss_kl(&o.u.losskl, s);
         case FPD_OP_ADAM: return fpd_adam(&o.u.adam, s);
+        case FPD_OP_ADAMW: return fpd_adamw(&o.u.adamw, s);
         case FPD_OP_SGD: return fpd_sgd(&o.u.sgd, s);
         case FPD_OP_EMA: return fpd_ema(&o.u.ema, s);
         case FPD_OP_GRAD_CLIP: return fpd_grad_clip(&o.u.clip, s);

@@ -174,6 +174,8 @@ int fpd_loss_kl_launch(const fpd_loss_kl_t& a, hipStream_t st);          // csrc
 int64_t fpd_loss_kl_scratch_size(const fpd_loss_t& a);
 int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st);
 int fpd_sgd_launch(const fpd_sgd_t& a, hipStream_t st);
+int fpd_adamw_launch(const fpd_adamw_t& a, hipStream_t st);              // csrc/adamw.hip: the streaming kernel + the counter's tick
+int fpd_adamw_geometry_of(const fpd_adamw_t& a, int* blocks, int64_t* nvec);  // its validation, grid and 16-byte vectors
 int fpd_ema_launch(const fpd_ema_t& a, hipStream_t st);                  // csrc/ema.hip: the streaming kernel + the counter's tick
 int fpd_ema_geometry_of(const fpd_ema_t& a, int* blocks, int64_t* nvec);      // its validation, grid and vectors per segment
 int fpd_grad_clip_launch(const fpd_grad_clip_t& a, hipStream_t st);      // csrc/grad_clip.hip: sums of squares, finalise, in-place scale

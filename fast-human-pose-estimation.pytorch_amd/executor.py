@@ -841,6 +841,11 @@ class GraphInstance:
         return self.A.view(self.g.out_grads[i].buf)
 
 
+def _is_adamw(opt):
+    from .lib.utils.utils import FusedAdamW      # (imported here: lib.utils imports this package's runtime)
+    return isinstance(opt, FusedAdamW)
+
+
 class FusedFPDStep:
     """The fused FPD iteration (lib/core/function.py:119-147 of the reference) on one GPU:
          teacher forward (eval BN) -> student forward (train BN) -> fused pose+KD loss fwd/bwd
@@ -947,6 +952,10 @@ class FusedFPDStep:
             self._add_sgd(sgd, student_state, n, ema, clip)
             self._add_accum(student_state)
             return
+        if adam is not None and _is_adamw(adam):    # a lib.utils.utils.FusedAdamW: one OP_ADAMW where OP_ADAM sits
+            self._add_adamw(adam, student_state, n, ema, clip)
+            self._add_accum(student_state)
+            return
         if adam is not None:        # share moments / step / lr with a lib.utils.utils.FusedAdam (checkpointable state)
             self.m, self.v, self.lr_dev, self.step_dev = adam.m, adam.v, adam.lr_dev, adam.step_dev
             betas, eps = adam.param_groups[0]['betas'], adam.param_groups[0]['eps']
@@ -1027,6 +1036,27 @@ class FusedFPDStep:
             raise R.FpdError('FusedFPDStep: ema= averages another model than the student of this step')
         self._ema_args = a
         self.student.plan.add(R.OP_EMA, a)
+
+    def _add_adamw(self, adamw, student_state, n, ema=None, clip=None):
+        """The optimizer range = one OP_ADAMW sharing m, v, vmax, the exemption mask, lr_dev and step_dev with the FusedAdamW,
+        with the hyperparameters of its first param group as they are NOW (core.function keys its step cache on them)."""
+        g = adamw.param_groups[0]
+        self.m, self.v, self.vmax = adamw.m, adamw.v, adamw.vmax
+        self.lr_dev, self.step_dev = adamw.lr_dev, adamw.step_dev
+        self.betas, self.eps = g['betas'], g['eps']
+        words = (n + 31) // 32
+        if (adamw.m.numel() < n or adamw.v.numel() < n or (adamw.vmax is not None and adamw.vmax.numel() < n)
+                or (adamw.mask is not None and adamw.mask.numel() < words)
+                or adamw.model._flat['param'].data_ptr() != student_state.A.tensor('param').data_ptr()):
+            raise R.FpdError('FusedFPDStep: adam= is the FusedAdamW of another model than the student of this step '
+                             '(its moment arenas and mask do not cover the %d elements of this parameter arena)' % n)
+        a = adamw.adamw_args(student_state)
+        self._adamw_args = a      # (grad_scale 1: the loss kernel already folds 1/world_size into the gradient)
+        b = len(self.student.plan)
+        self._add_clip(clip, student_state)
+        self.student.plan.add(R.OP_ADAMW, a)
+        self._add_ema(ema, student_state)
+        self.student.rng['adam'] = (b, len(self.student.plan))
 
     def _add_sgd(self, sgd, student_state, n, ema=None, clip=None):
         """The optimizer range ('adam' by name, so that run / capture / phase timing need not know) = one OP_SGD with the

@@ -97,7 +97,11 @@ def _defaults():
                   'CLIP_GRAD_NORM': 0.0,
                   # not in the reference: one optimizer update per this many batches, their gradients averaged inside the fused
                   # step (FusedFPDStep accum=); 1 = every batch; the tools refuse a value below 1
-                  'ACCUM_STEPS': 1},
+                  'ACCUM_STEPS': 1,
+                  # not in the reference: OPTIMIZER adamw (utils.FusedAdamW) decays the weights by WD, decoupled from the
+                  # gradient.  AMSGRAD: keep the running maximum of the second moment (adamw, and adam); NO_DECAY_NORM_BIAS:
+                  # BN weights / biases and conv biases are exempt from the decay (adamw only)
+                  'AMSGRAD': False, 'NO_DECAY_NORM_BIAS': False},
         'TEST': {'BATCH_SIZE_PER_GPU': 32, 'FLIP_TEST': False, 'POST_PROCESS': False, 'SHIFT_HEATMAP': False, 'MODEL_FILE': '',
                  # read by DATASET.DATASET coco (default.py:110-119); NMS_THRE and BBOX_THRE are accepted and unused, as there
                  'USE_GT_BBOX': False, 'IMAGE_THRE': 0.1, 'NMS_THRE': 0.6, 'SOFT_NMS': False, 'OKS_THRE': 0.5, 'IN_VIS_THRE': 0.0,

@@ -6,7 +6,7 @@ student weights).  Like the reference (function.py:150-155) EVERY iteration feed
 device appends {avg_acc, cnt, pose, kd} of each iteration to a ring (csrc/pck.hip) that is drained -- the only host
 synchronisation of the loop -- when a log line is due (PRINT_FREQ) and at the end of the epoch.
 
-Not silently substituted: the fused step implements Adam and SGD (lib.utils.utils.FusedAdam / FusedSGD) and JointsMSELoss /
+Not silently substituted: the fused step implements Adam, AdamW and SGD (lib.utils.utils.FusedAdam / FusedAdamW / FusedSGD) and JointsMSELoss /
 JointsOHKMMSELoss / JointsKLDLoss criteria; any other optimizer / criterion object raises instead of being ignored."""
 import logging
 import os
@@ -16,7 +16,7 @@ import torch
 
 from ... import executor as E
 from ... import runtime as R
-from ..utils.utils import FusedAdam, FusedSGD
+from ..utils.utils import FusedAdam, FusedAdamW, FusedSGD
 from .evaluate import accuracy  # noqa: F401  (re-exported like the reference's core.function namespace)
 from .loss import JointsKLDLoss, JointsMSELoss, JointsOHKMMSELoss
 
@@ -46,9 +46,9 @@ def _check_supported(optimizer, pose_criterion, kd_pose_criterion):
     silently ignore.  Returns the use_target_weight pair and the topk pair (None for a JointsMSELoss criterion; None instead
     of the pair when neither criterion mines).  With a JointsKLDLoss in either slot a third element follows: the temperature
     pair (None for a JointsMSELoss criterion); a KL criterion beside a mining one is refused."""
-    if not isinstance(optimizer, (FusedAdam, FusedSGD)):
-        raise R.FpdError('fpd_train: the fused MI355X step implements Adam and SGD only (utils.get_optimizer with '
-                         "TRAIN.OPTIMIZER 'adam' -> FusedAdam, 'sgd' -> FusedSGD); got %s -- its update rule and state "
+    if not isinstance(optimizer, (FusedAdam, FusedAdamW, FusedSGD)):
+        raise R.FpdError('fpd_train: the fused MI355X step implements Adam, AdamW and SGD only (utils.get_optimizer with '
+                         "TRAIN.OPTIMIZER 'adam' -> FusedAdam, 'adamw' -> FusedAdamW, 'sgd' -> FusedSGD); got %s -- its update rule and state "
                          'would be ignored' % type(optimizer).__name__)
     for name, c in (('pose_criterion', pose_criterion), ('kd_pose_criterion', kd_pose_criterion)):
         if not isinstance(c, (JointsMSELoss, JointsOHKMMSELoss, JointsKLDLoss)):
@@ -76,7 +76,8 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     clip: a utils.GradClipper of the student (its max_norm lives in the recorded plan op, so it is part of the key; the object
     is compared by identity).  accum: FusedFPDStep's micro-batches per update; above 1 it adds plan ranges, so it is part of
     the key (None and 1 are the same step).
-    A FusedSGD's (momentum, weight_decay, nesterov) live in the recorded plan op, so they are part of the key."""
+    A FusedSGD's (momentum, weight_decay, nesterov) live in the recorded plan op, so they are part of the key; so are a
+    FusedAdamW's ('adamw', weight_decay, amsgrad, no_decay_norm_bias) and its betas and eps."""
     s, t = _unwrap(model), (_unwrap(tmodel) if tmodel is not None else None)
     # The cache lives ON the student module (not in a module-level dict keyed by id(): ids are recycled once an object
     # is collected, and a global would keep every plan and its arenas alive for the life of the process).  The teacher
@@ -89,6 +90,10 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     if is_sgd:
         g = optimizer.param_groups[0]
         key += (('sgd', float(g['momentum']), float(g['weight_decay']), bool(g['nesterov'])),)
+    if isinstance(optimizer, FusedAdamW):      # its decay, betas and eps live in the recorded plan op, like a FusedSGD's
+        g = optimizer.param_groups[0]
+        key += (('adamw', float(g['weight_decay']), bool(optimizer.amsgrad), bool(optimizer.no_decay_norm_bias)),
+                ('betas', float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])))
     if ema is not None:
         key += (('ema', float(ema.decay), bool(ema.warmup)),)
     if clip is not None:

@@ -7,8 +7,9 @@ from ... import runtime as R
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
-    """What FusedAdam and FusedSGD share: one param group over the model's flat arenas, the device lr / step scalars the
-    kernels read, and the per-parameter views of a flat state arena in the reference's shapes."""
+    """What FusedAdam, FusedAdamW and FusedSGD share: one param group over the model's flat arenas (FusedAdamW splits it in two
+    under its exemption), the device lr / step scalars the kernels read, and the per-parameter views of a flat state arena
+    in the reference's shapes."""
 
     def _init_flat(self, model, defaults):
         self.model = model.module if hasattr(model, 'module') else model
@@ -108,6 +109,172 @@ class FusedAdam(_FlatOptimizer):
         for k in ('lr', 'betas', 'eps', 'initial_lr'):   # initial_lr: what torch's LR schedulers resume from
             if k in g:
                 self.param_groups[0][k] = tuple(g[k]) if k == 'betas' else g[k]
+        self.param_groups[0].setdefault('initial_lr', self.param_groups[0]['lr'])
+        self._lr_host = None
+        self.sync_lr()
+
+
+def no_decay_mask(table):
+    """The exemption of `no_decay_norm_bias` over a graph.ParamTable: every trainable tensor whose logical shape has fewer than
+    2 dimensions (BN weight and bias, conv bias).  -> (ranges, words): the exempt [first, end) element ranges of the parameter
+    arena in table order, and the numpy uint32 mask fpd_adamw_t.no_decay_bits takes -- bit i & 31 of word i >> 5 set = element
+    i is exempt, ceil(n / 32) words.  The alignment gaps between tensors get no bit: their parameters and gradients are zero,
+    which the decay leaves alone."""
+    import numpy as np
+    n = table.sizes['param']
+    ranges = [(table[k].off, table[k].off + table[k].numel) for k in table.trainable_keys() if len(table[k].shape) < 2]
+    bits = np.zeros((n + 31) // 32 * 32, dtype=np.uint8)
+    for lo, hi in ranges:
+        bits[lo:hi] = 1
+    return ranges, np.packbits(bits, bitorder='little').view('<u4').astype(np.uint32)
+
+
+class FusedAdamW(_FlatOptimizer):
+    """torch.optim.AdamW(lr, betas, eps, weight_decay, amsgrad) semantics -- decoupled weight decay, optionally the AMSGrad
+    maximum -- as ONE HIP launch (csrc/adamw.hip) over the model's flat parameter / gradient arenas.  no_decay_norm_bias: the
+    tensors with fewer than 2 dimensions (BN weight and bias, conv bias) are exempt from the decay, through a bit mask the
+    kernel reads (1/8 byte per element); they form a second param group with weight_decay 0, the way the recipes that exempt
+    them hand two groups to torch.  weight_decay = 0 with amsgrad is torch.optim.Adam(amsgrad=True).  One lr serves both
+    groups: param_groups[0]['lr'] is read at every step, like FusedAdam's.  The second moment maximum is allocated only under
+    amsgrad.  Create it after .to(device), like any torch optimizer."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, no_decay_norm_bias=False):
+        if not 0.0 <= lr:
+            raise ValueError('Invalid learning rate: %r' % (lr,))
+        if not 0.0 <= eps:
+            raise ValueError('Invalid epsilon value: %r' % (eps,))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError('Invalid beta parameter at index 0: %r' % (betas[0],))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError('Invalid beta parameter at index 1: %r' % (betas[1],))
+        if not 0.0 <= weight_decay < float('inf'):
+            raise ValueError('Invalid weight_decay value: %r' % (weight_decay,))
+        self.amsgrad, self.no_decay_norm_bias = bool(amsgrad), bool(no_decay_norm_bias)
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=self.amsgrad, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None)
+        m = model.module if hasattr(model, 'module') else model
+        table = m.table
+        exempt = [self.no_decay_norm_bias and len(table[k].shape) < 2 for k in table.trainable_keys()]
+        # position in the state dict -> index of the trainable tensor: torch numbers the parameters group by group
+        self._order = [i for i, e in enumerate(exempt) if not e] + [i for i, e in enumerate(exempt) if e]
+        self._group_sizes = [len(exempt) - sum(exempt)] + ([sum(exempt)] if self.no_decay_norm_bias else [])
+        flat = self._init_flat(model, defaults)
+        self.m = torch.zeros_like(flat)
+        self.v = torch.zeros_like(flat)
+        self.vmax = torch.zeros_like(flat) if self.amsgrad else None
+        self.no_decay_ranges, self.mask = [], None
+        if self.no_decay_norm_bias:
+            self.no_decay_ranges, words = no_decay_mask(table)
+            self.mask = torch.from_numpy(words.view('int32').copy()).to(flat.device)
+
+    def _init_flat(self, model, defaults):
+        flat = super()._init_flat(model, defaults)
+        if self.no_decay_norm_bias:              # re-group: the decayed tensors first, then the exempt ones at weight_decay 0
+            params = self.param_groups[0]['params']
+            if len(params) != len(self._order):
+                raise R.FpdError('FusedAdamW: the model has %d parameters, its table %d trainable tensors' % (len(params), len(self._order)))
+            k = self._group_sizes[0]
+            g1 = {key: v for key, v in self.param_groups[0].items() if key != 'params'}
+            g1.update(weight_decay=0.0, params=[params[i] for i in self._order[k:]])
+            self.param_groups[0]['params'] = [params[i] for i in self._order[:k]]
+            self.param_groups.append(g1)
+        return flat
+
+    def sync_lr(self):
+        for g in self.param_groups[1:]:          # one lr: the schedule writes group 0, the state dict shows it in both
+            g['lr'] = self.param_groups[0]['lr']
+            if 'initial_lr' in self.param_groups[0]:
+                g['initial_lr'] = self.param_groups[0]['initial_lr']
+        super().sync_lr()
+
+    def adamw_args(self, st=None):
+        """The filled fpd_adamw_t over the arenas of the model's device state: hyperparameters of group 0 as they are now, the
+        schedule through lr_dev / step_dev."""
+        st = self.model.device_state() if st is None else st
+        g = self.param_groups[0]
+        a = R.AdamWT()
+        a.n = st.table.sizes['param']
+        a.param, a.grad = st.A.tensor('param').data_ptr(), st.A.tensor('grad').data_ptr()
+        a.m, a.v, a.param_lp = self.m.data_ptr(), self.v.data_ptr(), None
+        a.lr, a.beta1, a.beta2, a.eps = g['lr'], g['betas'][0], g['betas'][1], g['eps']
+        a.bias_corr1 = a.bias_corr2 = 1.0
+        a.grad_scale = 1.0
+        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
+        a.weight_decay = g['weight_decay']
+        a.vmax = self.vmax.data_ptr() if self.vmax is not None else None
+        a.no_decay_bits = self.mask.data_ptr() if self.mask is not None else None
+        return a
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if not self.m.is_cuda:
+            raise R.FpdError('FusedAdamW.step needs the model on a CUDA (ROCm) device; there is no CPU path')
+        self.sync_lr()
+        R.check(R.lib().fpd_adamw(self.adamw_args(), R.current_stream()), 'fpd_adamw')
+
+    # ---- checkpoint interop: torch.optim.AdamW's layout (per-parameter step / exp_avg / exp_avg_sq [/ max_exp_avg_sq] in the
+    #      reference's OIHW shapes).  One param group, or with the exemption two -- decayed first, exempt at weight_decay 0,
+    #      ids numbered group by group as torch numbers them -- so the dict loads into a stock AdamW built with the same
+    #      groups, and back ----
+    def _state_arenas(self):
+        names = [('exp_avg', self.m), ('exp_avg_sq', self.v)]
+        return names + ([('max_exp_avg_sq', self.vmax)] if self.amsgrad else [])
+
+    def state_dict(self):
+        self.sync_lr()
+        step = self.step_dev.to(torch.float32).reshape(())
+        state = {}
+        if int(self.step_dev.item()) > 0:
+            views = [(name, self._views(t)) for name, t in self._state_arenas()]
+            for pos, i in enumerate(self._order):
+                state[pos] = dict({'step': step.clone()}, **{name: v[i].clone() for name, v in views})
+        groups, first = [], 0
+        for g, k in zip(self.param_groups, self._group_sizes):
+            d = {key: v for key, v in g.items() if key != 'params'}
+            d['params'] = list(range(first, first + k))
+            groups.append(d)
+            first += k
+        return {'state': state, 'param_groups': groups}
+
+    def load_state_dict(self, sd):
+        groups = sd['param_groups']
+        if [len(g['params']) for g in groups] != self._group_sizes:
+            raise ValueError('optimizer state partitions the parameters into groups of %r, this FusedAdamW (no_decay_norm_bias=%s) '
+                             'into %r' % ([len(g['params']) for g in groups], self.no_decay_norm_bias, self._group_sizes))
+        if any(bool(g.get('amsgrad', False)) != self.amsgrad for g in groups):
+            raise ValueError('optimizer state has amsgrad=%r, this FusedAdamW amsgrad=%r' % (groups[0].get('amsgrad', False), self.amsgrad))
+        if any(g.get('maximize', False) for g in groups):
+            raise ValueError('FusedAdamW implements maximize False; the state has maximize True')
+        if len(groups) == 2 and float(groups[1].get('weight_decay', 0)) != 0.0:
+            raise ValueError('the exempt group of the optimizer state has weight_decay %r, not 0' % (groups[1]['weight_decay'],))
+        if float(groups[0].get('weight_decay', 0)) < 0.0:
+            raise ValueError('Invalid weight_decay value: %r' % (groups[0]['weight_decay'],))
+        st = sd.get('state', {})
+        ids = [pid for g in groups for pid in g['params']]
+        if len(st) not in (0, len(ids)):
+            raise ValueError('optimizer state has %d parameter entries, the model has %d' % (len(st), len(ids)))
+        arenas = self._state_arenas()
+        views = [(name, self._views(t)) for name, t in arenas]
+        for pid, i in zip(ids, self._order):     # every entry is looked at before anything is written
+            e = st.get(pid)
+            for name, v in views:
+                if e is not None and (name not in e or tuple(e[name].shape) != tuple(v[i].shape)):
+                    raise ValueError('optimizer state entry %r: %s is missing or has another shape than the parameter' % (pid, name))
+        for _, t in arenas:
+            t.zero_()
+        self.step_dev.zero_()
+        for pid, i in zip(ids, self._order):
+            e = st.get(pid)
+            if e is None:
+                continue
+            for name, v in views:
+                v[i].copy_(e[name])
+            self.step_dev.fill_(int(float(e['step'])))
+        for k in ('lr', 'betas', 'eps', 'weight_decay', 'initial_lr'):   # initial_lr: what torch's LR schedulers resume from
+            if k in groups[0]:
+                self.param_groups[0][k] = tuple(groups[0][k]) if k == 'betas' else groups[0][k]
+        for g in self.param_groups[1:]:
+            g.update({k: self.param_groups[0][k] for k in ('lr', 'betas', 'eps', 'initial_lr') if k in self.param_groups[0]})
         self.param_groups[0].setdefault('initial_lr', self.param_groups[0]['lr'])
         self._lr_host = None
         self.sync_lr()
@@ -380,10 +547,31 @@ def multistep_lr(base_lr, milestones, gamma, epoch):
     return base_lr * gamma ** sum(1 for m in milestones if m <= epoch + 1)
 
 
+def _cfg_flag(cfg, name):
+    """TRAIN.<name> as a bool; a config object without the key (callers that build only the keys they read) means false."""
+    try:
+        v = getattr(cfg.TRAIN, name)
+    except (AttributeError, KeyError):
+        return False
+    if isinstance(v, str) and v.lower() in ('true', 'false'):     # YAML's spelling, as a KEY VALUE pair of the command line
+        v = v.lower() == 'true'
+    if not isinstance(v, bool):
+        raise ValueError('TRAIN.%s must be true or false, got %r' % (name, v))
+    return v
+
+
 def get_optimizer(cfg, model):
-    """utils.py:59-75."""
+    """utils.py:59-75, plus what the reference does not offer: TRAIN.OPTIMIZER adamw (decoupled TRAIN.WD, TRAIN.AMSGRAD,
+    TRAIN.NO_DECAY_NORM_BIAS), and adam with TRAIN.AMSGRAD = torch.optim.Adam(amsgrad=True).  Plain adam ignores TRAIN.WD, as the
+    reference does."""
+    amsgrad = _cfg_flag(cfg, 'AMSGRAD')
     if cfg.TRAIN.OPTIMIZER == 'adam':
+        if amsgrad:
+            return FusedAdamW(model, lr=cfg.TRAIN.LR, weight_decay=0, amsgrad=True)
         return FusedAdam(model, lr=cfg.TRAIN.LR)
+    if cfg.TRAIN.OPTIMIZER == 'adamw':
+        return FusedAdamW(model, lr=cfg.TRAIN.LR, weight_decay=cfg.TRAIN.WD, amsgrad=amsgrad,
+                          no_decay_norm_bias=_cfg_flag(cfg, 'NO_DECAY_NORM_BIAS'))
     if cfg.TRAIN.OPTIMIZER == 'sgd':
         return FusedSGD(model, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM, weight_decay=cfg.TRAIN.WD,
                         nesterov=cfg.TRAIN.NESTEROV)

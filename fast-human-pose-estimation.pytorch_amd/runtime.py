@@ -18,7 +18,7 @@ BACKEND_MFMA, BACKEND_NAIVE, BACKEND_MFMA_GENERIC = 0, 1, 2
 (OP_CONV, OP_WGRAD, OP_STEM_FWD, OP_STEM_WGRAD, OP_EW, OP_LOSS, OP_ADAM, OP_MEMSET, OP_WPREP, OP_BNUPD,
  OP_WREDUCE, OP_BNECK, OP_BNECK_FOLD, OP_CONV_PAIR, OP_BNECK_PAIR, OP_EW_PAIR, OP_PCK, OP_HEAD, OP_HEAD_FOLD,
  OP_NOP, OP_AFFSUM, OP_NCHW2NHWC, OP_CONV_F8, OP_WQUANT, OP_LOSS_OHKM, OP_SGD, OP_EW_MERGE, OP_LOSS_KL, OP_EMA,
- OP_GRAD_CLIP, OP_GRAD_ACCUM) = range(31)
+ OP_GRAD_CLIP, OP_GRAD_ACCUM, OP_ADAMW) = range(32)
 ACCUM_FIRST, ACCUM_ADD, ACCUM_FIN = 0, 1, 2
 EWM_MAXPOOL_BWD, EWM_SUMPOOL = 0, 1
 AFFSUM_MAX = 4
@@ -257,6 +257,10 @@ class AdamT(C.Structure):
                 ('bias_corr2', _f32), ('grad_scale', _f32), ('_pad', _i32), ('lr_dev', _vp), ('step_dev', _vp)]
 
 
+class AdamWT(C.Structure):
+    _fields_ = AdamT._fields_ + [('weight_decay', _f32), ('_pad2', _i32), ('vmax', _vp), ('no_decay_bits', _vp)]
+
+
 class SgdT(C.Structure):
     _fields_ = [('n', _i64), ('param', _vp), ('grad', _vp), ('buf', _vp), ('param_lp', _vp), ('lr', _f32),
                 ('momentum', _f32), ('weight_decay', _f32), ('grad_scale', _f32), ('nesterov', _i32), ('_pad', _i32),
@@ -317,7 +321,7 @@ _STRUCTS = {'fpd_bn_t': BnT, 'fpd_conv_t': ConvT, 'fpd_wgrad_t': WgradT, 'fpd_st
             'fpd_coco_match_t': CocoMatchT, 'fpd_coco_accum_t': CocoAccumT, 'fpd_val_post_t': ValPostT, 'fpd_dark_t': DarkT,
             'fpd_vis_minmax_t': VisMinmaxT, 'fpd_vis_max_preds_t': VisMaxPredsT, 'fpd_vis_joints_grid_t': VisJointsGridT,
             'fpd_vis_heatmap_grid_t': VisHeatmapGridT, 'fpd_loss_kl_t': LossKlT, 'fpd_ema_t': EmaT,
-            'fpd_grad_clip_t': GradClipT, 'fpd_grad_accum_t': GradAccumT}
+            'fpd_grad_clip_t': GradClipT, 'fpd_grad_accum_t': GradAccumT, 'fpd_adamw_t': AdamWT}
 
 # every symbol include/fpd_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 2      # include/fpd_amd.h FPD_ABI_VERSION
@@ -380,6 +384,8 @@ SYMBOLS = {
     'fpd_loss_kl': (C.c_int, [C.POINTER(LossKlT), _vp]),
     'fpd_loss_kl_scratch_bytes': (C.c_int64, [C.POINTER(LossT)]),
     'fpd_adam': (C.c_int, [C.POINTER(AdamT), _vp]),
+    'fpd_adamw': (C.c_int, [C.POINTER(AdamWT), _vp]),
+    'fpd_adamw_geometry': (C.c_int, [C.POINTER(AdamWT), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'fpd_sgd': (C.c_int, [C.POINTER(SgdT), _vp]),
     'fpd_ema': (C.c_int, [C.POINTER(EmaT), _vp]),
     'fpd_ema_geometry': (C.c_int, [C.POINTER(EmaT), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),

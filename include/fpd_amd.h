@@ -387,6 +387,47 @@ typedef struct {
     int64_t* step_dev;     /* optional: device step counter t (bias corrections use t+1; incremented after) */
 } fpd_adam_t;
 
+/* torch.optim.AdamW(lr, betas, eps, weight_decay, amsgrad) step over one flat fp32 arena: fpd_adam_t's fields plus the
+ * decoupled weight decay, the AMSGrad maximum and a bit mask of elements the decay skips.  Arithmetic in csrc/adamw_math.h,
+ * one float32 rounding per operation, never fused:
+ *   g = grad * grad_scale
+ *   if element i decays:  p = p * keep,  keep = 1 - lr * weight_decay     (one multiply, one subtract; torch's
+ *                                                                          param.mul_(1 - lr * wd), BEFORE the moments)
+ *   m = beta1 * m + (1 - beta1) * g
+ *   v = beta2 * v + ((1 - beta2) * g) * g
+ *   vmax != NULL (AMSGrad):  vmax = (v > vmax || v != v) ? v : vmax;  vhat = vmax     (torch.maximum: a NaN wins)
+ *   else                     vhat = v
+ *   denom = sqrtf(vhat) * inv_sqrt_bc2 + eps
+ *   p = p - step_size * (m / denom)
+ * with bc1 = (float)(1 - pow((double)beta1, t)), bc2 likewise, t = *step_dev + 1 (pow in double on the float32 betas),
+ * step_size = lr / bc1 and inv_sqrt_bc2 = 1 / sqrtf(bc2) in float32 -- fpd_adam's formula with two insertions.  The schedule
+ * comes from lr_dev / step_dev, or, with a NULL pointer, from lr resp. bias_corr1 / bias_corr2 of the struct.  The decay is
+ * decoupled only (no L2 term in the gradient); weight_decay = 0 with vmax is torch.optim.Adam(amsgrad = True).
+ * Element i decays when weight_decay != 0 and bit (i & 31) of no_decay_bits[i >> 5] is clear; a NULL mask = the decay
+ * covers the arena.  The mask has ceil(n / 32) words.  An element whose gradient, m and v are zero keeps m and v, and keeps a
+ * parameter of +-0 (eps > 0): the alignment gaps of an arena need no mask bit.
+ * One streaming launch (256 threads a block, the grid cap of the flat optimizer launches): 16-byte vectors where param, grad,
+ * m, v and vmax are 16-byte aligned and param_lp 8-byte aligned, element by element otherwise, a scalar tail; a one-thread
+ * launch behind it adds 1 to *step_dev, so no block reads a counter that has moved.
+ * Refused before any launch: n < 0 or n >= 2^60, a null param / grad / m / v, weight_decay negative or not finite, a beta
+ * outside [0, 1), eps negative or NaN, a misaligned pointer, any written range (param, m, v, vmax, param_lp, the counter)
+ * overlapping any other range. */
+typedef struct {
+    int64_t n;
+    float* param; const float* grad; float* m; float* v;
+    void* param_lp;        /* optional bf16 copy [n], round to nearest even */
+    float lr, beta1, beta2, eps;
+    float bias_corr1, bias_corr2;   /* 1-beta^t, used when step_dev is NULL */
+    float grad_scale;      /* multiply grads first (1/world_size) */
+    int32_t _pad;
+    const float* lr_dev;   /* optional: read lr from device memory (graph-replay safe) */
+    int64_t* step_dev;     /* optional: device step counter t (bias corrections use t+1; incremented after) */
+    float weight_decay;    /* >= 0, decoupled */
+    int32_t _pad2;
+    float* vmax;           /* optional [n]: non-NULL = AMSGrad, the running maximum of v */
+    const uint32_t* no_decay_bits;   /* optional [ceil(n / 32)]: a set bit exempts that element from the decay */
+} fpd_adamw_t;
+
 /* torch.optim.SGD(lr, momentum, dampening = 0, weight_decay, nesterov, maximize = False) step over one flat fp32 arena
  * (lib/utils/utils.py:61-67), one launch:
  *   g = grad * grad_scale [+ weight_decay * param];  momentum != 0: buf = momentum * buf + g, g = nesterov ? g + momentum * buf : buf;
@@ -545,6 +586,11 @@ int fpd_loss_kl(const fpd_loss_kl_t* a, fpd_stream_t stream);
 /* bytes of fpd_loss_kl_t.scratch for these dimensions (B, J, H, W, S are looked at); negative on bad dimensions */
 int64_t fpd_loss_kl_scratch_bytes(const fpd_loss_t* a);
 int fpd_adam(const fpd_adam_t* a, fpd_stream_t stream);
+int fpd_adamw(const fpd_adamw_t* a, fpd_stream_t stream);
+/* The launch fpd_adamw() makes for `a` as it stands (pure host code, nothing is dereferenced).  blocks: its grid;
+ * *vec_elems: the leading elements moved as 16-byte vectors (a multiple of 4; 0 = element by element).  Returns 0, or the
+ * error code fpd_adamw() would give. */
+int fpd_adamw_geometry(const fpd_adamw_t* a, int32_t* blocks, int64_t* vec_elems);
 /* refuses (before any launch) null param / grad, n < 0, momentum < 0, weight_decay < 0, momentum != 0 without buf, nesterov without momentum */
 int fpd_sgd(const fpd_sgd_t* a, fpd_stream_t stream);
 int fpd_ema(const fpd_ema_t* a, fpd_stream_t stream);
@@ -1053,7 +1099,8 @@ enum {
     FPD_OP_LOSS_KL = 27,        /* args: fpd_loss_kl_t */
     FPD_OP_EMA = 28,            /* args: fpd_ema_t */
     FPD_OP_GRAD_CLIP = 29,      /* args: fpd_grad_clip_t */
-    FPD_OP_GRAD_ACCUM = 30      /* args: fpd_grad_accum_t */
+    FPD_OP_GRAD_ACCUM = 30,     /* args: fpd_grad_accum_t */
+    FPD_OP_ADAMW = 31           /* args: fpd_adamw_t */
 };
 typedef struct { void* ptr; int64_t bytes; } fpd_memset_t;                 /* zero-fill */
 typedef struct { const void* table; int32_t n; int32_t dtype; int64_t max_elems; } fpd_table_t;
