@@ -2,8 +2,7 @@
 // flat fp32 arenas, `grad` and `acc`, in one of three modes -- FIRST acc = grad, ADD acc = acc + grad, FIN grad = acc * s with
 // s read from a device float.  The arithmetic is csrc/grad_accum_math.h, which a host build checks against numpy
 // (tests/test_accum_cpu.py).  8 (FIRST, FIN) or 12 (ADD) bytes move per element: no LDS, no atomics, one writer per element.
-#include "common.h"
-#include "conv_dispatch.h"
+#include "flat_stream.h"
 #include "grad_accum_math.h"
 
 namespace {
@@ -13,33 +12,12 @@ template <int MODE>
 __global__ __launch_bounds__(256) void grad_accum_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t n, int64_t nvec,
                                                          const float* __restrict__ scale_dev) {
     const float s = MODE == FPD_ACCUM_FIN ? *scale_dev : 0.0f;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const float4* i4 = reinterpret_cast<const float4*>(in);
-    float4* o4 = reinterpret_cast<float4*>(out);
-    for (int64_t i = tid; i < nvec; i += nthr) {
-        const float4 x = i4[i];
-        float4 y;
-        if (MODE == FPD_ACCUM_FIRST) {
-            y = x;
-        } else if (MODE == FPD_ACCUM_ADD) {
-            y = o4[i];
-            y.x = fpd_accum_add(y.x, x.x); y.y = fpd_accum_add(y.y, x.y);
-            y.z = fpd_accum_add(y.z, x.z); y.w = fpd_accum_add(y.w, x.w);
-        } else {
-            y.x = fpd_accum_fin(x.x, s); y.y = fpd_accum_fin(x.y, s);
-            y.z = fpd_accum_fin(x.z, s); y.w = fpd_accum_fin(x.w, s);
-        }
-        o4[i] = y;
-    }
-    for (int64_t i = 4 * nvec + tid; i < n; i += nthr) {
-        if (MODE == FPD_ACCUM_FIRST) out[i] = fpd_accum_first(in[i]);
-        else if (MODE == FPD_ACCUM_ADD) out[i] = fpd_accum_add(out[i], in[i]);
-        else out[i] = fpd_accum_fin(in[i], s);
-    }
+    if constexpr (MODE == FPD_ACCUM_ADD)
+        flat_walk(n, nvec, nullptr, [](int64_t, float& y, float x) { y = fpd_accum_add(y, x); }, out, in);
+    else
+        flat_walk(n, nvec, nullptr, [&](int64_t, float& y, float x) { y = MODE == FPD_ACCUM_FIRST ? fpd_accum_first(x) : fpd_accum_fin(x, s); },
+                  flat_out{out}, in);
 }
-
-struct byte_range { uintptr_t lo, hi; const char* name; };
-inline bool overlap(const byte_range& p, const byte_range& q) { return p.lo < q.hi && q.lo < p.hi; }
 
 }  // namespace
 
@@ -48,26 +26,20 @@ inline bool overlap(const byte_range& p, const byte_range& q) { return p.lo < q.
 int fpd_grad_accum_geometry_of(const fpd_grad_accum_t& a, int* blocks, int64_t* nvec) {
     FPD_REQUIRE(a.mode == FPD_ACCUM_FIRST || a.mode == FPD_ACCUM_ADD || a.mode == FPD_ACCUM_FIN,
                 "grad_accum: unknown mode %d (FIRST 0, ADD 1, FIN 2)", a.mode);
-    FPD_REQUIRE(a.n >= 0, "grad_accum: n = %lld is negative", (long long)a.n);
-    FPD_REQUIRE(a.n < ((int64_t)1 << 60), "grad_accum: n = %lld is too large", (long long)a.n);
+    if (const int rc = require_flat_n("grad_accum", a.n)) return rc;
     FPD_REQUIRE(a.n == 0 || (a.grad != nullptr && a.acc != nullptr), "grad_accum: null grad or acc with n = %lld", (long long)a.n);
     FPD_REQUIRE(a.mode != FPD_ACCUM_FIN || a.scale_dev != nullptr, "grad_accum: null scale_dev in mode FIN");
     FPD_REQUIRE((((uintptr_t)a.grad | (uintptr_t)a.acc | (uintptr_t)a.scale_dev) & 3) == 0,
                 "grad_accum: grad, acc or scale_dev is misaligned (4 bytes)");
-    byte_range r[3];
+    byte_range r[3];      // marked written whatever the mode: grad and acc swap roles, and nothing may lie over the scale
     int nr = 0;
     if (a.n > 0) {
-        r[nr++] = {(uintptr_t)a.grad, (uintptr_t)a.grad + 4 * (uintptr_t)a.n, "grad"};
-        r[nr++] = {(uintptr_t)a.acc, (uintptr_t)a.acc + 4 * (uintptr_t)a.n, "acc"};
+        r[nr++] = range_of(a.grad, 4 * (uint64_t)a.n, true, "grad");
+        r[nr++] = range_of(a.acc, 4 * (uint64_t)a.n, true, "acc");
     }
-    if (a.scale_dev != nullptr) r[nr++] = {(uintptr_t)a.scale_dev, (uintptr_t)a.scale_dev + 4, "scale_dev"};
-    for (int i = 0; i < nr; ++i)
-        for (int j = i + 1; j < nr; ++j)
-            FPD_REQUIRE(!overlap(r[i], r[j]), "grad_accum: %s overlaps %s", r[i].name, r[j].name);
-    const bool aligned = (((uintptr_t)a.grad | (uintptr_t)a.acc) & 15) == 0;
-    *nvec = aligned ? a.n / 4 : 0;
-    const int64_t rest = a.n - 4 * *nvec;
-    *blocks = grid_for(*nvec > rest ? *nvec : rest);
+    if (a.scale_dev != nullptr) r[nr++] = range_of(a.scale_dev, 4, true, "scale_dev");
+    if (const int rc = require_disjoint("grad_accum", r, nr)) return rc;
+    flat_geometry(a.n, (uintptr_t)a.grad | (uintptr_t)a.acc, nullptr, nvec, blocks);
     return 0;
 }
 

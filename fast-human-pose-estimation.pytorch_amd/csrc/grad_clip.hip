@@ -3,8 +3,7 @@
 // (csrc/grad_clip_math.h, which a host build checks against numpy, tests/test_clip_cpu.py), and the in-place scale, which
 // every thread leaves at once when the coefficient is exactly 1.  No atomics: each partial has one writer and the additions
 // run in a fixed order, so the result is a function of the values and the grid, and the grid of n and the base's alignment.
-#include "common.h"
-#include "conv_dispatch.h"
+#include "flat_stream.h"
 #include "grad_clip_math.h"
 
 namespace {
@@ -22,14 +21,8 @@ __device__ __forceinline__ double sq(float x) { return (double)x * (double)x; }
 
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, int64_t nvec, double* __restrict__ partial) {
     __shared__ double lds[4];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const float4* g4 = reinterpret_cast<const float4*>(g);
     double acc = 0.0;
-    for (int64_t i = tid; i < nvec; i += nthr) {
-        const float4 x = g4[i];
-        acc += sq(x.x); acc += sq(x.y); acc += sq(x.z); acc += sq(x.w);
-    }
-    for (int64_t i = 4 * nvec + tid; i < n; i += nthr) acc += sq(g[i]);
+    flat_walk(n, nvec, nullptr, [&](int64_t, float x) { acc += sq(x); }, g);      // read only: a thread's squares add up in index order
     const double s = block_sum_d(acc, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
@@ -56,34 +49,21 @@ __global__ __launch_bounds__(256) void grad_clip_final_kernel(const double* __re
 __global__ __launch_bounds__(256) void grad_scale_kernel(float* __restrict__ g, int64_t n, int64_t nvec, const float* __restrict__ out) {
     const float coef = out[1];
     if (coef == 1.0f) return;                  // not clipped (a NaN coefficient is not 1: it is written into every element)
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    float4* g4 = reinterpret_cast<float4*>(g);
-    for (int64_t i = tid; i < nvec; i += nthr) {
-        float4 x = g4[i];
-        x.x = fpd_clip_scale(x.x, coef); x.y = fpd_clip_scale(x.y, coef);
-        x.z = fpd_clip_scale(x.z, coef); x.w = fpd_clip_scale(x.w, coef);
-        g4[i] = x;
-    }
-    for (int64_t i = 4 * nvec + tid; i < n; i += nthr) g[i] = fpd_clip_scale(g[i], coef);
+    flat_walk(n, nvec, nullptr, [&](int64_t, float& x) { x = fpd_clip_scale(x, coef); }, g);
 }
-
-struct byte_range { uintptr_t lo, hi; const char* name; };
-inline bool overlap(const byte_range& p, const byte_range& q) { return p.lo < q.hi && q.lo < p.hi; }
 
 }  // namespace
 
 // Bytes of `partial` that serve an arena of n elements at any alignment: one float64 per block of the largest grid.
 int64_t fpd_grad_clip_scratch_size(int64_t n) {
-    if (n < 0) return fpd_fail(-2, "grad_clip: n = %lld is negative", (long long)n);
-    if (n >= ((int64_t)1 << 60)) return fpd_fail(-2, "grad_clip: n = %lld is too large", (long long)n);
+    if (const int rc = require_flat_n("grad_clip", n)) return rc;
     return 8 * (int64_t)grid_for(n);
 }
 
 // Validation and the launches' geometry: fpd_grad_clip_launch() below and the query fpd_grad_clip_geometry() both come
 // through here.  Pure host code: counts and addresses are looked at, nothing is dereferenced.
 int fpd_grad_clip_geometry_of(const fpd_grad_clip_t& a, int* blocks, int64_t* nvec) {
-    FPD_REQUIRE(a.n >= 0, "grad_clip: n = %lld is negative", (long long)a.n);
-    FPD_REQUIRE(a.n < ((int64_t)1 << 60), "grad_clip: n = %lld is too large", (long long)a.n);
+    if (const int rc = require_flat_n("grad_clip", a.n)) return rc;
     FPD_REQUIRE(a.n == 0 || a.grad != nullptr, "grad_clip: null grad with n = %lld", (long long)a.n);
     FPD_REQUIRE(a.out != nullptr, "grad_clip: null out");
     FPD_REQUIRE(a.partial != nullptr, "grad_clip: null partial (scratch)");
@@ -94,19 +74,14 @@ int fpd_grad_clip_geometry_of(const fpd_grad_clip_t& a, int* blocks, int64_t* nv
     FPD_REQUIRE(((uintptr_t)a.partial & 7) == 0, "grad_clip: partial is misaligned (8 bytes)");
     FPD_REQUIRE(((uintptr_t)a.out & 3) == 0 && ((uintptr_t)a.counters & 7) == 0 && ((uintptr_t)a.grad & 3) == 0,
                 "grad_clip: grad, out or counters is misaligned (4, 4 and 8 bytes)");
-    byte_range r[4];
+    byte_range r[4];      // all four are written, grad by the scale
     int nr = 0;
-    if (a.n > 0) r[nr++] = {(uintptr_t)a.grad, (uintptr_t)a.grad + 4 * (uintptr_t)a.n, "grad"};
-    r[nr++] = {(uintptr_t)a.partial, (uintptr_t)a.partial + (uintptr_t)a.partial_bytes, "partial"};
-    r[nr++] = {(uintptr_t)a.out, (uintptr_t)a.out + 8, "out"};
-    if (a.counters != nullptr) r[nr++] = {(uintptr_t)a.counters, (uintptr_t)a.counters + 24, "counters"};
-    for (int i = 0; i < nr; ++i)
-        for (int j = i + 1; j < nr; ++j)
-            FPD_REQUIRE(!overlap(r[i], r[j]), "grad_clip: %s overlaps %s", r[i].name, r[j].name);
-    const bool aligned = ((uintptr_t)a.grad & 15) == 0;
-    *nvec = aligned ? a.n / 4 : 0;
-    const int64_t rest = a.n - 4 * *nvec;
-    *blocks = grid_for(*nvec > rest ? *nvec : rest);
+    if (a.n > 0) r[nr++] = range_of(a.grad, 4 * (uint64_t)a.n, true, "grad");
+    r[nr++] = range_of(a.partial, (uint64_t)a.partial_bytes, true, "partial");
+    r[nr++] = range_of(a.out, 8, true, "out");
+    if (a.counters != nullptr) r[nr++] = range_of(a.counters, 24, true, "counters");
+    if (const int rc = require_disjoint("grad_clip", r, nr)) return rc;
+    flat_geometry(a.n, (uintptr_t)a.grad, nullptr, nvec, blocks);
     return 0;
 }
 

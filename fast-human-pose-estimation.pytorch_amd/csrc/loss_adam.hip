@@ -5,6 +5,7 @@
 // effect of nn.BatchNorm2d(momentum=0.1) (lib/models/hourglass.py:10).
 #include <algorithm>
 
+#include "flat_stream.h"
 #include "loss_common.h"
 
 namespace {
@@ -94,7 +95,6 @@ __global__ __launch_bounds__(256) void adam_kernel(const fpd_adam_t a) {
         if (lp) lp[i] = f2bf(p);
     }
 }
-__global__ void adam_tick_kernel(int64_t* step) { *step += 1; }
 
 // torch.optim.SGD(momentum, dampening 0, weight_decay, nesterov) over the flat arena, one launch.  The roundings are those of torch's
 // CPU kernels: add(other, alpha) is ONE fused multiply-add, buf.mul_(momentum).add_(g) is two operations.  buf starts at zero, which
@@ -112,36 +112,18 @@ __device__ __forceinline__ float sgd_elem(float p, float g, float& b, const sgd_
     }
     return fmaf(-c.lr, g, p);
 }
-// nvec 16-byte vectors (0 when an arena is not 16-byte aligned), then elements [4 nvec, n) one by one; 12 B read + 8 B written per element
-// (4 + 4 without momentum) against Adam's 16 + 12.  Thread 0 ticks the step counter: nothing in this launch reads it.
+// The walk over the arenas is csrc/flat_stream.h (16-byte vectors, then the tail); 12 B read + 8 B written per element (4 + 4 without
+// momentum) against Adam's 16 + 12.  Thread 0 ticks the step counter: nothing in this launch reads it.
 template <bool MOM>
 __global__ __launch_bounds__(256) void sgd_kernel(const fpd_sgd_t a, const int64_t nvec) {
     sgd_coef c = {a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov};
     if (a.lr_dev != nullptr) c.lr = *a.lr_dev;
     bf16_t* lp = reinterpret_cast<bf16_t*>(a.param_lp);
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    float4* p4 = reinterpret_cast<float4*>(a.param);
-    const float4* g4 = reinterpret_cast<const float4*>(a.grad);
-    float4* b4 = reinterpret_cast<float4*>(a.buf);
-    for (int64_t i = tid; i < nvec; i += nthr) {
-        float4 p = p4[i], b = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 g = g4[i];
-        if (MOM) b = b4[i];
-        p.x = sgd_elem<MOM>(p.x, g.x, b.x, c); p.y = sgd_elem<MOM>(p.y, g.y, b.y, c);
-        p.z = sgd_elem<MOM>(p.z, g.z, b.z, c); p.w = sgd_elem<MOM>(p.w, g.w, b.w, c);
-        if (MOM) b4[i] = b;
-        p4[i] = p;
-        if (lp) *reinterpret_cast<uint2*>(lp + 4 * i) = make_uint2(f2bf_pk(p.x, p.y), f2bf_pk(p.z, p.w));
-    }
-    for (int64_t i = 4 * nvec + tid; i < a.n; i += nthr) {
-        float b = 0.f;
-        if (MOM) b = a.buf[i];
-        const float p = sgd_elem<MOM>(a.param[i], a.grad[i], b, c);
-        if (MOM) a.buf[i] = b;
-        a.param[i] = p;
-        if (lp) lp[i] = f2bf(p);
-    }
-    if (tid == 0 && a.step_dev != nullptr) *a.step_dev += 1;
+    if constexpr (MOM)
+        flat_walk(a.n, nvec, lp, [&](int64_t, float& p, float g, float& b) { p = sgd_elem<true>(p, g, b, c); }, a.param, a.grad, a.buf);
+    else
+        flat_walk(a.n, nvec, lp, [&](int64_t, float& p, float g) { float b = 0.f; p = sgd_elem<false>(p, g, b, c); }, a.param, a.grad);
+    if (flat_tid() == 0 && a.step_dev != nullptr) *a.step_dev += 1;
 }
 
 // Working copies of the convolution weights, refreshed once per step from the fp32 masters ([K][R][S][C]): w_fwd = the same layout in
@@ -254,15 +236,14 @@ int fpd_loss_launch(const fpd_loss_t& a, hipStream_t st) {
 
 int fpd_adam_launch(const fpd_adam_t& a, hipStream_t st) {
     FPD_LAUNCH(adam_kernel, dim3(grid_for(a.n)), dim3(256), 0, st, a);
-    if (a.step_dev != nullptr) FPD_LAUNCH(adam_tick_kernel, dim3(1), dim3(1), 0, st, a.step_dev);
+    if (a.step_dev != nullptr) FPD_LAUNCH(tick_kernel, dim3(1), dim3(1), 0, st, a.step_dev);
     return 0;
 }
 
 int fpd_sgd_launch(const fpd_sgd_t& a, hipStream_t st) {
-    const uintptr_t bits = (uintptr_t)a.param | (uintptr_t)a.grad | (a.momentum != 0.f ? (uintptr_t)a.buf : 0);
-    const bool aligned = (bits & 15) == 0 && ((uintptr_t)a.param_lp & 7) == 0;
-    const int64_t nvec = aligned ? a.n / 4 : 0;
-    const int g = grid_for(std::max<int64_t>(nvec, a.n - 4 * nvec));
+    int64_t nvec = 0;
+    int g = 0;
+    flat_geometry(a.n, (uintptr_t)a.param | (uintptr_t)a.grad | (a.momentum != 0.f ? (uintptr_t)a.buf : 0), a.param_lp, &nvec, &g);
     if (a.momentum != 0.f)
         FPD_LAUNCH(sgd_kernel<true>, dim3(g), dim3(256), 0, st, a, nvec);
     else

@@ -12,6 +12,7 @@ import torch
 
 from . import graph as G
 from . import runtime as R
+from .lib.utils.utils import fill_adam_args
 from .schedule import PhaseSchedule
 
 _EW = {'bnrelu_fwd': R.EW_BNRELU_FWD, 'bnrelu_bwd_r': R.EW_BNRELU_BWD_R, 'bn_bwd_apply': R.EW_BN_BWD_APPLY,
@@ -841,15 +842,12 @@ class GraphInstance:
         return self.A.view(self.g.out_grads[i].buf)
 
 
-def _is_adamw(opt):
-    from .lib.utils.utils import FusedAdamW      # (imported here: lib.utils imports this package's runtime)
-    return isinstance(opt, FusedAdamW)
-
-
 class FusedFPDStep:
     """The fused FPD iteration (lib/core/function.py:119-147 of the reference) on one GPU:
          teacher forward (eval BN) -> student forward (train BN) -> fused pose+KD loss fwd/bwd
-         -> student backward -> [RCCL all-reduce of the flat gradient] -> flat Adam (sgd=: flat SGD instead)
+         -> student backward -> [RCCL all-reduce of the flat gradient] -> the flat optimizer update: Adam with the step's own
+         moments, or the op that the optimizer given as adam= (a lib.utils.utils.FusedAdam or FusedAdamW) or sgd= (a FusedSGD)
+         plans itself (plan_op)
          [-> ema=: the weight average of a lib.utils.utils.ModelEma, one more launch in the optimizer's range].
     clip=: a lib.utils.utils.GradClipper of the student clips the (reduced) gradient to a global L2 norm at the head of the
     optimizer's range.
@@ -948,40 +946,33 @@ class FusedFPDStep:
         n = student_state.table.sizes['param']
         self.n_param = n
         self._dist_work = None
-        if sgd is not None:         # share the momentum buffer / step / lr with a lib.utils.utils.FusedSGD; no Adam moments
-            self._add_sgd(sgd, student_state, n, ema, clip)
-            self._add_accum(student_state)
-            return
-        if adam is not None and _is_adamw(adam):    # a lib.utils.utils.FusedAdamW: one OP_ADAMW where OP_ADAM sits
-            self._add_adamw(adam, student_state, n, ema, clip)
-            self._add_accum(student_state)
-            return
-        if adam is not None:        # share moments / step / lr with a lib.utils.utils.FusedAdam (checkpointable state)
-            self.m, self.v, self.lr_dev, self.step_dev = adam.m, adam.v, adam.lr_dev, adam.step_dev
-            betas, eps = adam.param_groups[0]['betas'], adam.param_groups[0]['eps']
-        else:
+        opt = adam if adam is not None else sgd
+        if opt is not None:         # a lib.utils.utils.FusedAdam / FusedAdamW / FusedSGD: its state, step and lr are shared (checkpointable),
+            g = opt.param_groups[0]     # its hyperparameters recorded as they are NOW (core.function keys its step cache on them)
+            self.m, self.v, self.vmax, self.buf = (getattr(opt, k, None) for k in ('m', 'v', 'vmax', 'buf'))
+            self.lr_dev, self.step_dev = opt.lr_dev, opt.step_dev
+            self.betas, self.eps = g.get('betas'), g.get('eps')
+            opcode, a = opt.plan_op(student_state)
+        else:                       # Adam with moments of the step's own
             self.m = torch.zeros(n, dtype=torch.float32, device=dev)
             self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.vmax = self.buf = None
             self.lr_dev = torch.full((1,), lr, dtype=torch.float32, device=dev)
             self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.betas, self.eps = betas, eps
-        a = R.AdamT()
-        a.n = n
-        pa = student_state.A
-        a.param, a.grad = pa.tensor('param').data_ptr(), pa.tensor('grad').data_ptr()
-        a.m, a.v = self.m.data_ptr(), self.v.data_ptr()
-        a.param_lp = None
-        a.lr, a.beta1, a.beta2, a.eps = lr, betas[0], betas[1], eps
-        a.bias_corr1 = a.bias_corr2 = 1.0
-        a.grad_scale = 1.0        # the loss kernel already folds 1/world_size into the gradient
-        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
-        self._adam_args = a
-        b = len(self.student.plan)
-        self._add_clip(clip, student_state)
-        self.student.plan.add(R.OP_ADAM, a)
-        self._add_ema(ema, student_state)
-        self.student.rng['adam'] = (b, len(self.student.plan))
+            self.betas, self.eps = betas, eps
+            opcode, a = R.OP_ADAM, fill_adam_args(R.AdamT(), student_state, self.m, self.v, lr, betas, eps, self.lr_dev, self.step_dev)
+        setattr(self, {R.OP_ADAM: '_adam_args', R.OP_ADAMW: '_adamw_args', R.OP_SGD: '_sgd_args'}[opcode], a)
+        self._add_optimizer(opcode, a, clip, ema)
         self._add_accum(student_state)
+
+    def _add_optimizer(self, opcode, args, clip, ema):
+        """The optimizer range ('adam' by name whatever the optimizer, so that run / capture / phase timing need not know):
+        [clip] -> the optimizer op -> [ema]."""
+        b = len(self.student.plan)
+        self._add_clip(clip, self.student.state)
+        self.student.plan.add(opcode, args)
+        self._add_ema(ema, self.student.state)
+        self.student.rng['adam'] = (b, len(self.student.plan))
 
     def _add_accum(self, student_state):
         """accum=k > 1: three one-op ranges behind the optimizer's, over the gradient arena and an arena `acc` of the same size --
@@ -1036,49 +1027,6 @@ class FusedFPDStep:
             raise R.FpdError('FusedFPDStep: ema= averages another model than the student of this step')
         self._ema_args = a
         self.student.plan.add(R.OP_EMA, a)
-
-    def _add_adamw(self, adamw, student_state, n, ema=None, clip=None):
-        """The optimizer range = one OP_ADAMW sharing m, v, vmax, the exemption mask, lr_dev and step_dev with the FusedAdamW,
-        with the hyperparameters of its first param group as they are NOW (core.function keys its step cache on them)."""
-        g = adamw.param_groups[0]
-        self.m, self.v, self.vmax = adamw.m, adamw.v, adamw.vmax
-        self.lr_dev, self.step_dev = adamw.lr_dev, adamw.step_dev
-        self.betas, self.eps = g['betas'], g['eps']
-        words = (n + 31) // 32
-        if (adamw.m.numel() < n or adamw.v.numel() < n or (adamw.vmax is not None and adamw.vmax.numel() < n)
-                or (adamw.mask is not None and adamw.mask.numel() < words)
-                or adamw.model._flat['param'].data_ptr() != student_state.A.tensor('param').data_ptr()):
-            raise R.FpdError('FusedFPDStep: adam= is the FusedAdamW of another model than the student of this step '
-                             '(its moment arenas and mask do not cover the %d elements of this parameter arena)' % n)
-        a = adamw.adamw_args(student_state)
-        self._adamw_args = a      # (grad_scale 1: the loss kernel already folds 1/world_size into the gradient)
-        b = len(self.student.plan)
-        self._add_clip(clip, student_state)
-        self.student.plan.add(R.OP_ADAMW, a)
-        self._add_ema(ema, student_state)
-        self.student.rng['adam'] = (b, len(self.student.plan))
-
-    def _add_sgd(self, sgd, student_state, n, ema=None, clip=None):
-        """The optimizer range ('adam' by name, so that run / capture / phase timing need not know) = one OP_SGD with the
-        hyperparameters of the FusedSGD's param group as they are NOW (core.function keys its step cache on them)."""
-        g = sgd.param_groups[0]
-        self.m = self.v = None
-        self.buf, self.lr_dev, self.step_dev = sgd.buf, sgd.lr_dev, sgd.step_dev
-        a = R.SgdT()
-        a.n = n
-        pa = student_state.A
-        a.param, a.grad = pa.tensor('param').data_ptr(), pa.tensor('grad').data_ptr()
-        a.buf = self.buf.data_ptr() if self.buf is not None else None
-        a.param_lp = None
-        a.lr, a.momentum, a.weight_decay, a.nesterov = g['lr'], g['momentum'], g['weight_decay'], int(g['nesterov'])
-        a.grad_scale = 1.0        # the loss kernel already folds 1/world_size into the gradient
-        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
-        self._sgd_args = a
-        b = len(self.student.plan)
-        self._add_clip(clip, student_state)
-        self.student.plan.add(R.OP_SGD, a)
-        self._add_ema(ema, student_state)
-        self.student.rng['adam'] = (b, len(self.student.plan))
 
     def enable_metric(self, min_slots=0):
         """Per-iteration PCK of the last student map against the target, on the device (lib.core.evaluate.DeviceAccuracy).

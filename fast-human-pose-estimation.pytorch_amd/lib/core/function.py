@@ -86,14 +86,7 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
     key = (tuple(batch_shape), float(alpha), world_size, tuple(use_target_weight)) + ((tuple(ohkm),) if ohkm is not None else ())
     if kl is not None:
         key += (('kl',) + tuple(kl),)
-    is_sgd = isinstance(optimizer, FusedSGD)
-    if is_sgd:
-        g = optimizer.param_groups[0]
-        key += (('sgd', float(g['momentum']), float(g['weight_decay']), bool(g['nesterov'])),)
-    if isinstance(optimizer, FusedAdamW):      # its decay, betas and eps live in the recorded plan op, like a FusedSGD's
-        g = optimizer.param_groups[0]
-        key += (('adamw', float(g['weight_decay']), bool(optimizer.amsgrad), bool(optimizer.no_decay_norm_bias)),
-                ('betas', float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])))
+    key += getattr(optimizer, 'plan_key', tuple)()      # (an object that is none of the three keys and builds as a plain Adam did)
     if ema is not None:
         key += (('ema', float(ema.decay), bool(ema.warmup)),)
     if clip is not None:
@@ -109,7 +102,7 @@ def fused_step_for(model, tmodel, optimizer, batch_shape, alpha, world_size=1, u
                           t.cfg_hg if t is not None else None, n, h, w, alpha,
                           lr=float(optimizer.param_groups[0]['lr']), world_size=world_size,
                           use_target_weight=use_target_weight, ohkm=ohkm, kl=kl, ema=ema, clip=clip, accum=accum,
-                          **{'sgd' if is_sgd else 'adam': optimizer})
+                          **{getattr(optimizer, 'keyword', 'adam'): optimizer})
     cache[key] = (t, optimizer, step, ema, clip)
     return step
 

@@ -6,10 +6,48 @@ import torch
 from ... import runtime as R
 
 
+def fill_flat_args(a, st, lr_dev, step_dev):
+    """What fpd_adam_t, fpd_adamw_t and fpd_sgd_t share, over the arenas of the device state `st`: the parameter and gradient
+    arenas and their size, no bf16 copy, grad_scale 1 (in the fused step the loss kernel already folds 1 / world_size into the
+    gradient) and the schedule through the device scalars lr_dev / step_dev."""
+    a.n = st.table.sizes['param']
+    a.param, a.grad = st.A.tensor('param').data_ptr(), st.A.tensor('grad').data_ptr()
+    a.param_lp = None
+    a.grad_scale = 1.0
+    a.lr_dev, a.step_dev = lr_dev.data_ptr(), step_dev.data_ptr()
+    return a
+
+
+def fill_adam_args(a, st, m, v, lr, betas, eps, lr_dev, step_dev):
+    """The Adam part of an fpd_adam_t or fpd_adamw_t on top of fill_flat_args: the moment arenas and the hyperparameters, the
+    bias corrections left to the kernel (it forms them from step_dev)."""
+    fill_flat_args(a, st, lr_dev, step_dev)
+    a.m, a.v = m.data_ptr(), v.data_ptr()
+    a.lr, a.beta1, a.beta2, a.eps = lr, betas[0], betas[1], eps
+    a.bias_corr1 = a.bias_corr2 = 1.0
+    return a
+
+
 class _FlatOptimizer(torch.optim.Optimizer):
     """What FusedAdam, FusedAdamW and FusedSGD share: one param group over the model's flat arenas (FusedAdamW splits it in two
-    under its exemption), the device lr / step scalars the kernels read, and the per-parameter views of a flat state arena
-    in the reference's shapes."""
+    under its exemption), the device lr / step scalars the kernels read, the per-parameter views of a flat state arena
+    in the reference's shapes, and the seam to the fused step: plan_op() and plan_key()."""
+
+    keyword = 'adam'                             # the FusedFPDStep argument that takes this optimizer
+
+    def _check_covers(self, st, *arenas, bits=None):
+        """plan_op(st) refuses a device state whose parameter arena this optimizer's own arenas (and mask bits) do not cover."""
+        n = st.table.sizes['param']
+        if (any(t is not None and t.numel() < n for t in arenas) or (bits is not None and 32 * bits.numel() < n)
+                or self.model._flat['param'].data_ptr() != st.A.tensor('param').data_ptr()):
+            raise R.FpdError('FusedFPDStep: %s= is the %s of another model than the student of this step '
+                             '(its state arenas do not cover the %d elements of this parameter arena)'
+                             % (self.keyword, type(self).__name__, n))
+
+    def plan_key(self):
+        """What core.function keys its step cache on: the hyperparameters that live in the op plan_op() records (lr and the
+        step count travel through device scalars and are not among them)."""
+        return ()
 
     def _init_flat(self, model, defaults):
         self.model = model.module if hasattr(model, 'module') else model
@@ -53,18 +91,15 @@ class FusedAdam(_FlatOptimizer):
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
 
-    def adam_args(self):
-        st = self.model.device_state()
+    def adam_args(self, st=None):
         g = self.param_groups[0]
-        a = R.AdamT()
-        a.n = st.table.sizes['param']
-        a.param, a.grad = st.A.tensor('param').data_ptr(), st.A.tensor('grad').data_ptr()
-        a.m, a.v, a.param_lp = self.m.data_ptr(), self.v.data_ptr(), None
-        a.lr, a.beta1, a.beta2, a.eps = g['lr'], g['betas'][0], g['betas'][1], g['eps']
-        a.bias_corr1 = a.bias_corr2 = 1.0
-        a.grad_scale = 1.0
-        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
-        return a
+        return fill_adam_args(R.AdamT(), self.model.device_state() if st is None else st, self.m, self.v, g['lr'], g['betas'],
+                              g['eps'], self.lr_dev, self.step_dev)
+
+    def plan_op(self, st):
+        """(op code, filled struct) of the update over the arenas of the device state `st`, for FusedFPDStep to record."""
+        self._check_covers(st, self.m, self.v)
+        return R.OP_ADAM, self.adam_args(st)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -190,20 +225,22 @@ class FusedAdamW(_FlatOptimizer):
     def adamw_args(self, st=None):
         """The filled fpd_adamw_t over the arenas of the model's device state: hyperparameters of group 0 as they are now, the
         schedule through lr_dev / step_dev."""
-        st = self.model.device_state() if st is None else st
         g = self.param_groups[0]
-        a = R.AdamWT()
-        a.n = st.table.sizes['param']
-        a.param, a.grad = st.A.tensor('param').data_ptr(), st.A.tensor('grad').data_ptr()
-        a.m, a.v, a.param_lp = self.m.data_ptr(), self.v.data_ptr(), None
-        a.lr, a.beta1, a.beta2, a.eps = g['lr'], g['betas'][0], g['betas'][1], g['eps']
-        a.bias_corr1 = a.bias_corr2 = 1.0
-        a.grad_scale = 1.0
-        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
+        a = fill_adam_args(R.AdamWT(), self.model.device_state() if st is None else st, self.m, self.v, g['lr'], g['betas'],
+                           g['eps'], self.lr_dev, self.step_dev)
         a.weight_decay = g['weight_decay']
         a.vmax = self.vmax.data_ptr() if self.vmax is not None else None
         a.no_decay_bits = self.mask.data_ptr() if self.mask is not None else None
         return a
+
+    def plan_op(self, st):
+        self._check_covers(st, self.m, self.v, self.vmax, bits=self.mask)
+        return R.OP_ADAMW, self.adamw_args(st)
+
+    def plan_key(self):
+        g = self.param_groups[0]
+        return (('adamw', float(g['weight_decay']), bool(self.amsgrad), bool(self.no_decay_norm_bias)),
+                ('betas', float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -286,6 +323,8 @@ class FusedSGD(_FlatOptimizer):
     gamma / beta included: the reference hands model.parameters() over as one group.  lr is read from
     param_groups[0]['lr'] at every step like FusedAdam's."""
 
+    keyword = 'sgd'
+
     def __init__(self, model, lr=1e-3, momentum=0, weight_decay=0, nesterov=False):
         if lr < 0.0:
             raise ValueError('Invalid learning rate: %r' % (lr,))
@@ -301,17 +340,20 @@ class FusedSGD(_FlatOptimizer):
         self.buf = torch.zeros_like(flat) if momentum != 0 else None
         self._resumed = False                    # a loaded state carries buffers but no step count
 
-    def sgd_args(self):
-        st = self.model.device_state()
+    def sgd_args(self, st=None):
         g = self.param_groups[0]
-        a = R.SgdT()
-        a.n = st.table.sizes['param']
-        a.param, a.grad = st.A.tensor('param').data_ptr(), st.A.tensor('grad').data_ptr()
-        a.buf, a.param_lp = (self.buf.data_ptr() if self.buf is not None else None), None
+        a = fill_flat_args(R.SgdT(), self.model.device_state() if st is None else st, self.lr_dev, self.step_dev)
+        a.buf = self.buf.data_ptr() if self.buf is not None else None
         a.lr, a.momentum, a.weight_decay, a.nesterov = g['lr'], g['momentum'], g['weight_decay'], int(g['nesterov'])
-        a.grad_scale = 1.0
-        a.lr_dev, a.step_dev = self.lr_dev.data_ptr(), self.step_dev.data_ptr()
         return a
+
+    def plan_op(self, st):
+        self._check_covers(st, self.buf)
+        return R.OP_SGD, self.sgd_args(st)
+
+    def plan_key(self):
+        g = self.param_groups[0]
+        return (('sgd', float(g['momentum']), float(g['weight_decay']), bool(g['nesterov'])),)
 
     @torch.no_grad()
     def step(self, closure=None):

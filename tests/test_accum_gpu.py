@@ -89,7 +89,7 @@ def _values(n, seed):
 # ---- the kernel ----
 
 @pytest.mark.parametrize('off', [0, 1])
-@pytest.mark.parametrize('n', [0, 1, 3, 5, 255, 256, 257, 1023, 4099, 2 ** 20 + 1])
+@pytest.mark.parametrize('n', [0, 1, 3, 5, 255, 256, 257, 1023, 4099, 2 ** 20 + 1, 4 * 2 ** 20 + 23])
 def test_three_modes_are_the_restatement_bit_for_bit(n, off):
     g0, a0 = _values(n, n + off)
     op = Op(g0, np.full(n, np.nan, np.float32), off)
@@ -99,6 +99,8 @@ def test_three_modes_are_the_restatement_bit_for_bit(n, off):
         assert blocks == min(max(-(-max(vec // 4, n - vec) // 256), 1), 4096)
     if n == 2 ** 20 + 1 and off == 1:
         assert blocks * 256 < n                                   # the grid-stride loop iterates
+    if n == 4 * 2 ** 20 + 23 and off == 0:
+        assert blocks * 256 < vec // 4                            # ... and so does the loop over 16-byte vectors
     # FIRST over an accumulator full of NaN: acc is not read, the copy keeps every bit (NaN payloads, -0)
     for launch in range(2):
         g, a = op.run(K.FIRST)

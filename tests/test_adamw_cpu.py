@@ -313,6 +313,13 @@ def test_fused_step_key_and_the_optimizer_check_know_adamw(runtime):
     assert F._check_supported(FusedAdamW(model), crit, crit) == ((True, True), None)
     with pytest.raises(runtime.FpdError, match='AdamW'):
         F._check_supported(torch.optim.AdamW(model.parameters()), crit, crit)
+    # what each optimizer adds to the step-cache key: the tuples fused_step_for used to assemble per class
+    from fpd_amd.lib.utils.utils import FusedAdam, FusedSGD
+    assert FusedAdam(model, lr=1e-3, betas=(0.8, 0.9), eps=1e-6).plan_key() == ()
+    assert FusedSGD(model, lr=0.1, momentum=0.5, weight_decay=1e-4, nesterov=True).plan_key() == (('sgd', 0.5, 1e-4, True),)
+    w = FusedAdamW(model, betas=(0.8, 0.9), eps=1e-6, weight_decay=0.05, amsgrad=True, no_decay_norm_bias=True)
+    assert w.plan_key() == (('adamw', 0.05, True, True), ('betas', 0.8, 0.9, 1e-6))
+    assert all(type(x) is float for x in w.plan_key()[0][1:2] + w.plan_key()[1][1:]) and (FusedAdam.keyword, FusedAdamW.keyword, FusedSGD.keyword) == ('adam', 'adam', 'sgd')
 
 
 # ---- the C ABI ----

@@ -131,13 +131,16 @@ def test_kernel_is_the_restatement_bit_for_bit(n, offset, wd, amsgrad):
 
 
 def test_vector_loop_iterates_past_the_capped_grid():
-    """More 16-byte vectors than the capped grid has threads: a thread owns a second vector, with decay, AMSGrad and the mask."""
+    """More 16-byte vectors than the capped grid has threads: a thread owns a second vector, with decay, AMSGrad and the mask
+    (full), and with the decay alone."""
     n = GRID_CAP + 4099
     p0, grads = _general(n)
-    exempt = W.exempt_of(n, W.mask_ranges(n) + [(GRID_CAP - 2, GRID_CAP + 3)])
-    got = run_adamw(p0, grads[:2], W.LRS[:2], wd=0.25, amsgrad=True, exempt=exempt, expect_vec=GRID_CAP + 4096)
-    _assert_bits(got, W.restated(p0, grads[:2], W.LRS[:2], W.BETAS, W.EPS, 0.25, True, exempt=exempt), ('p', 'm', 'v', 'vmax'), 'past the cap')
-    assert torch.equal(SC.bits(got['lp']), SC.bits(got['p'].bfloat16())) and got['step'] == 2
+    for full in (True, False):
+        exempt = W.exempt_of(n, W.mask_ranges(n) + [(GRID_CAP - 2, GRID_CAP + 3)]) if full else None
+        got = run_adamw(p0, grads[:2], W.LRS[:2], wd=0.25, amsgrad=full, exempt=exempt, expect_vec=GRID_CAP + 4096)
+        keys = ('p', 'm', 'v') + (('vmax',) if full else ())
+        _assert_bits(got, W.restated(p0, grads[:2], W.LRS[:2], W.BETAS, W.EPS, 0.25, full, exempt=exempt), keys, 'past the cap')
+        assert torch.equal(SC.bits(got['lp']), SC.bits(got['p'].bfloat16())) and got['step'] == 2
 
 
 @pytest.mark.parametrize('offset', [0, 1])
@@ -154,20 +157,21 @@ def test_device_schedule_gives_the_bits_of_the_host_schedule_and_counts_three_st
 
 @pytest.mark.parametrize('offset', [0, 1])
 def test_mask_exempts_exactly_its_elements_on_the_vector_and_the_element_path(offset):
-    n = 4101                                                      # 1025 vectors and a one-element tail, which is exempt
-    ranges = W.mask_ranges(n)
-    assert all(hi % 4 and (lo % 4 or lo == 0) for lo, hi in ranges)                    # none on a 4- (hence 32-) element boundary
-    exempt = W.exempt_of(n, ranges)
-    p0, grads = _general(n)
-    run = lambda wd, ex: run_adamw(p0, grads, W.LRS, wd=wd, amsgrad=True, offset=offset, exempt=ex, expect_vec=4100 if offset == 0 else 0)
-    masked, full, none = run(0.25, exempt), run(0.25, None), run(0.0, None)
-    ex = torch.from_numpy(exempt)
-    for k in ('p', 'lp'):
-        assert torch.equal(SC.bits(masked[k])[ex], SC.bits(none[k])[ex]), k                # exempt: a run with weight_decay = 0
-        assert torch.equal(SC.bits(masked[k])[~ex], SC.bits(full[k])[~ex]), k              # all others: a run with no mask
-    assert not bool((masked['p'][ex] == full['p'][ex]).any())
-    _assert_bits(masked, W.restated(p0, grads, W.LRS, W.BETAS, W.EPS, 0.25, True, exempt=exempt), ('p', 'm', 'v', 'vmax'), 'masked')
-    _assert_bits(run(0.0, exempt), none, ('p', 'm', 'v', 'vmax', 'lp'), 'a mask without a decay')      # nobody reads it
+    # 4101: 1025 vectors and a one-element tail, which is exempt.  35: eight vectors and a three-element tail in the mask's second
+    # word, with elements 31 and 32 (either side of the word boundary) and 34 (inside the tail) exempt
+    for n, ranges in ((4101, W.mask_ranges(4101)), (35, [(31, 33), (34, 35)])):
+        assert all(hi % 4 and (lo % 4 or lo == 0) for lo, hi in ranges)                    # none on a 4- (hence 32-) element boundary
+        exempt = W.exempt_of(n, ranges)
+        p0, grads = _general(n)
+        run = lambda wd, ex: run_adamw(p0, grads, W.LRS, wd=wd, amsgrad=True, offset=offset, exempt=ex, expect_vec=n - n % 4 if offset == 0 else 0)
+        masked, full, none = run(0.25, exempt), run(0.25, None), run(0.0, None)
+        ex = torch.from_numpy(exempt)
+        for k in ('p', 'lp'):
+            assert torch.equal(SC.bits(masked[k])[ex], SC.bits(none[k])[ex]), k                # exempt: a run with weight_decay = 0
+            assert torch.equal(SC.bits(masked[k])[~ex], SC.bits(full[k])[~ex]), k              # all others: a run with no mask
+        assert not bool((masked['p'][ex] == full['p'][ex]).any())
+        _assert_bits(masked, W.restated(p0, grads, W.LRS, W.BETAS, W.EPS, 0.25, True, exempt=exempt), ('p', 'm', 'v', 'vmax'), 'masked')
+        _assert_bits(run(0.0, exempt), none, ('p', 'm', 'v', 'vmax', 'lp'), 'a mask without a decay')      # nobody reads it
 
 
 @pytest.mark.parametrize('amsgrad', [False, True])

@@ -255,7 +255,7 @@ def test_geometry_query_reports_the_grid_the_launch_uses(tmp_path):
     geo = [[int(t) for t in l.split()[1:]] for l in out.stdout.splitlines() if l.startswith('GEO')]
     lines = [l.rstrip('\n').split('\t') for l in open(log)]
     grids = [int(f[1]) for f in lines if f[0] == 'ema_kernel']
-    ticks = [int(f[1]) for f in lines if f[0] == 'ema_tick_kernel']
+    ticks = [int(f[1]) for f in lines if f[0] == 'tick_kernel']
     assert len(geo) == 4 and [g[0] for g in geo] == grids and ticks == [1] * 4 and len(lines) == 8      # two launches a call, nothing else
     assert all(int(f[2]) == 256 for f in lines if f[0] == 'ema_kernel') and all(g[3] == 1 for g in geo)
     assert geo[0][:3] == [1, 0, 0] and geo[1][:3] == [4, 4096, 1028] and geo[2][:3] == [17, 0, 4] and geo[3][1] // 4 > geo[3][0] * 256

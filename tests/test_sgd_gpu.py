@@ -94,6 +94,8 @@ def test_sgd_kernel_grad_scale_null_buffer_unaligned_arenas_and_capped_grid():
     _assert_exact(4099, 0.5, 0.25, True, offset=1)               # arenas 4 bytes off a 16-byte boundary: element by element
     _assert_exact(4099, 0.5, 0.25, False, offset=2)              # 8 bytes off
     _assert_exact(GRID_CAP + 4099, 0.5, 0.25, True)              # more vectors than the capped grid has threads: the loop iterates
+    _assert_exact(4099, 0.0, 0.25, False, offset=1)              # the kernel without momentum on the same two paths
+    _assert_exact(GRID_CAP + 4099, 0.0, 0.25, False)
 
 
 @pytest.mark.parametrize('nesterov', [False, True])

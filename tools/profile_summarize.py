@@ -71,7 +71,7 @@ rows_stats = sorted(all_rows, key=lambda r: int(r['Start_Timestamp']))
 adams = [i for i, r in enumerate(rows_stats) if 'adam_kernel' in r['Kernel_Name']]
 STEPS = len(adams)
 # bench.py re-times single recorded ops live after its last step (roofline.avg_us, conv_classes): not part of a step
-tail = sum(1 for r in rows_stats[adams[-1] + 1:] if 'adam_tick' not in r['Kernel_Name'])
+tail = sum(1 for r in rows_stats[adams[-1] + 1:] if 'tick_kernel' not in r['Kernel_Name'])
 rows_stats = rows_stats[:adams[-1] + 2]
 print('%d steps in the trace; %d kernel records behind the last step (live re-timing of single ops) left out' % (STEPS, tail))
 for r in rows_stats:
