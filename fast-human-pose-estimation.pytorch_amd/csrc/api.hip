@@ -230,6 +230,7 @@ int fpd_conv_pair_fused_wgrad_partials(const fpd_conv_pair_t* p, int32_t* n_a, i
 }
 
 int fpd_conv_f8_in_domain(const fpd_conv_t* c) { return (c && fpd_conv_f8_domain(*c)) ? 1 : 0; }
+int fpd_conv_f8_variant(const fpd_conv_t* a) { return a ? fpd_conv_f8_variant_of(*a) : -1; }
 
 int fpd_conv_forward_f8(const fpd_conv_f8_t* a, fpd_stream_t stream) {
     FPD_REQUIRE(a, "conv_f8: null pointer");

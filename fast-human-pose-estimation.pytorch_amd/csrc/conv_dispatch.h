@@ -94,6 +94,7 @@ int fpd_conv_mfma_launch(const fpd_conv_t& a, hipStream_t st);
 int fpd_conv_smallc_launch(const fpd_conv_t& a, hipStream_t st);
 int fpd_conv_naive_launch(const fpd_conv_t& a, hipStream_t st);
 bool fpd_conv_f8_domain(const fpd_conv_t& a);
+int fpd_conv_f8_variant_of(const fpd_conv_t& a);          // the conv_tile_f8_kernel instantiation the launch runs: TN | BK << 4, -1: declined
 int fpd_conv_tile_f8_launch(const fpd_conv_t& a, const void* w8, const float* wscale, hipStream_t st);
 int fpd_weight_quant_f8_launch(const fpd_wquant_entry_t* table, int n, hipStream_t st);
 

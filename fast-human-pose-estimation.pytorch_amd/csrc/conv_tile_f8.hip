@@ -252,13 +252,7 @@ constexpr size_t LDS_MAX = 160 * 1024;
 static int tile_rows(int W) { return std::max(1, 128 / W); }
 
 template <int TN, int BK>
-int launch_f8(const fpd_conv_t& a, const void* w8, const float* wscale, hipStream_t st) {
-    constexpr int LDB = BK + 16;
-    const int hrows = tile_rows(a.W) + a.R - 1, WP = a.W + a.R - 1;
-    const size_t tile = (((size_t)(hrows * WP + 3) * LDB + 15) & ~(size_t)15) + (size_t)2 * 32 * TN * LDB;
-    const size_t epi = std::max((size_t)128 * (32 * TN + 4) * sizeof(float), (size_t)4 * 32 * TN * 2 * sizeof(double));
-    const size_t lds = (size_t)(2 * a.C + 4 * 32 * TN) * sizeof(float) + std::max(tile, epi);
-    if (lds > LDS_MAX) return 1;
+int launch_f8(const fpd_conv_t& a, const void* w8, const float* wscale, size_t lds, hipStream_t st) {
     static LdsAttr configured;        // per device, set once (thread-safe: common.h)
     if (int rc_ = configured.ensure(reinterpret_cast<const void*>(&conv_tile_f8_kernel<TN, BK>), lds)) return rc_;
     TileGeo8 g;
@@ -268,16 +262,6 @@ int launch_f8(const fpd_conv_t& a, const void* w8, const float* wscale, hipStrea
     dim3 grid(cdiv(a.N * a.H, g.nrows), cdiv(a.K, 32 * TN));
     FPD_LAUNCH((conv_tile_f8_kernel<TN, BK>), grid, dim3(256), lds, st, a, reinterpret_cast<const f8_t*>(w8), wscale, g);
     return 0;
-}
-
-template <int BK>
-int launch_f8_tn(const fpd_conv_t& a, const void* w8, const float* wscale, hipStream_t st) {
-    const int mt = cdiv(a.N * a.H, tile_rows(a.W));
-    int tn = a.K > 64 ? 4 : (a.K > 32 ? 2 : 1);
-    while (tn > 1 && mt * cdiv(a.K, 32 * tn) < 128) tn >>= 1;
-    if (tn == 4) return launch_f8<4, BK>(a, w8, wscale, st);
-    if (tn == 2) return launch_f8<2, BK>(a, w8, wscale, st);
-    return launch_f8<1, BK>(a, w8, wscale, st);
 }
 
 }  // namespace
@@ -293,11 +277,42 @@ bool fpd_conv_f8_domain(const fpd_conv_t& a) {
     return (tile_rows(a.W) + a.R - 1) * a.W * (bk / 8) <= 2048;       // the halo fits the 8 staging vectors per thread
 }
 
+// The instantiation that serves `a` -- the ONE statement of the choice: the launch below walks it, fpd_conv_f8_variant() reports
+// it.  BK: 64 channels a chunk where C allows; TN: 4 / 2 / 1 accumulator tiles of 32 output channels by K, halved while the grid
+// stays under 128 blocks.  false: outside the domain (or over the LDS, which no shape of the domain is).
+struct F8Route { int tn, bk; size_t lds; };
+static bool f8_route(const fpd_conv_t& a, F8Route& r) {
+    if (!fpd_conv_f8_domain(a)) return false;
+    r.bk = (a.C % 64 == 0) ? 64 : 32;
+    const int mt = cdiv(a.N * a.H, tile_rows(a.W));
+    r.tn = a.K > 64 ? 4 : (a.K > 32 ? 2 : 1);
+    while (r.tn > 1 && mt * cdiv(a.K, 32 * r.tn) < 128) r.tn >>= 1;
+    const int LDB = r.bk + 16;
+    const int hrows = tile_rows(a.W) + a.R - 1, WP = a.W + a.R - 1;
+    const size_t tile = (((size_t)(hrows * WP + 3) * LDB + 15) & ~(size_t)15) + (size_t)2 * 32 * r.tn * LDB;
+    const size_t epi = std::max((size_t)128 * (32 * r.tn + 4) * sizeof(float), (size_t)4 * 32 * r.tn * 2 * sizeof(double));
+    r.lds = (size_t)(2 * a.C + 4 * 32 * r.tn) * sizeof(float) + std::max(tile, epi);
+    return r.lds <= LDS_MAX;
+}
+
+// TN | BK << 4, -1: declined
+int fpd_conv_f8_variant_of(const fpd_conv_t& a) {
+    F8Route r;
+    return f8_route(a, r) ? (r.tn | r.bk << 4) : -1;
+}
+
 // 1 = outside the domain
 int fpd_conv_tile_f8_launch(const fpd_conv_t& a, const void* w8, const float* wscale, hipStream_t st) {
-    if (!fpd_conv_f8_domain(a)) return 1;
-    if (a.C % 64 == 0) return launch_f8_tn<64>(a, w8, wscale, st);
-    return launch_f8_tn<32>(a, w8, wscale, st);
+    F8Route r;
+    if (!f8_route(a, r)) return 1;
+    switch (r.tn | r.bk << 4) {
+        case 4 | 64 << 4: return launch_f8<4, 64>(a, w8, wscale, r.lds, st);
+        case 2 | 64 << 4: return launch_f8<2, 64>(a, w8, wscale, r.lds, st);
+        case 1 | 64 << 4: return launch_f8<1, 64>(a, w8, wscale, r.lds, st);
+        case 4 | 32 << 4: return launch_f8<4, 32>(a, w8, wscale, r.lds, st);
+        case 2 | 32 << 4: return launch_f8<2, 32>(a, w8, wscale, r.lds, st);
+        default: return launch_f8<1, 32>(a, w8, wscale, r.lds, st);
+    }
 }
 
 int fpd_weight_quant_f8_launch(const fpd_wquant_entry_t* table, int n, hipStream_t st) {

@@ -331,6 +331,7 @@ SYMBOLS = {
     'fpd_conv_forward_pair': (C.c_int, [C.POINTER(ConvPairT), _vp]),
     'fpd_conv_forward_f8': (C.c_int, [C.POINTER(ConvF8T), _vp]),
     'fpd_conv_f8_in_domain': (C.c_int, [C.POINTER(ConvT)]),
+    'fpd_conv_f8_variant': (C.c_int, [C.POINTER(ConvT)]),
     'fpd_weight_quant_f8': (C.c_int, [_vp, _i32, _vp]),
     'fpd_bottleneck_forward': (C.c_int, [C.POINTER(BneckT), _vp]),
     'fpd_bottleneck_fold': (C.c_int, [C.POINTER(BneckT), _vp]),

@@ -655,6 +655,10 @@ typedef struct {
 } fpd_conv_f8_t;
 int fpd_conv_forward_f8(const fpd_conv_f8_t* a, fpd_stream_t stream);
 int fpd_conv_f8_in_domain(const fpd_conv_t* c);   /* 1 = the fp8 kernel takes this shape, 0 = falls back to c.w */
+/* The instantiation of the fp8 kernel (csrc/conv_tile_f8.hip, compiled for TN in {1, 2, 4} accumulator tiles of 32 output
+ * channels x BK in {32, 64} channels a chunk) that would run this launch, decided by the route function the launch walks.
+ * Pure host code, nothing is dereferenced.   TN | BK << 4,   or -1 exactly where fpd_conv_f8_in_domain() is 0. */
+int fpd_conv_f8_variant(const fpd_conv_t* a);
 
 /* fp32 master weights -> e4m3 + per-output-channel scale (amax / 448; 1 for an all-zero row), one launch for a table. */
 typedef struct {

@@ -100,8 +100,10 @@ def test_round2_entry_points_validate_their_arguments_without_a_device(runtime):
     c8.w8, c8.w8_scale = 24, 32                               # e4m3 weights must be 16-byte aligned
     assert lib.fpd_conv_forward_f8(c8, None) != 0 and 'aligned' in err()
     assert lib.fpd_conv_f8_in_domain(c) == 1
+    assert lib.fpd_conv_f8_variant(c) == 1 | 32 << 4          # TN | BK << 4: K = 32 is one accumulator tile, C = 32 one chunk of 32
     c.stride, c.P, c.Q = 2, 4, 4
     assert lib.fpd_conv_f8_in_domain(c) == 0
+    assert lib.fpd_conv_f8_variant(c) == -1 and lib.fpd_conv_f8_variant(None) == -1
     assert lib.fpd_weight_quant_f8(None, 3, None) != 0 and 'null table' in err()
     p = lib.fpd_plan_create()
     assert lib.fpd_plan_add(p, R.OP_CONV_F8, R.C.byref(c8), R.C.sizeof(c8)) == 0
